@@ -7,7 +7,13 @@ One *step* = one pass of the valuation hot path over one batch: the reference's
 batch, all kernels on device-resident inputs (synthetic data, cfg2 of BASELINE.json:
 10k games, ~16M actions per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--games G]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--games G] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line; ``--dump-outputs``
+also writes a seeded sample of the last step's outputs as ``DIR/<name>.npy``.  ``--full`` adds
+everything else: the parity check of the timed buffers against the numpy oracle, the
+``--rotate`` figure, the side entries (cfg3, cfg5, conversion, device rate, end to end) and
+the CPU baseline.
 
 N > 1 runs one rank per GPU under torch.distributed.run; each rank values its own
 10k games (weak scaling, no data-path collective) and rank 0 prints ONE JSON line.
@@ -977,6 +983,50 @@ def cpu_baseline(d, seconds: float) -> dict:
                       f'game + xT 16x12 fit + rate), numpy oracle, 1 thread, {dt:.1f} s'}
 
 
+DUMP_ROWS_WIDE = 8192      # sampled rows of the 568 feature columns (~21 MB)
+DUMP_ROWS_NARROW = 262144  # sampled rows of labels, formula values and xT rates (~11 MB)
+
+
+def dump_rows(n: int, k: int, seed: int = 2026) -> np.ndarray:
+    """The dumped rows of an ``n``-row output: all of them, or the first, the last and k - 2
+    seeded random ones (sorted; fixed by n, k and the seed)."""
+    if n <= k:
+        return np.arange(n)
+    rest = np.random.default_rng([seed, n, k]).choice(np.arange(1, n - 1), k - 2, replace=False)
+    return np.sort(np.concatenate(([0, n - 1], rest)))
+
+
+def dump_outputs(path: str, out, lab_buf, val, xt_last, n: int, rate: bool = True) -> None:
+    """--dump-outputs: what the last timed step left in the buffers a caller of the step reads,
+    as ``path/<name>.npy`` (float32 for bools and labels, float64 otherwise; rows x columns for
+    the feature blocks), every value finite.  The big outputs are sampled by row (dump_rows),
+    under 64 MB in all."""
+    os.makedirs(path, exist_ok=True)
+    dev = val.device
+    wide = torch.from_numpy(dump_rows(n, DUMP_ROWS_WIDE)).to(dev)
+    narrow = torch.from_numpy(dump_rows(n, DUMP_ROWS_NARROW)).to(dev)
+
+    def save(name, t, dtype):
+        np.save(os.path.join(path, name + '.npy'), t.cpu().numpy().astype(dtype))
+    for name, blk, dtype in (('features_bool', out.bool_block, np.float32),
+                             ('features_f64', out.f64_block, np.float64),
+                             ('features_i64', out.i64_block, np.float64)):
+        R = blk.shape[2]  # tiled column-major [n_tiles, n_cols, R]: row r = (r // R, :, r % R)
+        save(name, blk[wide // R, :, wide % R], dtype)
+    save('labels', lab_buf[:2][:, narrow], np.float32)  # scores, concedes
+    save('values', val[:, narrow], np.float64)  # offensive, defensive, vaep value
+    sol = xt_last['sol']
+    save('xt_surface', sol.mats[3].reshape(12, 16), np.float64)
+    save('xt_iterations', torch.tensor([_iterations(sol)]), np.float64)
+    if rate:  # (--xt-source coords rates into a tensor of its own, which the step drops)
+        # the rate is NaN for every action but a successful move (ExpectedThreat.rate); the files
+        # hold finite numbers only, so: which rows are rated (1 / 0), and the rates with 0 elsewhere
+        r = xt_last['rate'][narrow]
+        rated = ~torch.isnan(r)
+        save('xt_rated', rated, np.float32)
+        save('xt_rate', torch.where(rated, r, torch.zeros_like(r)), np.float64)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -988,7 +1038,7 @@ def main() -> None:
     ap.add_argument('--games', type=int, default=10000, help='games per GPU (cfg2: 10k)')
     ap.add_argument('--cpu-seconds', type=float, default=15.0)
     ap.add_argument('--rotate', type=int, default=2,
-                    help='also time the step over K device copies of the batch in turn (K >= 2; '
+                    help='--full: also time the step over K device copies of the batch in turn (K >= 2; '
                          '0: skip): the figure without cross-step Infinity Cache reuse')
     ap.add_argument('--e2e-games', type=int, default=1000,
                     help='games of the end-to-end (pandas in -> pandas out) side entry (0: skip)')
@@ -997,7 +1047,7 @@ def main() -> None:
                     help='dev A/B only: skip the parity check of the timed buffers (the line '
                          'then carries no "parity" field)')
     ap.add_argument('--no-side', action='store_true',
-                    help='skip the cfg3 (atomic) and cfg5 (xT 105x68) side measurements')
+                    help='--full: skip the cfg3 (atomic) and cfg5 (xT 105x68) side measurements')
     ap.add_argument('--cfg5-games', type=int, default=62500,
                     help='games of the cfg5 side entry (BASELINE cfg5: 62,500 = 1.0e8 actions, '
                          'split over the ranks; 0 = the step batch)')
@@ -1061,6 +1111,17 @@ def main() -> None:
                     help='output blocks: contig = the bool block in physically contiguous VRAM '
                          '(default; profiles/r02u_goalscore_fused_ab.md r02aq - r02au), else '
                          'placement A/B knobs (bool-first = three caching-allocator blocks)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run everything else the benchmark measures or '
+                         'checks: the parity check of the timed buffers against the oracle, the '
+                         '--rotate figure, the cfg3 / cfg5 / conversion / device-rate / end-to-end '
+                         'side entries and the CPU baseline (each still switched by its own option). '
+                         'Without it the run sets up, warms up, times the steps and prints the line')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps write what the last step computed (a fixed, seeded '
+                         'sample of rows of the feature blocks, labels, formula values and xT rates, '
+                         'and the xT surface) as DIR/<name>.npy (rank 0; finite values only: the '
+                         'rate\'s NaNs as xt_rated.npy beside zeroed rates)')
     args = ap.parse_args()
     EVENTS['kind'] = args.events
     if args.gpus < 1:
@@ -1288,22 +1349,24 @@ def main() -> None:
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    evs = [[[_event(True), _event(True)] for _ in range(nv + 1)] for _ in range(args.steps)]
+    # per-launch HIP events on every `--event-every`-th step of the timed region (each record is
+    # a marker between the kernels; the step's own launches keep their back-to-back order on the
+    # other steps): the kernels' mean durations are the mean over the sampled steps
+    sampled = {k: [[_event(True), _event(True)] for _ in range(nv + 1)]
+               for k in range(0, args.steps, max(1, args.event_every))}
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    # per-launch HIP events on every `--event-every`-th step of the timed region (each record is
-    # a marker between the kernels; the step's own launches keep their back-to-back order on the
-    # other steps): the kernels' mean durations are the mean over the sampled steps
-    sampled = [k for k in range(args.steps) if k % max(1, args.event_every) == 0]
     for k in range(args.steps):
-        step(evs[k] if k in sampled else None)
+        step(sampled.get(k))
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
     wall = time.perf_counter() - t0
-    evs = [evs[k] for k in sampled]
+    evs = list(sampled.values())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, lab_buf, val, xt_last, n, rate=base['xt'] != 'coords')
     kern = {name: float(np.mean([e[i][0].elapsed_time(e[i][1]) for e in evs]))
             for i, name in enumerate(order)}
     kern['xt_fit_rate'] = float(np.mean([e[nv][0].elapsed_time(e[nv][1]) for e in evs]))
@@ -1311,7 +1374,8 @@ def main() -> None:
     if dist:
         wall = _reduce(dist, wall, dist.ReduceOp.MAX, dev)
         total_actions = int(_reduce(dist, n, dist.ReduceOp.SUM, dev))
-    check = not args.no_check
+    # everything below the timed steps that takes a run or a check of its own is --full's
+    check = args.full and not args.no_check
     par = Parity()
     if check:  # outside the timed region: the last timed step's own buffers vs the oracle
         tc = time.perf_counter()
@@ -1324,7 +1388,7 @@ def main() -> None:
         par.merge(dist, dev)
         check_s = time.perf_counter() - tc
     rotate = None
-    if args.rotate >= 2:  # the same step over K device copies of the batch, one per step in turn
+    if args.full and args.rotate >= 2:  # the same step over K device copies of the batch in turn
         rotate = rotate_extra(args, dist, dev, d, ps, pc, inp, step, n, total_actions, world)
     extra_side = {}
 
@@ -1337,7 +1401,7 @@ def main() -> None:
             import traceback
             traceback.print_exc()
             extra_side[name] = {'error': f'{type(e).__name__}: {e}'}
-    if not args.no_side:
+    if args.full and not args.no_side:
         # cfg3 first: its bool block wants a physically contiguous range, which cfg5's ~1e8
         # actions of device batches (allocated and freed by its entry) would fragment
         side('atomic_cfg3', lambda: atomic_extra(dist, rank, world, dev, args.atomic_games, check=check))
@@ -1459,7 +1523,7 @@ def main() -> None:
                                    'xT 16x12 counts the step solved from, its surface and '
                                    'iteration count, and its rate of the sampled games')
     line.update(extra_side)
-    if not args.no_cpu and world == 1:  # the CPU comparator runs on rank 0 at N = 1 only
+    if args.full and not args.no_cpu and world == 1:  # the CPU comparator: rank 0 at N = 1 only
         line['cpu_baseline'] = cpu_baseline(d, args.cpu_seconds)
         ref = reference_cpu_record()
         if ref is not None:

@@ -4,8 +4,9 @@
 # retries).  Outputs land in gpurun_out/TAG_*.
 #   tests[:A,B,..]    python -m pytest tests -m gpu (-k "A or B")    -> TAG_gpu_tests.log
 #   smoke             __graft_entry__.smoke()                      -> TAG_smoke.log
-#   bench[:ARGS]      python bench.py ARGS (commas = spaces)       -> TAG_bench.json / .err
-#   prof              scripts/profile_round.sh TAG 10 (trace + PMC) -> gpurun_out/prof_TAG_*
+#   bench[:ARGS]      python bench.py ARGS (commas = spaces; --full for the parity check and
+#                     the side entries)                            -> TAG_bench.json / .err
+#   prof              scripts/profile_round.sh TAG 10 (trace + PMC) -> $PROFILE_OUT/prof_TAG_*
 #   py:SCRIPT[:ARGS]  python scripts/SCRIPT ARGS (commas = spaces) -> TAG_SCRIPT.log
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-.}"

@@ -2,13 +2,14 @@
 
     python scripts/summarize_profile.py r01 [N_ACTIONS]
 
-Reads gpurun_out/prof_<tag>_{trace,fetch,write}/ (see scripts/profile_round.sh) and writes
+Reads $PROFILE_OUT/prof_<tag>_{trace,fetch,write}/ (default prof_out/, as
+scripts/profile_round.sh) and writes
   profiles/<tag>_kernel_stats.csv   rocprofv3 --kernel-trace --stats summary of the step alone
-  profiles/<tag>_side_kernel_stats.csv   the same with bench.py's side entries
+  profiles/<tag>_side_kernel_stats.csv   the same with bench.py --full's side entries
   profiles/<tag>_pmc.csv            per-kernel mean FETCH_SIZE / WRITE_SIZE (KiB) + HBM bytes
   profiles/pmc_dominant_kernel.json HBM bytes per action of the dominant kernel (read by bench.py,
                                     which quotes them only while the loaded library's build id
-                                    equals the profiled one, gpurun_out/prof_<tag>_build_id.txt)
+                                    equals the profiled one, prof_<tag>_build_id.txt)
 HBM bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024: on gfx950 FETCH_SIZE reports half the
 bytes of wide streaming reads (MI355X_MICROARCH.md, HBM section); WRITE_SIZE is exact for
 16-byte-per-lane streaming stores.
@@ -25,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main(tag: str, n_actions: int, dominant=None) -> None:
     out = os.path.join(ROOT, 'profiles')
-    src = os.path.join(ROOT, 'gpurun_out')
+    src = os.path.join(ROOT, os.environ.get('PROFILE_OUT', 'prof_out'))
     shutil.copy(os.path.join(src, f'prof_{tag}_trace', 'run_kernel_stats.csv'),
                 os.path.join(out, f'{tag}_kernel_stats.csv'))
     side = os.path.join(src, f'prof_{tag}_side', 'run_kernel_stats.csv')

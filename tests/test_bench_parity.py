@@ -1,6 +1,6 @@
 """bench.py's parity check of the timed buffers (CPU): fed the oracle's own outputs laid out as
 the device blocks it passes, and a single changed bool / int / float / count / surface value
-makes it fail. The GPU side of the same check runs inside every bench.py line."""
+makes it fail. The GPU side of the same check runs inside every bench.py --full line."""
 import os
 import sys
 from types import SimpleNamespace
@@ -124,6 +124,47 @@ def test_xt_check_passes_and_catches_one_count():
     par = bench.Parity()
     bench.check_xt_rate(par, d, r2, ref)
     assert not par.ok
+
+
+def test_dump_outputs_writes_the_sampled_rows(tmp_path, monkeypatch):
+    """--dump-outputs: the files hold the sampled rows of the buffers (untiled, rows x columns),
+    float32 / float64 only, the same rows on every call; first and last row always among them."""
+    rows = bench.dump_rows(16_000_000, bench.DUMP_ROWS_WIDE)
+    assert len(rows) == bench.DUMP_ROWS_WIDE == len(set(rows.tolist()))
+    assert rows[0] == 0 and rows[-1] == 15_999_999 and (np.diff(rows) > 0).all()
+    assert (rows == bench.dump_rows(16_000_000, bench.DUMP_ROWS_WIDE)).all()
+    assert (bench.dump_rows(5, 8) == np.arange(5)).all()
+    d = synthetic.spadl_games(3, mean_actions=700)
+    n = int(d['game_off'][-1])
+    p = synthetic.probabilities(n)
+    out = _blocks(d)
+    sc, co, val = _labels_formula(d, p)
+    lab_buf = torch.stack([sc, co, torch.zeros_like(sc)])
+    fit = xo.fit({c: d[c] for c in ('start_x', 'start_y', 'end_x', 'end_y', 'type_id', 'result_id')}, 16, 12)
+    rate = torch.from_numpy(xo.rate({c: d[c] for c in ('start_x', 'start_y', 'end_x', 'end_y',
+                                                         'type_id', 'result_id')}, fit['xT']))
+    mats = torch.zeros((4, 192), dtype=torch.float64)
+    mats[3] = torch.from_numpy(fit['xT'].reshape(-1).copy())
+    last = {'sol': SimpleNamespace(mats=mats, n_iter=len(fit['heatmaps']) - 1), 'rate': rate}
+    monkeypatch.setattr(bench, 'DUMP_ROWS_WIDE', 100)
+    monkeypatch.setattr(bench, 'DUMP_ROWS_NARROW', 500)
+    bench.dump_outputs(str(tmp_path), out, lab_buf, val, last, n)
+    got = {f[:-4]: np.load(tmp_path / f) for f in sorted(os.listdir(tmp_path))}
+    assert sorted(got) == ['features_bool', 'features_f64', 'features_i64', 'labels', 'values',
+                           'xt_iterations', 'xt_rate', 'xt_rated', 'xt_surface']
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+    wide, narrow = bench.dump_rows(n, 100), bench.dump_rows(n, 500)
+    blocks = {k: out.rows(k, 0, n).numpy() for k in 'bfi'}
+    for k, name in zip('bfi', ('features_bool', 'features_f64', 'features_i64')):
+        assert np.array_equal(got[name], blocks[k][:, wide].T.astype(got[name].dtype), equal_nan=True)
+    assert np.array_equal(got['labels'], np.stack([sc.numpy(), co.numpy()])[:, narrow])
+    assert np.array_equal(got['values'], val.numpy()[:, narrow])
+    # the rate's NaNs (every action but a successful move) as a 1 / 0 column beside zeroed rates
+    want = rate.numpy()[narrow]
+    assert np.isnan(want).any() and not np.isnan(want).all()
+    assert np.array_equal(got['xt_rated'], (~np.isnan(want)).astype(np.float32))
+    assert np.array_equal(got['xt_rate'], np.where(np.isnan(want), 0.0, want))
+    assert np.array_equal(got['xt_surface'], fit['xT']) and got['xt_iterations'][0] == last['sol'].n_iter
 
 
 def test_sample_games_covers_first_and_last():

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_gpus_2_launches_two_ranks():
     env = dict(os.environ, SA_DIST_BACKEND='gloo')
     env.pop('WORLD_SIZE', None)
-    p = subprocess.run([sys.executable, 'bench.py', '--gpus', '2', '--games', '20', '--steps', '2',
+    p = subprocess.run([sys.executable, 'bench.py', '--full', '--gpus', '2', '--games', '20', '--steps', '2',
                         '--warmup', '1', '--no-side', '--no-cpu'], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=240)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
@@ -37,7 +37,7 @@ def test_bench_gpus_2_side_entries(solve):
     (counts or surface, iterations, rates vs the oracle) ok either way."""
     env = dict(os.environ, SA_DIST_BACKEND='gloo')
     env.pop('WORLD_SIZE', None)
-    p = subprocess.run([sys.executable, 'bench.py', '--gpus', '2', '--games', '20', '--steps', '2',
+    p = subprocess.run([sys.executable, 'bench.py', '--full', '--gpus', '2', '--games', '20', '--steps', '2',
                         '--warmup', '1', '--no-cpu', '--cfg5-games', '45', '--atomic-games', '30',
                         '--e2e-games', '5', '--cfg5-solve', solve], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=240)
@@ -69,6 +69,43 @@ def test_bench_gpus_2_side_entries(solve):
     assert a['parity']['ok']
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain ``bench.py --gpus 1 --steps K --warmup W`` times the steps and prints the headline
+    fields only: no parity check, rotate figure, side entry or CPU baseline (those are --full's);
+    ``--dump-outputs`` writes the last step's sampled outputs as float .npy files."""
+    env = dict(os.environ)
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'SA_BENCH_DIST'):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--games', '20', '--steps', '3',
+                        '--warmup', '1', '--dump-outputs', str(tmp_path / 'o')], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=120)
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
+    assert p.returncode == 0 and len(lines) == 1, p.stdout[-2000:] + p.stderr[-3000:]
+    out = json.loads(lines[0])
+    assert out['steps'] == 3 and out['warmup'] == 1 and out['n_gpus'] == 1
+    assert out['value'] > 0 and out['ms_per_step'] > 0 and out['unit'] == 'actions/s'
+    assert out['higher_is_better'] is True and out['dtype'] == 'f64' and out['metric']
+    n = out['config']['actions_per_gpu']
+    assert abs(out['value'] - n / out['ms_per_step'] * 1e3) <= 1e-2 * out['value']  # ms: 4 decimals
+    for moved in ('parity', 'rotate', 'cpu_baseline', 'atomic_cfg3', 'xt105_cfg5',
+                  'convert_to_atomic', 'rate_on_device', 'end_to_end'):
+        assert moved not in out, moved
+    import numpy as np
+    got = {f[:-4]: np.load(tmp_path / 'o' / f) for f in os.listdir(tmp_path / 'o')}
+    assert sorted(got) == ['features_bool', 'features_f64', 'features_i64', 'labels', 'values',
+                           'xt_iterations', 'xt_rate', 'xt_rated', 'xt_surface']
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    k = min(n, 8192)
+    assert got['features_bool'].shape == (k, 515) and set(np.unique(got['features_bool'])) <= {0.0, 1.0}
+    assert got['features_f64'].shape == (k, 47) and got['features_i64'].shape == (k, 6)
+    assert got['labels'].shape == (2, n) and got['values'].shape == (3, n)
+    # the rate: NaN for every action but a successful move, dumped as a 1 / 0 column + zeroed rates
+    assert got['xt_rate'].shape == got['xt_rated'].shape == (n,)
+    assert set(np.unique(got['xt_rated'])) == {0.0, 1.0} and (got['xt_rate'][got['xt_rated'] == 0] == 0).all()
+    assert got['xt_surface'].shape == (12, 16) and got['xt_iterations'][0] > 0
+
+
 def test_bench_rccl_one_rank_every_entry():
     """bench.py's process-group path through REAL RCCL (backend nccl) with one rank on the test
     GPU (SA_BENCH_DIST=1 under torch.distributed.run): the step's all-reduce of the xT counts,
@@ -78,7 +115,7 @@ def test_bench_rccl_one_rank_every_entry():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'SA_DIST_BACKEND'):
         env.pop(k, None)
     p = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1',
-                        '--master-addr', '127.0.0.1', '--master-port', '29533', 'bench.py', '--gpus', '1',
+                        '--master-addr', '127.0.0.1', '--master-port', '29533', 'bench.py', '--full', '--gpus', '1',
                         '--games', '20', '--steps', '2', '--warmup', '1', '--no-cpu', '--cfg5-games', '45',
                         '--atomic-games', '30', '--e2e-games', '5'], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=280)
