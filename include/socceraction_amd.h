@@ -697,6 +697,42 @@ int sa_tree_predict_staged(const sa_tree_model* model, const int32_t* bool_cols,
                            const sa_block* f64_blk, const sa_block* i64_blk, int64_t n, int32_t le,
                            int32_t f32, void* stream);
 
+/* ---- grouped sums (rating tables) --------------------------------------------- */
+/* Order-independent grouped sums: A.groupby(key)[values].sum() of the reference's notebooks
+ * (public-notebooks/4-compute-vaep-values-and-top-players.ipynb), the same bit for bit from run
+ * to run, for any chunking, batch split, row order or device count.  A finite value v of column
+ * c (contract |v| < 2^scale_exp[c]) is quantised to Q = trunc(v * 2^(95 - scale_exp[c])), taken
+ * from its mantissa and exponent bits, split into three limbs of 32 magnitude bits that carry
+ * v's sign, and each limb is added as an integer: limbs[g][c][0..2] = sums of m0, m1, m2 with
+ * Q = s * (m2 * 2^64 + m1 * 2^32 + m0) (csrc/sa_fixed.h).  Fewer than 2^30 rows may be summed
+ * into one table.
+ * sa_group_sums ADDS the rows of one batch to caller-zeroed tables: key [n] int32 group codes
+ * (-1 skips the row, as pandas drops NaN keys; any other code outside [0, n_groups) sets
+ * SA_GROUP_ERR_KEY), cols [host] n_cols device columns of n values, all f64 (f32 = 0) or all f32
+ * (widened exactly), scale_exp [host] one exponent in [-900, 900] per column, limbs
+ * [n_groups][n_cols][3] int64, count [n_groups] int64 rows per group, err one uint32 of
+ * SA_GROUP_ERR_* bits (OR-ed in).  NaN adds nothing to its column (the row still counts); +-inf
+ * sets SA_GROUP_ERR_NONFINITE, |v| >= 2^scale_exp SA_GROUP_ERR_RANGE, and a row that sets an
+ * error bit adds nothing, its count included.  Each workgroup sums chunks of
+ * SA_GROUP_CHUNK_ROWS rows in an LDS table of SA_GROUP_LDS_SLOTS slots (the slot is the code
+ * when n_groups <= SA_GROUP_LDS_SLOTS, else (code * SA_GROUP_HASH_MUL mod 2^32) >> 24 with
+ * linear probing) and flushes it with 64-bit integer atomics when a chunk ends or the table is
+ * more than half full.  Columns aligned to 16 bytes are read with 16-byte loads.
+ * sa_group_finalize: out [n_cols][n_groups] f64, each total rounded once (nearest, ties to even)
+ * and scaled by 2^(scale_exp - 95). */
+#define SA_GROUP_MAX_COLS 8
+#define SA_GROUP_LDS_SLOTS 256
+#define SA_GROUP_CHUNK_ROWS 8192
+#define SA_GROUP_HASH_MUL 2654435761u
+#define SA_GROUP_ERR_KEY 1
+#define SA_GROUP_ERR_NONFINITE 2
+#define SA_GROUP_ERR_RANGE 4
+int sa_group_sums(const int32_t* key, const void* const* cols, int32_t n_cols, int32_t f32,
+                  int64_t n, int32_t n_groups, const int32_t* scale_exp, int64_t* limbs,
+                  int64_t* count, uint32_t* err, void* stream);
+int sa_group_finalize(const int64_t* limbs, int32_t n_groups, int32_t n_cols,
+                      const int32_t* scale_exp, double* out, void* stream);
+
 /* ---- runtime ------------------------------------------------------------------ */
 int sa_abi_version(void);
 const char* sa_last_error(void);

@@ -31,6 +31,11 @@ SA_XT_SOLVE_EXACT = 1  # sa_xt_solve_ex / sa_xt_solve_compact: the reference's s
 XT_SOLVE_PATHS = ('sequential', 'reordered', 'inside-bound', 'unavailable', 'timeout')
 SA_BOOL_TILE_QUANTUM = 1024
 SA_NUM_TILE_QUANTUM = 128
+SA_GROUP_MAX_COLS = 8
+SA_GROUP_LDS_SLOTS = 256  # slots of the grouped sums' LDS table
+SA_GROUP_CHUNK_ROWS = 8192
+SA_GROUP_HASH_MUL = 2654435761
+SA_GROUP_ERR_KEY, SA_GROUP_ERR_NONFINITE, SA_GROUP_ERR_RANGE = 1, 2, 4
 SA_OK, SA_EINVAL, SA_EHIP, SA_EDATA, SA_ENOMEM = 0, -1, -2, -3, -4
 
 # enum sa_xfn (order matters: mirrors include/socceraction_amd.h)
@@ -237,6 +242,11 @@ _SIGNATURES = {
                                               ctypes.POINTER(SaBlock), _p, ctypes.c_int64,
                                               ctypes.POINTER(SaBlock), ctypes.POINTER(SaBlock),
                                               ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _p]),
+    'sa_group_sums': (ctypes.c_int, [_p, ctypes.POINTER(_p), ctypes.c_int32, ctypes.c_int32,
+                                     ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), _p,
+                                     _p, _p, _p]),
+    'sa_group_finalize': (ctypes.c_int, [_p, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.POINTER(ctypes.c_int32), _p, _p]),
     'sa_device_alloc': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
     'sa_device_free': (ctypes.c_int, [_p]),
     'sa_copy2d_async': (ctypes.c_int, [_p, ctypes.c_int64, _p, ctypes.c_int64, ctypes.c_int64,

@@ -997,6 +997,129 @@ def xt_rate(batch: ActionBatch, grid: torch.Tensor, L: int, W: int) -> Tuple[tor
     return out[:batch.n], err
 
 
+# ------------------------------------------------------------------------------- grouped sums
+GROUP_MAX_ROWS = 1 << 30  # fewer rows than this per table: the int64 limb sums cannot overflow
+
+
+@dataclass
+class GroupSums:
+    """Order-independent grouped sums (``sa_group_sums``): the fixed-point limb sums and row
+    counts of ``n_groups`` groups x ``n_cols`` value columns.  ``buf`` is ONE contiguous int64
+    allocation -- ``limbs`` [G, V, 3], ``count`` [G], the error word and a word the all-reduce
+    carries the row total in -- so ranks join their tables with one integer all-reduce
+    (``shard.allreduce_group_sums``) and batches accumulate into it call after call."""
+    n_groups: int
+    n_cols: int
+    scale_exp: Tuple[int, ...]   # per column: the contract is |v| < 2 ** scale_exp
+    buf: torch.Tensor            # int64 [G * V * 3 + G + 2]
+    rows: int = 0                # rows passed in so far (the capacity bound counts every row)
+
+    @property
+    def limbs(self) -> torch.Tensor:
+        G, V = self.n_groups, self.n_cols
+        return self.buf[:G * V * 3].view(G, V, 3)
+
+    @property
+    def count(self) -> torch.Tensor:
+        G, V = self.n_groups, self.n_cols
+        return self.buf[G * V * 3:G * V * 3 + G]
+
+    @property
+    def err(self) -> torch.Tensor:
+        """The ``SA_GROUP_ERR_*`` bits, int32 [1] (the low half of the buffer's error word)."""
+        return self.buf[-2:-1].view(torch.int32)[:1]
+
+    def zero_(self) -> 'GroupSums':
+        self.buf.zero_()
+        self.rows = 0
+        return self
+
+    def check_errors(self) -> None:
+        e = int(self.err.item())
+        if e & _native.SA_GROUP_ERR_KEY:
+            raise ValueError(f'group codes must be -1 (skip the row) or in [0, {self.n_groups})')
+        if e & _native.SA_GROUP_ERR_NONFINITE:
+            raise ValueError('grouped sums: a value is infinite')
+        if e & _native.SA_GROUP_ERR_RANGE:
+            raise ValueError(f'grouped sums: a value reaches 2 ** scale_exp (scale_exp = '
+                             f'{list(self.scale_exp)}): accumulate with a larger scale_exp')
+
+    def _exps(self):
+        return (ctypes.c_int32 * self.n_cols)(*self.scale_exp)
+
+    def finalize(self) -> torch.Tensor:
+        """The sums as f64 ``[V, G]``: every total rounded once to the nearest double."""
+        out = torch.empty((self.n_cols, self.n_groups), dtype=torch.float64, device=self.buf.device)
+        _native.check(_native.lib().sa_group_finalize(_ptr(self.limbs), self.n_groups, self.n_cols,
+                                                      self._exps(), _ptr(out), stream_handle()))
+        return out
+
+
+def group_sums_zero(n_groups: int, n_cols: int, scale_exp: Sequence[int], dev) -> GroupSums:
+    """An empty table."""
+    if not 1 <= n_cols <= _native.SA_GROUP_MAX_COLS:
+        raise ValueError(f'grouped sums take 1..{_native.SA_GROUP_MAX_COLS} value columns')
+    if n_groups < 1:
+        raise ValueError('n_groups must be at least 1')
+    exps = tuple(int(e) for e in scale_exp)
+    if len(exps) != n_cols or any(not -900 <= e <= 900 for e in exps):
+        raise ValueError('scale_exp: one exponent in [-900, 900] per column')
+    buf = torch.zeros(n_groups * n_cols * 3 + n_groups + 2, dtype=torch.int64, device=dev)
+    return GroupSums(int(n_groups), int(n_cols), exps, buf)
+
+
+def _auto_scale_exp(cols: Sequence[torch.Tensor]) -> Tuple[int, ...]:
+    """Per column, the exponent of the largest finite magnitude plus one: |v| < 2 ** E."""
+    big = torch.stack([torch.where(torch.isfinite(c), c.abs(), torch.zeros_like(c)).max().to(torch.float64)
+                       if c.numel() else torch.zeros((), dtype=torch.float64, device=c.device)
+                       for c in cols])
+    return tuple(min(900, max(-900, int(e))) for e in torch.frexp(big)[1].tolist())
+
+
+def group_sums(keys: torch.Tensor, cols, n_groups: int, scale_exp: Optional[Sequence[int]] = None,
+               acc: Optional[GroupSums] = None) -> GroupSums:
+    """Add the rows of ``cols`` (``V`` <= 8 device columns of ``n`` values, all float64 or all
+    float32; a sequence of 1-D tensors or one ``[V, n]`` tensor) to the sums of their groups.
+    ``keys``: int32 ``[n]`` group codes, -1 skips the row.  Returns a new :class:`GroupSums`, or
+    ``acc`` extended.  ``scale_exp=None`` takes ``acc``'s exponents, or for a new table the
+    exponent of each column's largest finite magnitude in this call plus one (one host sync); a
+    call whose values overflow ``acc``'s exponents raises ValueError."""
+    n = int(keys.numel())
+    cols = [c if c.is_contiguous() else c.contiguous() for c in cols]
+    V = len(cols)
+    if not 1 <= V <= _native.SA_GROUP_MAX_COLS:
+        raise ValueError(f'grouped sums take 1..{_native.SA_GROUP_MAX_COLS} value columns')
+    dt = cols[0].dtype
+    if dt not in (torch.float32, torch.float64) or any(c.dtype != dt for c in cols):
+        raise TypeError('value columns must all be float32 or all float64')
+    if keys.dtype != torch.int32 or keys.dim() != 1 or not keys.is_contiguous():
+        raise TypeError('keys must be a contiguous 1-D int32 tensor')
+    if any(c.dim() != 1 or c.numel() != n or c.device != keys.device for c in cols):
+        raise ValueError('every value column holds one value per key, on the keys\' device')
+    if scale_exp is None:
+        need = _auto_scale_exp(cols)
+        if acc is None:
+            scale_exp = need
+        elif any(a > b for a, b in zip(need, acc.scale_exp)):
+            raise ValueError(f'grouped sums: this call needs scale_exp {list(need)}, the table was '
+                             f'started with scale_exp {list(acc.scale_exp)}')
+    if acc is None:
+        acc = group_sums_zero(n_groups, V, scale_exp, keys.device)
+    elif acc.n_groups != n_groups or acc.n_cols != V or \
+            (scale_exp is not None and tuple(int(e) for e in scale_exp) != acc.scale_exp):
+        raise ValueError('acc was started for another n_groups, column count or scale_exp')
+    if acc.rows + n >= GROUP_MAX_ROWS:
+        raise ValueError(f'grouped sums: a table takes fewer than 2**30 rows ({acc.rows} + {n})')
+    if n == 0:
+        return acc
+    acc.rows += n
+    ptrs =(ctypes.c_void_p * V)(*[c.data_ptr() for c in cols])
+    _native.check(_native.lib().sa_group_sums(_ptr(keys), ptrs, V, int(dt == torch.float32), n,
+                                              acc.n_groups, acc._exps(), _ptr(acc.limbs),
+                                              _ptr(acc.count), _ptr(acc.err), stream_handle()))
+    return acc
+
+
 def goalscore_into(batch: ActionBatch, out: FeatureBlocks) -> None:
     """Launch only the goalscore scan into the plan's goalscore columns."""
     from ._native import XFN

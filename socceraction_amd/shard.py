@@ -87,6 +87,32 @@ def allreduce_xt_counts(acc, group=None) -> None:
     _all_reduce(acc.buf.view(torch.int32), group=group)
 
 
+def allreduce_group_sums(acc, group=None) -> None:
+    """Sum the grouped-sum tables of ``acc`` (``ops.GroupSums``) over the ranks of ``group`` in
+    place with ONE integer SUM all-reduce of its buffer: limb sums, row counts, the error word
+    and the row total.  Integer sums are exact and associative, so the joined table is the one
+    a single rank would have summed over all rows, bit for bit, for any rank count.  Every rank
+    must hold the same groups and ``scale_exp``.  The three error bits travel as 16-bit lanes
+    (up to 65535 ranks' flags add without touching each other) and come back as bits."""
+    import torch.distributed as dist
+    if dist.get_world_size(group) > 65535:
+        raise ValueError('the grouped-sum all-reduce sums one 16-bit lane per error flag: at most 65535 ranks')
+    tail = acc.buf[-2:]
+    e = tail[0].clone()
+    tail[0] = (e & 1) | ((e & 2) << 15) | ((e & 4) << 30)
+    tail[1] = acc.rows
+    _all_reduce(acc.buf, group=group)
+    s = tail[0].clone()
+    tail[0] = ((s & 0xFFFF) != 0).to(torch.int64) | (((s >> 16) & 0xFFFF) != 0).to(torch.int64) * 2 | \
+        (((s >> 32) & 0xFFFF) != 0).to(torch.int64) * 4
+    acc.rows = int(tail[1].item())
+    tail[1] = 0
+    from .ops import GROUP_MAX_ROWS
+    if acc.rows >= GROUP_MAX_ROWS:
+        raise ValueError(f'grouped sums: the ranks\' tables hold {acc.rows} rows together, a table '
+                         'takes fewer than 2**30')
+
+
 def _flag_count_range(acc, group) -> None:
     """The int32-word sum is exact while every summed count stays below 2**31: each rank's shot
     and move counts below 2**31 // world guarantee it (a transition count never exceeds its

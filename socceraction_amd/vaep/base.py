@@ -289,10 +289,10 @@ class VAEP:
         self._trees_cache = (key, res)
         return res
 
-    def _rate_device(self, ab: ActionBatch, trees) -> pd.DataFrame:
-        """features -> predict_proba -> formula without leaving HBM; only the three value
-        columns are copied back. The probability dtype is the learner's (float32 for
-        xgboost, float64 for scikit-learn), as in the reference's host path."""
+    def _values_device(self, ab: ActionBatch, trees):
+        """features -> predict_proba -> formula without leaving HBM: the ``[3, ld]`` device
+        tensor of offensive / defensive / vaep values. The probability dtype is the learner's
+        (float32 for xgboost, float64 for scikit-learn), as in the reference's host path."""
         import torch
         known, _ = self._split_xfns()
         # the learners read the bool features as bitmaps (64 instead of 515 B/action written);
@@ -321,7 +321,11 @@ class VAEP:
             pc = trees['concedes'].predict_blocks(fb)
         if ps.dtype != pc.dtype:  # pandas would upcast the mixed pair
             ps, pc = ps.to(torch.float64), pc.to(torch.float64)
-        v = ops.formula(ab, ps, pc).cpu().numpy()[:, :ab.n]
+        return ops.formula(ab, ps, pc)
+
+    def _rate_device(self, ab: ActionBatch, trees) -> pd.DataFrame:
+        """:meth:`_values_device`; only the three value columns are copied back."""
+        v = self._values_device(ab, trees).cpu().numpy()[:, :ab.n]
         return pd.DataFrame({'offensive_value': v[0], 'defensive_value': v[1],
                              'vaep_value': v[2]})
 
@@ -343,10 +347,10 @@ class VAEP:
         y_hat = self._estimate_probabilities(game_states)
         return self._vaep.value(actions, y_hat.scores, y_hat.concedes)
 
-    def rate_batch(self, games: pd.DataFrame, actions: pd.DataFrame,
-                   game_states: Optional[pd.DataFrame] = None) -> pd.DataFrame:
-        """VAEP values of many games (contiguous per game): one feature launch, one host
-        ``predict_proba`` per model, one formula launch with per-game segments."""
+    def _values_batch(self, games: pd.DataFrame, actions: pd.DataFrame,
+                      game_states: Optional[pd.DataFrame] = None):
+        """The ``[3, ld]`` device tensor of :meth:`rate_batch`'s values (offensive, defensive,
+        vaep), before its copy back."""
         if not self.__models:
             raise NotFittedError()
         if game_states is None:
@@ -355,19 +359,44 @@ class VAEP:
                 home_of = games.set_index('game_id')['home_team_id']
                 ab = ActionBatch.from_frame(actions, atomic=self._atomic, home_team_id=home_of,
                                             segments='game')
-                return self._rate_device(ab, trees)
+                return self._values_device(ab, trees)
             game_states = self.compute_features_batch(games, actions)
         y_hat = self._estimate_probabilities(game_states)
-        n = len(actions)
         ps = np.asarray(y_hat.scores.to_numpy())
         pc = np.asarray(y_hat.concedes.to_numpy())
         dt = np.float32 if (ps.dtype == np.float32 and pc.dtype == np.float32) else np.float64
         import torch
         ab = ActionBatch.from_frame(actions, atomic=self._atomic, segments='game')
-        out = ops.formula(ab, torch.from_numpy(np.ascontiguousarray(ps, dt)).to(ab.device),
-                          torch.from_numpy(np.ascontiguousarray(pc, dt)).to(ab.device))
-        v = out.cpu().numpy()[:, :n]
+        return ops.formula(ab, torch.from_numpy(np.ascontiguousarray(ps, dt)).to(ab.device),
+                           torch.from_numpy(np.ascontiguousarray(pc, dt)).to(ab.device))
+
+    def rate_batch(self, games: pd.DataFrame, actions: pd.DataFrame,
+                   game_states: Optional[pd.DataFrame] = None) -> pd.DataFrame:
+        """VAEP values of many games (contiguous per game): one feature launch, one host
+        ``predict_proba`` per model, one formula launch with per-game segments."""
+        v = self._values_batch(games, actions, game_states).cpu().numpy()[:, :len(actions)]
         return pd.DataFrame({'offensive_value': v[0], 'defensive_value': v[1], 'vaep_value': v[2]})
+
+    def rate_players(self, games: pd.DataFrame, actions: pd.DataFrame, by='player_id',
+                     groups=None) -> pd.DataFrame:
+        """The rating table of the reference's notebook 4: the values of :meth:`rate_batch`
+        summed per ``by`` (a column or a list of columns of ``actions``) with ``count``, as
+        ``ratings.group_sums(actions, self.rate_batch(games, actions), by, scale_exp=(2, 2, 2))``
+        but without the copy back of the values: they stay in HBM (device learners) or come
+        from the host ``predict_proba`` path, go through the order-independent grouped sums
+        (|value| <= 2, so the scale exponent is 2) and only the G-row table leaves the device."""
+        from .. import ratings
+        if not self.__models:
+            raise NotFittedError()
+        n = len(actions)
+        codes, keys = ratings.factorize(actions, by, groups)
+        names = ['offensive_value', 'defensive_value', 'vaep_value']
+        if len(keys) == 0 or n == 0:  # nothing to rate: the empty table
+            return ratings.group_sums(actions, {c: np.zeros(n) for c in names}, by, groups)
+        v = self._values_batch(games, actions)
+        acc = ratings.sum_device(codes, [v[i, :n] for i in range(3)], len(keys),
+                                 scale_exp=(2, 2, 2), dev=v.device)
+        return ratings.table(acc, keys, names)
 
     def score(self, X: pd.DataFrame, y: pd.DataFrame) -> Dict[str, Dict[str, float]]:
         """Brier score and AUROC per label (reference vaep/base.py:335-366)."""

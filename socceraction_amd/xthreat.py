@@ -345,13 +345,9 @@ class ExpectedThreat:
         self._grid_cache = (key, res)
         return res
 
-    def rate(self, actions: pd.DataFrame, use_interpolation: bool = False) -> np.ndarray:
-        """xT value of every successful move, NaN elsewhere (reference xthreat.py:408-465)."""
-        if not np.any(self.xT):
-            raise NotFittedError()
+    def _rate_device(self, actions: pd.DataFrame, use_interpolation: bool) -> torch.Tensor:
+        """The f64 ``[n]`` device tensor :meth:`rate` copies back (``actions`` not empty)."""
         g = self._grid(use_interpolation)
-        if len(actions) == 0:
-            return np.empty(0)
         ab = ActionBatch.from_frame(actions)
         if use_interpolation:
             xT, L, W, axes = g
@@ -360,7 +356,33 @@ class ExpectedThreat:
             out, err = ops.xt_rate(ab, *g)
         if int(err.item()):
             raise ValueError('Cannot convert non-finite values (NA or inf) to integer')
-        return out.cpu().numpy()
+        return out
+
+    def rate(self, actions: pd.DataFrame, use_interpolation: bool = False) -> np.ndarray:
+        """xT value of every successful move, NaN elsewhere (reference xthreat.py:408-465)."""
+        if not np.any(self.xT):
+            raise NotFittedError()
+        self._grid(use_interpolation)
+        if len(actions) == 0:
+            return np.empty(0)
+        return self._rate_device(actions, use_interpolation).cpu().numpy()
+
+    def rate_players(self, actions: pd.DataFrame, by='player_id', use_interpolation: bool = False,
+                     groups=None) -> pd.DataFrame:
+        """The xT rating table: :meth:`rate`'s values summed per ``by`` with ``count``, as
+        ``ratings.group_sums(actions, pd.Series(self.rate(actions), name='xT_value'), by,
+        scale_exp=(1,))`` but summed on the device before the copy back (order-independent
+        grouped sums, scale exponent 1 since an xT difference lies inside (-1, 1)).  The NaN of
+        actions that are not successful moves is skipped; ``count`` is every row of the group."""
+        from . import ratings
+        if not np.any(self.xT):
+            raise NotFittedError()
+        codes, keys = ratings.factorize(actions, by, groups)
+        if len(actions) == 0 or len(keys) == 0:  # nothing to rate: the empty table
+            return ratings.group_sums(actions, {'xT_value': np.zeros(len(actions))}, by, groups)
+        out = self._rate_device(actions, use_interpolation)
+        acc = ratings.sum_device(codes, [out], len(keys), scale_exp=(1,), dev=out.device)
+        return ratings.table(acc, keys, ['xT_value'])
 
     def save_model(self, filepath: str, overwrite: bool = True) -> None:
         """Save the xT surface as JSON (reference xthreat.py:467-504)."""
