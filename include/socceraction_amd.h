@@ -733,6 +733,52 @@ int sa_group_sums(const int32_t* key, const void* const* cols, int32_t n_cols, i
 int sa_group_finalize(const int64_t* limbs, int32_t n_groups, int32_t n_cols,
                       const int32_t* scale_exp, double* out, void* stream);
 
+/* ---- binary classification scores ---------------------------------------------- */
+/* Brier score, log loss and exact AUROC of one label column y [n] uint8 (0 / 1) against one
+ * probability column p [n] (f32 != 0: float, else double), as the last cell of the reference's
+ * public-notebooks/3-estimate-scoring-and-conceding-probabilities.ipynb and VAEP.score compute
+ * them with scikit-learn.  Each result is a function of the multiset of (y, p) rows: the same bit
+ * for bit from run to run and for any row order or batch split.  n < 2^30.  Columns whose
+ * pointers are 4-byte (y) and 16-byte (p) aligned are read with one 4-byte and 16-byte loads per
+ * four rows; rows >= n are never read.
+ * sa_metric_sums ADDS the rows of one batch to caller-zeroed outputs: count[0] rows, count[1]
+ * rows with y = 1; limbs[0][0..2] the sa_fixed.h limb sums of the Brier terms (p - y)^2 at scale
+ * exponent SA_METRIC_BRIER_EXP, limbs[1][0..2] those of the log-loss terms -log(q) at
+ * SA_METRIC_LOGLOSS_EXP, both terms computed in f64; q is the probability of the true class as
+ * sklearn.metrics.log_loss forms it: the complement 1 - p in p's type, both clipped to
+ * [eps, 1 - eps] of that type.  err: one uint32 of SA_METRIC_ERR_* bits (OR-ed in): p is NaN
+ * (NAN), p outside [0, 1] or infinite (RANGE), y neither 0 nor 1 (LABEL); a row that sets a bit
+ * adds nothing, its count included.  Each thread sums in int64, the workgroup reduces, and one set
+ * of 64-bit integer atomics per workgroup reaches the outputs; a workgroup takes
+ * SA_METRIC_CHUNK_ROWS contiguous rows per loop step.
+ * sa_metric_finalize (host pointers, no device work): out[0] = Brier score, out[1] = log loss,
+ * each sa_fx_finalize(limb sums) / count[0].
+ * AUROC = U2 / (2 * n_pos * n_neg) with the integer U2 = sum over (positive, negative) pairs of
+ * 2 if p_pos > p_neg, 1 if equal, else 0 (below 2^63).  Rows are compared by the order key of
+ * p: its bit pattern with -0.0 mapped to +0.0 (uint32 for f32, uint64 for f64; monotonic, p >= 0).
+ * sa_auc_keys writes the keys of the rows with y == minority to keys [capacity], in unspecified
+ * order, from *cursor (caller-zeroed, advanced by the number of such rows; keys past capacity are
+ * dropped).  The caller sorts them ascending (the top bit is clear: a signed sort will do).
+ * sa_auc_count looks every row with y == 1 - minority up in sorted_keys [m] and ADDS to *u2
+ * (caller-zeroed) 2 * (m - upper) + (upper - lower) when minority = 1, 2 * lower +
+ * (upper - lower) when minority = 0, lower / upper = the number of keys below / not above the
+ * row's.  An evenly spaced sample of at most SA_AUC_LDS_SAMPLE keys decides the top levels of the
+ * search in LDS, global memory the rest; any m in [1, n]. */
+#define SA_METRIC_BRIER_EXP 1
+#define SA_METRIC_LOGLOSS_EXP 6
+#define SA_METRIC_CHUNK_ROWS 4096
+#define SA_METRIC_ERR_NAN 1
+#define SA_METRIC_ERR_RANGE 2
+#define SA_METRIC_ERR_LABEL 4
+#define SA_AUC_LDS_SAMPLE 1024
+int sa_metric_sums(const uint8_t* y, const void* p, int32_t f32, int64_t n, int64_t* count,
+                   int64_t* limbs, uint32_t* err, void* stream);
+int sa_metric_finalize(const int64_t* count, const int64_t* limbs, double* out);
+int sa_auc_keys(const uint8_t* y, const void* p, int32_t f32, int64_t n, int32_t minority,
+                void* keys, int64_t capacity, uint64_t* cursor, void* stream);
+int sa_auc_count(const uint8_t* y, const void* p, int32_t f32, int64_t n, const void* sorted_keys,
+                 int64_t m, int32_t minority, uint64_t* u2, void* stream);
+
 /* ---- runtime ------------------------------------------------------------------ */
 int sa_abi_version(void);
 const char* sa_last_error(void);

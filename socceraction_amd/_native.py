@@ -36,6 +36,10 @@ SA_GROUP_LDS_SLOTS = 256  # slots of the grouped sums' LDS table
 SA_GROUP_CHUNK_ROWS = 8192
 SA_GROUP_HASH_MUL = 2654435761
 SA_GROUP_ERR_KEY, SA_GROUP_ERR_NONFINITE, SA_GROUP_ERR_RANGE = 1, 2, 4
+SA_METRIC_BRIER_EXP, SA_METRIC_LOGLOSS_EXP = 1, 6  # scale exponents of the score terms
+SA_METRIC_CHUNK_ROWS = 4096
+SA_METRIC_ERR_NAN, SA_METRIC_ERR_RANGE, SA_METRIC_ERR_LABEL = 1, 2, 4
+SA_AUC_LDS_SAMPLE = 1024  # sorted minority keys sa_auc_count keeps in LDS
 SA_OK, SA_EINVAL, SA_EHIP, SA_EDATA, SA_ENOMEM = 0, -1, -2, -3, -4
 
 # enum sa_xfn (order matters: mirrors include/socceraction_amd.h)
@@ -247,6 +251,13 @@ _SIGNATURES = {
                                      _p, _p, _p]),
     'sa_group_finalize': (ctypes.c_int, [_p, ctypes.c_int32, ctypes.c_int32,
                                          ctypes.POINTER(ctypes.c_int32), _p, _p]),
+    'sa_metric_sums': (ctypes.c_int, [_p, _p, ctypes.c_int32, ctypes.c_int64, _p, _p, _p, _p]),
+    'sa_metric_finalize': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                          ctypes.POINTER(ctypes.c_double)]),
+    'sa_auc_keys': (ctypes.c_int, [_p, _p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, _p,
+                                   ctypes.c_int64, _p, _p]),
+    'sa_auc_count': (ctypes.c_int, [_p, _p, ctypes.c_int32, ctypes.c_int64, _p, ctypes.c_int64,
+                                    ctypes.c_int32, _p, _p]),
     'sa_device_alloc': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
     'sa_device_free': (ctypes.c_int, [_p]),
     'sa_copy2d_async': (ctypes.c_int, [_p, ctypes.c_int64, _p, ctypes.c_int64, ctypes.c_int64,

@@ -1120,6 +1120,147 @@ def group_sums(keys: torch.Tensor, cols, n_groups: int, scale_exp: Optional[Sequ
     return acc
 
 
+# ------------------------------------------------------------------------------- binary scores
+def fixed_sum_value(l0: int, l1: int, l2: int, scale_exp: int) -> float:
+    """``sa_fx_finalize`` in Python integers: the limb sums' total times 2^(scale_exp - 95),
+    rounded once to the nearest double (int / int division rounds half to even)."""
+    return (int(l0) + (int(l1) << 32) + (int(l2) << 64)) / (1 << (95 - scale_exp))
+
+
+def scores_from_sums(n: int, n_pos: int, brier_limbs, log_loss_limbs, u2: Optional[int]) -> dict:
+    """The score dict of :meth:`BinaryMetrics.finalize` from the integer sums (host, float64):
+    means of the fixed-point totals, ``auroc = U2 / (2 n_pos n_neg)`` as one correctly rounded
+    quotient of integers (None when ``u2`` is None or one class is absent), and the scores of
+    the constant prediction ``n_pos / n``."""
+    import math
+    n, n_pos = int(n), int(n_pos)
+    if n < 1:
+        raise ValueError('binary scores need at least one row')
+    n_neg = n - n_pos
+    base = n_pos / n
+    eps = float(np.finfo(np.float64).eps)
+    q1 = min(max(base, eps), 1 - eps)
+    q0 = min(max(1.0 - base, eps), 1 - eps)
+    return {
+        'brier': fixed_sum_value(*brier_limbs, _native.SA_METRIC_BRIER_EXP) / n,
+        'log_loss': fixed_sum_value(*log_loss_limbs, _native.SA_METRIC_LOGLOSS_EXP) / n,
+        'auroc': int(u2) / (2 * n_pos * n_neg) if u2 is not None and n_pos and n_neg else None,
+        'brier_baseline': (n_pos * (1.0 - base) ** 2 + n_neg * base ** 2) / n,
+        'log_loss_baseline': -(n_pos * math.log(q1) + n_neg * math.log(q0)) / n,
+        'n': n, 'n_pos': n_pos}
+
+
+@dataclass
+class BinaryMetrics:
+    """The integer sums of the binary scores (``sa_metric_sums`` / ``sa_auc_count``) in ONE
+    contiguous int64 device buffer: ``count`` [2] (rows, positives), ``limbs`` [2, 3] (Brier
+    and log-loss terms), the error word and ``u2``.  :meth:`add` takes further batches for the
+    sums; the AUROC needs every row at once and belongs to the call that created the object."""
+    buf: torch.Tensor            # int64 [10]
+    rows: int = 0                # rows passed in so far
+    auc_rows: int = -1           # rows u2 was counted over (-1: not counted)
+
+    @property
+    def count(self) -> torch.Tensor:
+        return self.buf[0:2]
+
+    @property
+    def limbs(self) -> torch.Tensor:
+        return self.buf[2:8].view(2, 3)
+
+    @property
+    def err(self) -> torch.Tensor:
+        """The ``SA_METRIC_ERR_*`` bits, int32 [1] (the low half of the buffer's error word)."""
+        return self.buf[8:9].view(torch.int32)[:1]
+
+    @property
+    def u2(self) -> torch.Tensor:
+        return self.buf[9:10]
+
+    def add(self, y: torch.Tensor, p: torch.Tensor) -> 'BinaryMetrics':
+        """Add one batch (``y`` uint8 / bool labels, ``p`` float32 / float64 probabilities, 1-D
+        device tensors of one length) to the counts and the Brier / log-loss sums."""
+        y, p = _metric_columns(y, p)
+        n = int(y.numel())
+        if y.device != self.buf.device:
+            raise ValueError('the batch must live on the accumulator\'s device')
+        if self.rows + n >= GROUP_MAX_ROWS:
+            raise ValueError(f'binary scores take fewer than 2**30 rows ({self.rows} + {n})')
+        if n == 0:
+            return self
+        self.rows += n
+        _native.check(_native.lib().sa_metric_sums(_ptr(y), _ptr(p), int(p.dtype == torch.float32), n,
+                                                   _ptr(self.count), _ptr(self.limbs), _ptr(self.err),
+                                                   stream_handle()))
+        return self
+
+    @staticmethod
+    def raise_errors(err: int) -> None:
+        """scikit-learn's exceptions for the ``SA_METRIC_ERR_*`` bits."""
+        if err & _native.SA_METRIC_ERR_NAN:
+            raise ValueError('Input contains NaN.')
+        if err & _native.SA_METRIC_ERR_RANGE:
+            raise ValueError('probabilities must lie in [0, 1]')
+        if err & _native.SA_METRIC_ERR_LABEL:
+            raise ValueError('labels must be 0 or 1')
+
+    def finalize(self) -> dict:
+        """One copy back of the ten words, then :func:`scores_from_sums`; ValueError for a row
+        that was NaN, outside [0, 1] or labelled other than 0 / 1.  ``auroc`` is None unless
+        ``u2`` covers every row added and both classes are present."""
+        h = self.buf.cpu().tolist()
+        self.raise_errors(h[8] & 0xFFFFFFFF)
+        return scores_from_sums(h[0], h[1], h[2:5], h[5:8], h[9] if self.auc_rows == self.rows else None)
+
+
+def _metric_columns(y: torch.Tensor, p: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    if y.dtype == torch.bool:
+        y = y.view(torch.uint8)
+    if y.dtype != torch.uint8:
+        raise TypeError('labels must be uint8 or bool')
+    if p.dtype not in (torch.float32, torch.float64):
+        raise TypeError('probabilities must be float32 or float64')
+    if y.dim() != 1 or p.dim() != 1 or y.numel() != p.numel() or y.device != p.device:
+        raise ValueError('one label per probability, both 1-D and on one device')
+    return y.contiguous(), p.contiguous()
+
+
+def binary_metrics(y: torch.Tensor, p: torch.Tensor, acc: Optional[BinaryMetrics] = None) -> BinaryMetrics:
+    """Order-independent Brier / log-loss sums and the exact AUROC count of the label column
+    ``y`` (uint8 or bool) against the probability column ``p`` (float32 or float64), both 1-D
+    device tensors.  With ``acc``, the batch is added to its sums (:meth:`BinaryMetrics.add`)
+    and no AUROC is counted.  Without, a new accumulator: the sums, ONE host read of the counts
+    (which class is the minority, and the error bits: ValueError as in ``finalize``), the
+    minority class's order keys compacted and sorted, and every majority row looked up in them
+    (``sa_auc_keys``, ``torch.sort``, ``sa_auc_count``).  With a single class present the AUROC
+    is left uncounted."""
+    if acc is not None:
+        return acc.add(y, p)
+    y, p = _metric_columns(y, p)
+    acc = BinaryMetrics(torch.zeros(10, dtype=torch.int64, device=y.device)).add(y, p)
+    n = acc.rows
+    if n == 0:
+        return acc
+    h = acc.buf.cpu().tolist()
+    acc.raise_errors(h[8] & 0xFFFFFFFF)
+    n_pos = h[1]
+    minority = int(n_pos <= n - n_pos)
+    m = n_pos if minority else n - n_pos
+    if m == 0:
+        return acc
+    f32 = int(p.dtype == torch.float32)
+    keys = torch.empty(m, dtype=torch.int32 if f32 else torch.int64, device=y.device)
+    cursor = torch.zeros(1, dtype=torch.int64, device=y.device)
+    lib = _native.lib()
+    _native.check(lib.sa_auc_keys(_ptr(y), _ptr(p), f32, n, minority, _ptr(keys), m, _ptr(cursor),
+                                  stream_handle()))
+    keys = torch.sort(keys).values  # the top bit is clear: the signed order is the keys' order
+    _native.check(lib.sa_auc_count(_ptr(y), _ptr(p), f32, n, _ptr(keys), m, minority, _ptr(acc.u2),
+                                   stream_handle()))
+    acc.auc_rows = n
+    return acc
+
+
 def goalscore_into(batch: ActionBatch, out: FeatureBlocks) -> None:
     """Launch only the goalscore scan into the plan's goalscore columns."""
     from ._native import XFN

@@ -289,9 +289,9 @@ class VAEP:
         self._trees_cache = (key, res)
         return res
 
-    def _values_device(self, ab: ActionBatch, trees):
-        """features -> predict_proba -> formula without leaving HBM: the ``[3, ld]`` device
-        tensor of offensive / defensive / vaep values. The probability dtype is the learner's
+    def _proba_device(self, ab: ActionBatch, trees):
+        """features -> predict_proba without leaving HBM: the device probability columns
+        ``(p_scores, p_concedes)`` (at least ``ab.n`` rows each). The dtype is the learner's
         (float32 for xgboost, float64 for scikit-learn), as in the reference's host path."""
         import torch
         known, _ = self._split_xfns()
@@ -321,6 +321,12 @@ class VAEP:
             pc = trees['concedes'].predict_blocks(fb)
         if ps.dtype != pc.dtype:  # pandas would upcast the mixed pair
             ps, pc = ps.to(torch.float64), pc.to(torch.float64)
+        return ps, pc
+
+    def _values_device(self, ab: ActionBatch, trees):
+        """:meth:`_proba_device` -> formula: the ``[3, ld]`` device tensor of offensive /
+        defensive / vaep values, of the probabilities' dtype."""
+        ps, pc = self._proba_device(ab, trees)
         return ops.formula(ab, ps, pc)
 
     def _rate_device(self, ab: ActionBatch, trees) -> pd.DataFrame:
@@ -347,10 +353,12 @@ class VAEP:
         y_hat = self._estimate_probabilities(game_states)
         return self._vaep.value(actions, y_hat.scores, y_hat.concedes)
 
-    def _values_batch(self, games: pd.DataFrame, actions: pd.DataFrame,
-                      game_states: Optional[pd.DataFrame] = None):
-        """The ``[3, ld]`` device tensor of :meth:`rate_batch`'s values (offensive, defensive,
-        vaep), before its copy back."""
+    def _probabilities_batch(self, games: pd.DataFrame, actions: pd.DataFrame,
+                             game_states: Optional[pd.DataFrame] = None):
+        """``(ActionBatch, {label column: device probability column})`` of many games, as
+        :meth:`rate_batch` estimates them: supported tree learners on the device feature blocks
+        (nothing leaves HBM), any other learner through the feature frame and the host
+        ``predict_proba``, its columns uploaded (float32 when the scores / concedes pair is, else float64)."""
         if not self.__models:
             raise NotFittedError()
         if game_states is None:
@@ -359,16 +367,24 @@ class VAEP:
                 home_of = games.set_index('game_id')['home_team_id']
                 ab = ActionBatch.from_frame(actions, atomic=self._atomic, home_team_id=home_of,
                                             segments='game')
-                return self._values_device(ab, trees)
+                ps, pc = self._proba_device(ab, trees)
+                return ab, {'scores': ps, 'concedes': pc}
             game_states = self.compute_features_batch(games, actions)
         y_hat = self._estimate_probabilities(game_states)
-        ps = np.asarray(y_hat.scores.to_numpy())
-        pc = np.asarray(y_hat.concedes.to_numpy())
-        dt = np.float32 if (ps.dtype == np.float32 and pc.dtype == np.float32) else np.float64
+        cols = {c: np.asarray(y_hat[c].to_numpy()) for c in y_hat.columns}
+        pair = [cols[c] for c in ('scores', 'concedes') if c in cols] or list(cols.values())
+        dt = np.float32 if all(v.dtype == np.float32 for v in pair) else np.float64
         import torch
         ab = ActionBatch.from_frame(actions, atomic=self._atomic, segments='game')
-        return ops.formula(ab, torch.from_numpy(np.ascontiguousarray(ps, dt)).to(ab.device),
-                           torch.from_numpy(np.ascontiguousarray(pc, dt)).to(ab.device))
+        return ab, {c: torch.from_numpy(np.ascontiguousarray(v, dt)).to(ab.device)
+                    for c, v in cols.items()}
+
+    def _values_batch(self, games: pd.DataFrame, actions: pd.DataFrame,
+                      game_states: Optional[pd.DataFrame] = None):
+        """The ``[3, ld]`` device tensor of :meth:`rate_batch`'s values (offensive, defensive,
+        vaep), before its copy back."""
+        ab, proba = self._probabilities_batch(games, actions, game_states)
+        return ops.formula(ab, proba['scores'], proba['concedes'])
 
     def rate_batch(self, games: pd.DataFrame, actions: pd.DataFrame,
                    game_states: Optional[pd.DataFrame] = None) -> pd.DataFrame:
@@ -408,4 +424,27 @@ class VAEP:
             scores[col] = {}
             scores[col]['brier'] = brier_score_loss(y[col], y_hat[col])
             scores[col]['auroc'] = roc_auc_score(y[col], y_hat[col])
+        return scores
+
+    def score_batch(self, games: pd.DataFrame, actions: pd.DataFrame,
+                    nr_actions: Optional[int] = None) -> Dict[str, Dict[str, float]]:
+        """Brier score, AUROC and log loss per label of the fitted models on many games
+        (contiguous per game), with the Brier score and log loss of the base-rate prediction
+        (``*_baseline``; the last cell of the reference's notebook 3), without building the
+        feature frame: the probabilities of :meth:`rate_batch`'s path and the labels of the same
+        encoded batch stay in HBM and go through the order-independent score kernels
+        (:func:`socceraction_amd.metrics.binary_scores`); learners the device does not evaluate
+        take the feature frame and the host ``predict_proba``, and their probabilities are
+        uploaded to the same kernels.  ``nr_actions``: the labels' look-ahead (default 10)."""
+        from .. import metrics
+        ab, proba = self._probabilities_batch(games, actions)
+        lb = ops.labels(ab, 10 if nr_actions is None else int(nr_actions))
+        scores: Dict[str, Dict[str, float]] = {}
+        for col, p in proba.items():
+            name = 'goal_from_shot' if (self._atomic and col == 'goal') else col
+            if name not in ('scores', 'concedes', 'goal_from_shot'):
+                raise ValueError(f'score_batch knows the labels scores, concedes and goal_from_shot, not {col!r}')
+            res = metrics.binary_scores(getattr(lb, name)[:ab.n], p[:ab.n])
+            scores[col] = {k: res[k] for k in ('brier', 'auroc', 'log_loss', 'brier_baseline',
+                                               'log_loss_baseline')}
         return scores
