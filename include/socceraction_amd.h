@@ -649,7 +649,8 @@ int sa_pack_bits(const sa_block* bool_blk, int64_t n, uint8_t* bits, int64_t col
  * of a binary gradient-boosted tree ensemble for every row of the feature blocks.
  * nodes: n_nodes records of 24 bytes { double threshold_or_leaf_value; int32 feature (-1 =
  * leaf); int32 left; int32 right | (default_left << 31); int32 pad } with absolute child
- * indices; roots[n_trees] the root node of each tree, summed in that order onto base_margin.
+ * indices; roots[n_trees] the root node of each tree, summed in that order onto base_margin
+ * (n_trees = 0: roots may be NULL, every p_out is the link of base_margin).
  * feature_slots[f] = (kind << 24) | column locates model feature f in the blocks (kind 0 =
  * bool block, 1 = f64, 2 = i64).  le = 1: `x <= threshold` goes left (scikit-learn), 0:
  * `x < threshold` (xgboost); NaN follows default_left.  f32 = 1: xgboost float32 arithmetic

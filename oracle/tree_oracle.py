@@ -47,6 +47,33 @@ def predict_xgboost_json(model: dict, X: np.ndarray) -> np.ndarray:
     return (np.float32(1.0) / (np.float32(1.0) + np.exp(-margin))).astype(np.float32)
 
 
+def predict_flat(trees, base_margin, X: np.ndarray, lt: bool, dtype) -> np.ndarray:
+    """P(class 1) of a model given as explicit per-tree arrays -- dicts of ``left``, ``right``
+    (-1 = leaf), ``feature``, ``cond`` (threshold, or the leaf value) and ``default_left`` --
+    under either learner's rule: ``lt=True, dtype=float32`` is xgboost's (``float32(x) < thr``
+    goes left, float32 sums and link), ``lt=False, dtype=float64`` scikit-learn's (``x <= thr``,
+    float64).  NaN follows ``default_left``; leaves are added in tree order onto ``base_margin``."""
+    dtype = np.dtype(dtype).type
+    margin = np.full(X.shape[0], dtype(base_margin), dtype)
+    for t in trees:
+        leaf = _walk(X, np.asarray(t['left'], np.int64), np.asarray(t['right'], np.int64),
+                     np.asarray(t['feature'], np.int64), np.asarray(t['cond'], dtype),
+                     np.asarray(t['default_left']).astype(bool), lt, dtype)
+        margin = (margin + leaf).astype(dtype)
+    return (dtype(1.0) / (dtype(1.0) + np.exp(-margin))).astype(dtype)
+
+
+def condition_bits(X: np.ndarray, feature: int, thr, default_left: bool, lt: bool, dtype) -> np.ndarray:
+    """The bool vector "goes right" of one split condition over the rows of X:
+    ``~(dtype(x) < dtype(thr))`` (``<=`` when not ``lt``), NaN -> ``not default_left``."""
+    dtype = np.dtype(dtype).type
+    v = X[:, feature].astype(dtype)
+    t = dtype(thr)
+    with np.errstate(invalid='ignore'):
+        left = (v < t) if lt else (v <= t)
+    return np.where(np.isnan(v), not default_left, ~left)
+
+
 def predict_sklearn_nodes(clf, X: np.ndarray) -> np.ndarray:
     """The same walk over a HistGradientBoostingClassifier's nodes (x <= threshold, float64,
     expit) -- checked against the estimator's own predict_proba."""

@@ -511,7 +511,8 @@ extern "C" int sa_tree_predict(const void* nodes, int32_t n_nodes, const int32_t
                                const sa_block* bool_blk, const sa_block* f64_blk, const sa_block* i64_blk,
                                int64_t n, double base_margin, int32_t le, int32_t f32, void* p_out,
                                void* stream) {
-  if (n < 0 || n_nodes < 1 || n_trees < 0 || n_features < 0 || !nodes || !roots || !p_out ||
+  // (a model without trees has no roots to point at: every row gets the link of the base margin)
+  if (n < 0 || n_nodes < 1 || n_trees < 0 || n_features < 0 || !nodes || (n_trees > 0 && !roots) || !p_out ||
       (n_features > 0 && !feature_slots))
     return fail(SA_EINVAL, "bad tree model arguments");
   sa_block z{nullptr, 0, 0, 16};  // absent block: never read (no slot refers to it)

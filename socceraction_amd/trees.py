@@ -403,6 +403,11 @@ def condition_bitmaps(batch, plan, models: Sequence[TreeEnsemble], flip: bool = 
     words = max(2, -(-n // 128) * 2)  # int64 words per row: a whole number of 16-B runs
     if bits is None:
         bits = torch.empty((max(nb + n_num, 1), words), dtype=torch.int64, device=dev)
+    if nb and n % 128 and -(-n // 16) * 16 < words * 64:
+        # the bool pass writes the 16-row groups up to the one holding row n - 1 (rows >= n of
+        # that group clear); the later groups of the last 128-row run are cleared here, so that
+        # every bit at a row >= n is clear in the bool rows as it is in the condition rows
+        bits[:nb, words - 2:words].zero_()
     s = batch.struct(flip=flip)
     _native.check(_native.lib().sa_vaep_features_conditions(
         ctypes.byref(s), ctypes.byref(plan.struct), bits.data_ptr(), words * 8, nb, plan.n_f64,

@@ -281,9 +281,11 @@ def test_condition_bitmaps_match_staged_walk(sa, case):
     """sa_vaep_features_conditions + the staged walk over bitmaps only (trees.predict_pair_conditions:
     the learners' numeric split conditions evaluated inside the numeric feature pass) == each
     learner's staged walk over the feature blocks, bit for bit: two xgboost-shaped learners over
-    bool and numeric (f64 and i64) features with NaN-free and NaN-routed splits, several tiles and
-    a batch whose length is not a multiple of 128; and a plan with no bool column at all
-    (numeric-only xfns: the condition rows start at bitmap row 0)."""
+    bool and numeric (f64 and i64) features with default_left set both ways, several tiles and a
+    batch whose length is not a multiple of 128; and a plan with no bool column at all
+    (numeric-only xfns: the condition rows start at bitmap row 0).  The synthetic batch holds no
+    NaN, so no row takes a default direction here: NaN coordinates reaching the condition pass, and
+    both paths against the oracle, are in tests/test_gpu_tree_boundaries.py."""
     from socceraction_amd import synthetic, catalog
     from oracle import vaep_oracle as vo
     B, ops, trees = sa['batch'], sa['ops'], sa['trees']

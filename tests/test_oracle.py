@@ -169,3 +169,104 @@ def test_tree_oracle_xgboost_rules():
     p = to.predict_xgboost_json(model, X)
     m = np.array([-1.0, 0.5, 0.5, -1.0], np.float32)
     np.testing.assert_array_equal(p, (1 / (1 + np.exp(-m))).astype(np.float32))
+
+
+def _flat_of_xgboost_json(model):
+    return [{'left': t['left_children'], 'right': t['right_children'], 'feature': t['split_indices'],
+             'cond': t['split_conditions'], 'default_left': t['default_left']}
+            for t in model['learner']['gradient_booster']['model']['trees']]
+
+
+def test_predict_flat_equals_predict_xgboost_json():
+    """predict_flat under xgboost's rule (`<`, float32) == predict_xgboost_json on a synthetic
+    JSON model, bit for bit, with NaN, thresholds hit exactly and a non-default base score."""
+    from oracle import tree_oracle as to
+    from socceraction_amd.trees import synthetic_xgboost_json
+    model = synthetic_xgboost_json(12, n_trees=30, depth=4, seed=9, base_score=0.3)
+    rng = np.random.default_rng(0)
+    X = rng.normal(0.0, 30.0, (500, 12))
+    X[::11, 3] = np.nan
+    t0 = model['learner']['gradient_booster']['model']['trees'][0]
+    X[::5, t0['split_indices'][0]] = t0['split_conditions'][0]  # equality at a root
+    p = np.float32(0.3)
+    base = np.float32(-np.log(np.float32(1.0) / p - np.float32(1.0)))
+    got = to.predict_flat(_flat_of_xgboost_json(model), base, X, True, np.float32)
+    assert got.dtype == np.float32
+    np.testing.assert_array_equal(got, to.predict_xgboost_json(model, X))
+
+
+def test_predict_flat_equals_sklearn_predict_proba():
+    """predict_flat under scikit-learn's rule (`<=`, float64) == predict_proba of a fitted
+    HistGradientBoostingClassifier (rtol 1e-12), incl. missing values."""
+    from sklearn.ensemble import HistGradientBoostingClassifier
+
+    from oracle import tree_oracle as to
+    g = load('spadl', 'full0')
+    X = np.concatenate([g['k3_feat_b'].astype(np.float64), g['k3_feat_f'],
+                        g['k3_feat_i'].astype(np.float64)], axis=1).copy()
+    y = g['scores'].astype(int)
+    y[::7] = 1
+    X[::13, 520] = np.nan
+    clf = HistGradientBoostingClassifier(max_iter=30, max_leaf_nodes=9, random_state=0).fit(X, y)
+    flat = []
+    for it in clf._predictors:
+        nd = it[0].nodes
+        leaf = nd['is_leaf'].astype(bool)
+        flat.append({'left': np.where(leaf, -1, nd['left'].astype(np.int64)),
+                     'right': np.where(leaf, -1, nd['right'].astype(np.int64)),
+                     'feature': nd['feature_idx'], 'cond': np.where(leaf, nd['value'], nd['num_threshold']),
+                     'default_left': nd['missing_go_to_left']})
+    base = float(np.asarray(clf._baseline_prediction).reshape(-1)[0])
+    got = to.predict_flat(flat, base, X, False, np.float64)
+    assert got.dtype == np.float64
+    np.testing.assert_allclose(got, clf.predict_proba(X)[:, 1], rtol=1e-12, atol=0)
+
+
+def test_condition_bits_rules():
+    """condition_bits: equality goes right under `<` and left under `<=`; the compare is made in
+    the given dtype (a float64 value above its float32 rounding); -0.0 == 0.0; NaN follows the
+    default direction."""
+    from oracle import tree_oracle as to
+    x = 0.1  # float32(0.1) > 0.1
+    t = float(np.float32(x))
+    X = np.array([[x], [t], [np.nextafter(np.float32(t), np.float32(np.inf))], [-0.0], [np.nan]])
+    np.testing.assert_array_equal(to.condition_bits(X, 0, t, True, True, np.float32),
+                                  [True, True, True, False, False])
+    np.testing.assert_array_equal(to.condition_bits(X, 0, t, False, True, np.float64),
+                                  [False, True, True, False, True])
+    np.testing.assert_array_equal(to.condition_bits(X, 0, t, False, False, np.float64),
+                                  [False, False, True, False, True])
+    np.testing.assert_array_equal(to.condition_bits(X, 0, 0.0, True, True, np.float32),
+                                  [True, True, True, True, False])
+
+
+def test_boundary_models_meet_the_coverage_floor():
+    """tests/tree_boundary_models.py on the oracle's own features of a synthetic batch with NaN
+    coordinates (no device): margins stay within +-4 in units of 2^-6 (asserted by the builder),
+    and from 7 trees on the batch visits numeric ties on >= 1 % of its rows, a
+    split where the float64 and the float32 compare disagree, NaN defaults in both directions and
+    constant bool splits in both directions -- under the float32 `<` and the float64 `<=` rule."""
+    import tree_boundary_models as bm
+    from oracle import tree_oracle as to
+    from socceraction_amd import synthetic
+    d = synthetic.spadl_games(2, seed=5)
+    off = d['game_off']
+    for c in ('start_x', 'end_y'):
+        d[c] = d[c].copy()
+        d[c][[0, 1, 127, 128, int(off[1]), int(off[2]) - 1]] = np.nan
+    cols = {c: d[c] for c in d if c not in ('game_off', 'home_team_id', 'seg', 'pos')}
+    feats = vo.features(cols, 3, vo.SPADL_DEFAULT, seg_off=off, home=list(d['home_team_id']))
+    X = np.stack([c[2].astype(np.float64) for c in feats], axis=1)
+    kinds = [c[1] for c in feats]
+    for n_trees in (0, 1, 7, 37):
+        m = bm.boundary_model(X, kinds, n_trees, seed=100 + n_trees)
+        assert m.n_trees == n_trees and m.max_margin <= 4.0
+        np.testing.assert_array_equal(to.predict_flat(m.flat_lt, 0.0, X, True, np.float32),
+                                      to.predict_xgboost_json(m.json, X))
+        if n_trees < 7:
+            continue
+        for lt, flat, dt in ((True, m.flat_lt, np.float32), (False, m.flat_le, np.float64)):
+            cov = bm.coverage(flat, X, kinds, lt, dt)
+            assert cov['num_tie_fraction'] >= 0.01 and cov['disagree_splits'] >= 1, cov
+            assert cov['nan_left'] >= 1 and cov['nan_right'] >= 1, cov
+            assert cov['const_left'] >= 1 and cov['const_right'] >= 1 and cov['f_tie_visits'] >= 1, cov
