@@ -1,6 +1,6 @@
 """Time the per-batch bucket pass of the band-owned count (K1 + K2 + K3, ``ops.xt_bucket``) on
 one 10k-game batch with HIP events -- for A/B of library builds chosen with
-SOCCERACTION_AMD_LIB (probe builds may write wrong keys; only the time is read)."""
+SOCCERACTION_AMD_LIB."""
 import json
 import os
 import sys

@@ -1,4 +1,4 @@
-/* The compact xT iteration (xt_iter_ell_kernel, SA_XE_QDIV) forms cnt / move as
+/* The compact iteration's quotient (xt_iter_ell_kernel): cnt / move is formed as
  *   r = RN(1 / move), y = RN(cnt * r), T = RN(y + r * RN(cnt - y * move))  (two fmas)
  * and relies on T == RN(cnt / move), the IEEE quotient the reference's numpy division gives.
  * This checks it on the host: every cnt < 65536 against divisors 1..D and 2^40 - D/2 .. 2^40 +

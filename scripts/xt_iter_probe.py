@@ -44,7 +44,6 @@ def main():
           for k in range(args.batches)]
     dev = bs[0].device
     acc = ops.xt_count_many(bs, l, w)
-    probe = os.environ.get('SOCCERACTION_AMD_LIB', '').split('_lib')[-1].startswith('/libsocceraction_amd_xtime')  # SA_XE_PROBE=16 build
     lib, C = _native.lib(), l * w
     p = lambda t: t.data_ptr()  # noqa: E731
     ell = torch.empty(int(lib.sa_xt_compact_bytes(C, C)) // 4, dtype=torch.int32, device=dev)
@@ -57,10 +56,7 @@ def main():
                                           p(gp[1]), stream_handle()))
     xo = torch.empty(C, dtype=torch.float64, device=dev)
     fl = torch.zeros(1, dtype=torch.int32, device=dev)
-    # the surface when the library is the product one, else (the probe build's values are
-    # wrong, its solve would not converge) a random x in [0, 0.1)
-    x = (torch.rand(C, dtype=torch.float64, device=dev) * 0.1 if probe
-         else ops.xt_solve(acc, transition=False).mats[3].contiguous())
+    x = ops.xt_solve(acc, transition=False).mats[3].contiguous()  # the surface
     lens = rl.cpu().numpy()
     ns = (C + 31) // 32
     slice_max = np.array([lens[32 * s:32 * s + 32].max() for s in range(ns)])
@@ -79,16 +75,6 @@ def main():
     mid = int(np.argsort(slice_max)[ns // 2])
     out['median_slice'] = {'slice': mid, 'len': int(slice_max[mid]), 'us': _ev(run(32 * mid, 32), args.reps)}
     out['first_k_slices_us'] = {k: _ev(run(0, min(C, 32 * k)), args.reps) for k in (8, 32, 64, 128)}
-    if probe:
-        ph = {}
-        for name, sl in (('longest', smax), ('shortest', smin), ('median', mid)):
-            run(32 * sl, 32)()
-            torch.cuda.synchronize()
-            v = xo[32 * sl:32 * sl + 44].cpu().numpy()  # chunks, then 100 MHz ticks from entry
-            ph[name] = {'chunks': int(v[0]), 'setup_us': v[1] / 100, 'chain_done_us': v[2] / 100,
-                        'clk_product_wave0_work_barrier': [int(v[40]), int(v[41])],
-                        'clk_chain_work_barrier': [int(v[42]), int(v[43])]}
-        out['phases_one_workgroup'] = ph
     print(json.dumps(out), flush=True)
 
 

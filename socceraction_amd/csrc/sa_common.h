@@ -148,12 +148,8 @@ __device__ __forceinline__ uint32_t xt_cell_code(int t, int r, double sx, double
 // Grids of C <= SA_XT_CELLS16_MAX_C cells (the small-grid count; 16 x 12) carry a 16-bit cell
 // code (include/socceraction_amd.h): s * C + e for a successful move with finite coordinates,
 // then the ranges below -- 2 B per action written by the feature pass and read by the count and
-// the rate instead of 4 (the bench step: 2.951 -> 2.935 ms, profiles/r05ap).  SA_XT_CELLS16=0
-// (A/B builds) keeps the u32 code for every grid.
-#ifndef SA_XT_CELLS16
-#define SA_XT_CELLS16 1
-#endif
-__host__ __device__ constexpr bool xt_c16(int C) { return SA_XT_CELLS16 && C <= SA_XT_CELLS16_MAX_C; }
+// the rate instead of 4 (the bench step: 2.951 -> 2.935 ms, profiles/r05ap).
+__host__ __device__ constexpr bool xt_c16(int C) { return C <= SA_XT_CELLS16_MAX_C; }
 constexpr uint32_t XT_C16_NONE = 0xFFFFu;
 // ranges (C <= 202 < 256, so no division decodes them): successful move with finite
 // coordinates s << 8 | e; shot with a finite start XT_C16_SHOT + 2 s + goal; a move with a finite

@@ -18,7 +18,6 @@
 // afterwards).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <type_traits>
 
@@ -38,17 +37,8 @@ struct TNode {  // 24 B
 constexpr int TR_THREADS = 1024;  // 16 waves share one LDS copy of the model
 constexpr int TR_LDS_NODES = 2048;  // 48 KB
 constexpr int TR_LDS_SLOTS = 2048;  // 8 KB
-#ifndef SA_TREE_SCALED
-#define SA_TREE_SCALED 1  // staged walk: condition byte offsets in the staged nodes (0: indices)
-#endif
-#ifndef SA_TREE_PERSIST
-#define SA_TREE_PERSIST 0  // staged walk grid: N x the resident workgroups looping over tiles (A/B: 1.19 ms vs 1.12 per learner at N = 1, r06i; 0: one per tile)
-#endif
 #ifndef SA_TREE_TG
 #define SA_TREE_TG 8
-#endif
-#ifndef SA_TREE_FIXED
-#define SA_TREE_FIXED 1  // tree_depth given: fixed-depth walk over self-looping leaves
 #endif
 constexpr int TG = SA_TREE_TG;      // trees walked together per thread
 static_assert(TG >= 1 && TG <= 32, "SA_TREE_TG: trees per thread");
@@ -470,7 +460,8 @@ __global__ __launch_bounds__(TS_ROWS) void tree_cond_kernel(CondSet<typename std
                                            (size_t)(P.n_nodes + (P.n_nodes & 1)) * sizeof(A));
   int32_t* BC = RD + 2 * TSP;  // the bool conditions' columns / bitmap rows
   const int tid = threadIdx.x;
-  const bool scaled = SA_TREE_SCALED && (int64_t)n_cond * TS_CSTRIDE <= 0x10000;  // uniform
+  // condition byte offsets in the staged nodes while they fit 16 bits (else indices); uniform
+  const bool scaled = (int64_t)n_cond * TS_CSTRIDE <= 0x10000;
   for (int k = tid; k < P.n_nodes; k += TS_ROWS) {
     const uint32_t nd = P.nodes[k];
     N[k] = scaled ? (nd & 0xFFFF0000u) | ((nd & 0xFFFFu) * TS_CSTRIDE) : nd;
@@ -483,7 +474,7 @@ __global__ __launch_bounds__(TS_ROWS) void tree_cond_kernel(CondSet<typename std
   for (int k = tid; k < C.n_bool; k += TS_ROWS) BC[k] = C.bool_cols[k];
   __syncthreads();
   // tiles blockIdx.x, + gridDim.x, ...: the model's tables above are staged once per workgroup
-  // (the grid is sized to the resident workgroups when SA_TREE_PERSIST, else one per tile)
+  // (the grid is one workgroup per tile)
   const int64_t tiles = (n + TS_ROWS - 1) / TS_ROWS;
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int64_t R0 = tile * TS_ROWS;
@@ -523,20 +514,20 @@ extern "C" int sa_tree_predict(const void* nodes, int32_t n_nodes, const int32_t
   const TNode* nd = (const TNode*)nodes;
   const bool staged = n_nodes <= TR_LDS_NODES && n_features <= TR_LDS_SLOTS;
   const size_t lds_bytes = (size_t)n_nodes * sizeof(TNode) + (size_t)n_features * sizeof(int32_t);
-  if (SA_TREE_FIXED && tree_depth && n_nodes <= TR_LDS_NODES && n_trees > 0) {
+  if (tree_depth && n_nodes <= TR_LDS_NODES && n_trees > 0) {
     const size_t fb = (size_t)n_nodes * (f32 ? sizeof(LNode<float>) : sizeof(LNode<double>));
-#define SA_TREE_FIXED_LAUNCH(F, LEQ)                                                                    \
+#define SA_TF_LAUNCH(F, LEQ)                                                                    \
   hipLaunchKernelGGL((tree_fixed_kernel<F, LEQ>), grid, block, fb, st, nd, n_nodes, roots, tree_depth, n_trees, \
                      feature_slots, Bb, Bf, Bi, n, base_margin, p_out)
     if (f32 && le)
-      SA_TREE_FIXED_LAUNCH(true, true);
+      SA_TF_LAUNCH(true, true);
     else if (f32)
-      SA_TREE_FIXED_LAUNCH(true, false);
+      SA_TF_LAUNCH(true, false);
     else if (le)
-      SA_TREE_FIXED_LAUNCH(false, true);
+      SA_TF_LAUNCH(false, true);
     else
-      SA_TREE_FIXED_LAUNCH(false, false);
-#undef SA_TREE_FIXED_LAUNCH
+      SA_TF_LAUNCH(false, false);
+#undef SA_TF_LAUNCH
     return check_launch("tree_fixed_kernel");
   }
 #define SA_TREE_LAUNCH(F, S)                                                                       \
@@ -591,23 +582,14 @@ extern "C" int sa_tree_predict_staged(const sa_tree_model* model, const int32_t*
   const int64_t tiles = (n + TS_ROWS - 1) / TS_ROWS;
   const dim3 block(TS_ROWS);
   hipStream_t st = (hipStream_t)stream;
-  // SA_TREE_PERSIST: as many workgroups as are resident at once (each stages the model's tables
-  // once and loops over tiles); else one workgroup per tile
+  // one workgroup per tile
 #define SA_TS_LAUNCH(F, LEQ, A, N32)                                                                     \
   do {                                                                                                  \
     CondSet<A> C{bool_cols, num_cols, col_start, (const A*)num_thr, num_dl, n_bool, n_num > 0 ? n_ncol : 0, \
                  n_num};                                                                                \
     CondModel<A> P{(const uint32_t*)m.nodes, (const A*)m.leaf, m.roots, m.tree_depth, m.n_nodes,        \
                    m.n_trees,                m.base_margin,    m.p_out};                                \
-    int64_t g = tiles;                                                                                  \
-    if (SA_TREE_PERSIST) {                                                                              \
-      int per_cu = 0;                                                                                   \
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tree_cond_kernel<F, LEQ, N32>, TS_ROWS, \
-                                                       (size_t)lds) != hipSuccess || per_cu < 1)        \
-        per_cu = 1;                                                                                     \
-      g = std::min<int64_t>(tiles, (int64_t)per_cu * device_cus(current_device()) * SA_TREE_PERSIST);   \
-    }                                                                                                   \
-    hipLaunchKernelGGL((tree_cond_kernel<F, LEQ, N32>), dim3((unsigned)g), block, (size_t)lds, st, C, P, Bb, \
+    hipLaunchKernelGGL((tree_cond_kernel<F, LEQ, N32>), dim3((unsigned)tiles), block, (size_t)lds, st, C, P, Bb, \
                        bool_bits, bits_stride, Bf, Bi, n);                                               \
   } while (0)
   const bool n32 = (f32 & 2) != 0;  // float32 numeric blocks

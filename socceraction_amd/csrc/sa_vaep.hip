@@ -18,8 +18,10 @@
 //
 // Compile-time knobs (the default build is the measured configuration; variants are built
 // with `python -m socceraction_amd.build -DNAME=V --variant=tag`): SA_NT_STORES (non-temporal
-// stores), SA_XCD_REMAP (XCD-contiguous block order), SA_CG_COLS (bool columns per wave),
-// SA_DEBUG (device bounds checks, sa_debug.h).
+// stores), SA_NUM_NTL (non-temporal loads of the numeric pass's streamed inputs), SA_XCD_REMAP
+// (XCD-contiguous block order), SA_CG_COLS (bool columns per wave), SA_NUM_BLOCK_WAVES (numeric-pass
+// workgroup), SA_NUM_WAVES (numeric-pass VGPR cap), SA_DEBUG (device bounds checks, sa_debug.h).
+// Each sizes or tunes the one kernel of its job; no knob selects another code path.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -361,11 +363,7 @@ __device__ __forceinline__ void st_f64x2(double* __restrict__ base, int64_t col,
                                          double v0, double v1) {
   f64x2 v = {v0, v1};
   SA_DGUARD(col >= 0 && col < C, col, return);
-#if SA_NUM_PROBE & 8  // probe: the f64 block is not written (wrong outputs)
-  if (v0 == 1.2345e300) st16(base + col * R, v);
-#else
   st16(base + col * R, v);
-#endif
 }
 
 __device__ __forceinline__ void st_i64x2(int64_t* __restrict__ base, int64_t col, int64_t C, int64_t R,
@@ -400,36 +398,11 @@ __device__ __forceinline__ void st_i64x2(float* __restrict__ base, int64_t col, 
   st16(base + col * R, v);
 }
 
-// SA_NUM_PROBE (diagnostic builds only, wrong values): bit 0 = no transcendental math in the
-// numeric pass (sqrt / atan / division replaced by an add), bit 1 = no goalscore carry pass,
-// bit 2 = no coordinate / time reads, bit 3 = no f64-block stores, bit 7 = coordinate / time
-// reads from the first 8192 rows (L2 hits), bit 5 = no goalscore /
-// label / formula stores (the stores that precede the main row loads).
-#ifndef SA_NUM_PROBE
-#define SA_NUM_PROBE 0
-#endif
-#ifndef SA_COND_FAMILY
-#define SA_COND_FAMILY 1  // the COND pass in family-major column order (0: window-major, A/B)
-#endif
-#ifndef SA_NUM_FAMILY_MAJOR
-#define SA_NUM_FAMILY_MAJOR 0  // numeric pass store order (num_features_kernel, KF = 3)
-#endif
-#if SA_NUM_PROBE & 1
-#define NUM_SQRT(x) (x)
-#else
-#define NUM_SQRT(x) sqrt(x)
-#endif
-
 // nan_to_num(arctan(dy / dx)) of vaep/features.py:376 (atan(+-inf) = +-pi/2, 0/0 -> 0)
 __device__ __forceinline__ double polar_angle(double dy, double dx) {
-#if SA_NUM_PROBE & 1
-  return dy + dx;
-#else
   const double a = atan(dy / dx);
   return isnan(a) ? 0.0 : a;
-#endif
 }
-
 
 // goal / owngoal bytes of a word of type / result bytes (vaep/labels.py:28-33;
 // atomic/vaep/labels.py:27-28)
@@ -496,9 +469,6 @@ constexpr int BOOL_TILE = 1024;  // rows per tile of the bool block image
 // windows from the id columns (L2 hits: a tile's groups run back to back on one XCD) and
 // writes only the (family, window, value) columns inside its range.
 constexpr int CG_WAVES = 4;  // waves per workgroup
-#ifndef SA_BOOL_PROBE
-#define SA_BOOL_PROBE 0
-#endif
 #define CG_EQ(w, v) bytes_eq((w), (v))
 
 // WIDE (windowed mode, nb_prev_actions > 9: windows reach past the 8-row halo): each window's
@@ -506,8 +476,7 @@ constexpr int CG_WAVES = 4;  // waves per workgroup
 constexpr int BOOL_HALO = 8;  // rows before j0 held in registers: windows i <= 8 (k <= 9)
 constexpr int WIDE_D_MAX = 1 << 30;
 
-// The pass over logical workgroup `lblock` (bool_colgroup_kernel; and the bool workgroups of the
-// SA_FUSED_STEP probe's one-launch step).
+// The pass over logical workgroup `lblock` (bool_colgroup_kernel).
 template <bool ATOMIC, bool EXPLICIT, bool BITS, bool WIDE>
 __device__ __forceinline__ void bool_colgroup_body(const FeatArgs& args, int ngroups, int gcols,
                                                    int64_t lblock) {
@@ -556,11 +525,7 @@ __device__ __forceinline__ void bool_colgroup_body(const FeatArgs& args, int ngr
   uint32_t TR[6], RR[6], BR[6];  // rows j0-8 .. j0+15 (windowed mode)
   uint32_t tw[4], rw[4], bw[4];  // window i of the lane's 16 actions
   if (!EXPLICIT && !WIDE) {
-#if SA_BOOL_PROBE & 1  // probe: the id words from the first 8K rows (L2 hits; wrong values)
-    const int64_t wbase = ((j0 / 4) & 2047) + 2 - 2;
-#else
     const int64_t wbase = j0 / 4 - 2;
-#endif
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
       TR[k] = ld_u8x4(F0.type_id, wbase + k, n);
@@ -699,13 +664,8 @@ __device__ __forceinline__ void bool_colgroup_body(const FeatArgs& args, int ngr
           SA_DCHECK(s >= 0 && (WIDE || s <= BOOL_HALO), s);
           // team codes straight from L1/L2 (a few waves per tile need them): the kernel keeps
           // no LDS, so xT workgroups with large LDS footprints co-reside with it
-#if SA_BOOL_PROBE & 1
-          t0 = ld_or0(F0.team, ((j0 + mm) & 8191) + 16, n);
-          ti = ld_or0(F0.team, ((j0 + mm) & 8191) + 16 - s, n);
-#else
           t0 = ld_or0(F0.team, j0 + mm, n);
           ti = ld_or0(F0.team, j0 + mm - s, n);
-#endif
         }
         if (BITS)  // strided order: word mm & 3, byte mm >> 2
           m[mm & 3] |= (uint32_t)(t0 == ti) << (8 * (mm >> 2));
@@ -777,7 +737,7 @@ __device__ __forceinline__ void emit_window(const NumCols& C, int i, const Win& 
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
         const double dx = fabs(FIELD_L - w.c0[e]), dy = fabs(GOAL_Y - w.c1[e]);
-        dist[e] = NUM_SQRT(dx * dx + dy * dy);
+        dist[e] = sqrt(dx * dx + dy * dy);
         ang[e] = polar_angle(dy, dx);
       }
       st_f64x2(fb, C.sp + 2 * i, C.nf, Rf, dist[0], dist[1]);
@@ -788,7 +748,7 @@ __device__ __forceinline__ void emit_window(const NumCols& C, int i, const Win& 
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
         const double dx = fabs(FIELD_L - w.c2[e]), dy = fabs(GOAL_Y - w.c3[e]);
-        dist[e] = NUM_SQRT(dx * dx + dy * dy);
+        dist[e] = sqrt(dx * dx + dy * dy);
         ang[e] = polar_angle(dy, dx);
       }
       st_f64x2(fb, C.ep + 2 * i, C.nf, Rf, dist[0], dist[1]);
@@ -800,7 +760,7 @@ __device__ __forceinline__ void emit_window(const NumCols& C, int i, const Win& 
       for (int e = 0; e < 2; ++e) {
         mdx[e] = w.c2[e] - w.c0[e];
         mdy[e] = w.c3[e] - w.c1[e];
-        mv[e] = NUM_SQRT(mdx[e] * mdx[e] + mdy[e] * mdy[e]);
+        mv[e] = sqrt(mdx[e] * mdx[e] + mdy[e] * mdy[e]);
       }
       st_f64x2(fb, C.mv + 3 * i, C.nf, Rf, mdx[0], mdx[1]);
       st_f64x2(fb, C.mv + 3 * i + 1, C.nf, Rf, mdy[0], mdy[1]);
@@ -812,7 +772,7 @@ __device__ __forceinline__ void emit_window(const NumCols& C, int i, const Win& 
       for (int e = 0; e < 2; ++e) {
         sdx[e] = w.c2[e] - sx0[e];
         sdy[e] = w.c3[e] - sy0[e];
-        sm[e] = NUM_SQRT(sdx[e] * sdx[e] + sdy[e] * sdy[e]);
+        sm[e] = sqrt(sdx[e] * sdx[e] + sdy[e] * sdy[e]);
       }
       st_f64x2(fb, C.sd + 3 * (i - 1), C.nf, Rf, sdx[0], sdx[1]);
       st_f64x2(fb, C.sd + 3 * (i - 1) + 1, C.nf, Rf, sdy[0], sdy[1]);
@@ -828,7 +788,7 @@ __device__ __forceinline__ void emit_window(const NumCols& C, int i, const Win& 
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
         const double dx = fabs(FIELD_L - w.c0[e]), dy = fabs(GOAL_Y - w.c1[e]);
-        dist[e] = NUM_SQRT(dx * dx + dy * dy);
+        dist[e] = sqrt(dx * dx + dy * dy);
         ang[e] = polar_angle(dy, dx);
       }
       st_f64x2(fb, C.po + 2 * i, C.nf, Rf, dist[0], dist[1]);
@@ -919,23 +879,11 @@ __device__ __forceinline__ V ld_stream(const V* p) {  // BIT 1: coordinates / ti
 
 // rows r, r+1 (r even: 16-B aligned f64 pairs, 2-B aligned id pairs)
 __device__ __forceinline__ void load_pair(const sa_frame& F, int64_t r, bool atomic, Row& a, Row& b) {
-#if SA_NUM_PROBE & 4  // probe: no coordinate / time reads (wrong values)
-  const double q = (double)(r & 1023);
-  const f64x2 x0 = {q, q + 1}, x1 = {q * 0.5, q}, x2 = {q + 3, q}, x3 = {q, q * 0.25}, x4 = {q, q + 2};
-#elif SA_NUM_PROBE & 128  // probe: coordinate / time reads from the first 8192 rows (L2 hits; wrong values)
-  const int64_t rq = r & 8190;
-  const f64x2 x0 = *reinterpret_cast<const f64x2*>(F.c0 + rq);
-  const f64x2 x1 = *reinterpret_cast<const f64x2*>(F.c1 + rq);
-  const f64x2 x2 = *reinterpret_cast<const f64x2*>(F.c2 + rq);
-  const f64x2 x3 = *reinterpret_cast<const f64x2*>(F.c3 + rq);
-  const f64x2 x4 = *reinterpret_cast<const f64x2*>(F.time_seconds + rq);
-#else
   const f64x2 x0 = ld_stream(reinterpret_cast<const f64x2*>(F.c0 + r));
   const f64x2 x1 = ld_stream(reinterpret_cast<const f64x2*>(F.c1 + r));
   const f64x2 x2 = ld_stream(reinterpret_cast<const f64x2*>(F.c2 + r));
   const f64x2 x3 = ld_stream(reinterpret_cast<const f64x2*>(F.c3 + r));
   const f64x2 x4 = ld_stream(reinterpret_cast<const f64x2*>(F.time_seconds + r));
-#endif
   const uint32_t pe = *reinterpret_cast<const uint16_t*>(F.period_id + r);
   const uint32_t ty = *reinterpret_cast<const uint16_t*>(F.type_id + r);
   const uint32_t rs = atomic ? 0u : *reinterpret_cast<const uint16_t*>(F.result_id + r);
@@ -1033,7 +981,7 @@ __device__ __forceinline__ void goalscore_pair(const sa_actions& A, int64_t wb, 
   const int lane = threadIdx.x & (WAVE - 1);
   const SegCursor c0 = wave_cursor(A, wb);  // segment of the wave's first row (uniform)
   uint64_t carry = 0;
-  if (c0.s < wb && !(SA_NUM_PROBE & 2)) carry = wave_goals<ATOMIC>(F, n, c0.s, wb, F.team[c0.s]);
+  if (c0.s < wb) carry = wave_goals<ATOMIC>(F, n, c0.s, wb, F.team[c0.s]);
   bool gA[2], gB[2], isA[2];
   int64_t s[2];
 #pragma unroll
@@ -1173,7 +1121,7 @@ __device__ __forceinline__ void labels_pair(const sa_actions& A, int nr, int64_t
 __device__ __forceinline__ void labels_store(int64_t n, uint8_t* __restrict__ sc, uint8_t* __restrict__ co,
                                              uint8_t* __restrict__ gfs, int64_t jb, uint32_t so, uint32_t cout,
                                              uint32_t go) {
-  if (jb < n && !(SA_NUM_PROBE & 32)) {
+  if (jb < n) {
     if (jb + 1 < n) {
       if (sc) *reinterpret_cast<uint16_t*>(sc + jb) = (uint16_t)so;
       if (co) *reinterpret_cast<uint16_t*>(co + jb) = (uint16_t)cout;
@@ -1201,8 +1149,8 @@ template <bool ATOMIC, bool TAIL>
 constexpr int num_min_waves() {
   return SA_NUM_WAVES > 0 ? SA_NUM_WAVES : 1;
 }
-// The pass over the wave's 128 rows from wave_base.  F0: frames[0] with the streamed columns
-// (coordinates, time) where the caller wants them read from; ps / pc: the probabilities (TAIL).
+// The pass over the wave's 128 rows from wave_base.  F0: frames[0] of args; ps_in / pc_in: the
+// probabilities (TAIL).
 template <bool ATOMIC, bool EXPLICIT, int KF, bool TAIL = false, bool N32 = false, bool COND = false>
 __device__ __forceinline__ void num_features_body(const FeatArgs& args, int64_t wave_base, const sa_frame& F0,
                                                   const double* ps_in, const double* pc_in) {
@@ -1303,24 +1251,16 @@ __device__ __forceinline__ void num_features_body(const FeatArgs& args, int64_t 
       away[e] = A.home_team != nullptr && F0.team[j] != A.home_team[cur.g];
     }
     // -- every load is out; the stores follow
-    if (gcol >= 0 && (jw < n || COND) && !(SA_NUM_PROBE & 32)) {  // condition sinks: whole wave, tail masked
+    if (gcol >= 0 && (jw < n || COND)) {  // condition sinks: whole wave, tail masked
 #pragma unroll
       for (int k = 0; k < 3; ++k) st_i64x2(gib, gcol + k, (int)args.Ci, Ri, gs[k][0], gs[k][1]);
     }
     if (TAIL) {
       labels_store(n, args.sc, args.co, args.gfs, jw, lso, lco, lgo);
-      if (fok && !(SA_NUM_PROBE & 32)) {
-#if SA_NUM_PROBE & 64  // probe: the formula values into the f64 tile's last three columns
-        if constexpr (!COND && !N32) {
-          st16(fb + (args.Cf - 3) * Rf, fo);
-          st16(fb + (args.Cf - 2) * Rf, fd);
-          st16(fb + (args.Cf - 1) * Rf, fv);
-        }
-#else
+      if (fok) {
         st16(args.off + jw, fo);
         st16(args.def + jw, fd);
         st16(args.val + jw, fv);
-#endif
       }
     }
   }
@@ -1375,10 +1315,10 @@ __device__ __forceinline__ void num_features_body(const FeatArgs& args, int64_t 
           args.xt_cells[jb] = cc[0];
         }
       }
-      // COND: the family-major order too -- the condition tables are numbered by column, so
-      // visiting the columns in block order moves through each 64-condition chunk once (a chunk
-      // change flushes the held bitmaps: window-major order changed chunks ~12 times per wave)
-      if constexpr (SA_NUM_FAMILY_MAJOR || (COND && SA_COND_FAMILY)) {
+      // COND: family-major order -- the condition tables are numbered by column, so visiting the
+      // columns in block order moves through each 64-condition chunk once (a chunk change flushes
+      // the held bitmaps: window-major order changed chunks ~12 times per wave)
+      if constexpr (COND) {
       // family by family, each family's windows back to back: the block columns are
       // family-major with the windows adjacent, so the wave writes its [C x 128] slab front to
       // back instead of jumping by the family width for every window.  Window i of action e
@@ -1531,90 +1471,6 @@ void num_cond_lds_kernel(FeatArgs args) {
   const int64_t wave_base = args.row0 + (xcd_logical_block() * BLOCK_WAVES + wv) * WAVE_ACTS;
   num_features_body<ATOMIC, false, 3, false, false, true>(a, wave_base, a.a.frames[0], a.ps, a.pc);
 }
-
-// SA_FUSED_STEP = 1 (probe builds): the SPADL step's bool pass and numeric step pass as ONE
-// launch, their workgroups interleaved in proportion (logical workgroup L is a bool one when
-// floor((L + 1) nb / T) > floor(L nb / T)), so each CU mixes the pure-store bool tiles with the
-// read-heavy numeric tiles of the same rows, whose inputs the two then share in L2.  The A/B of
-// the headline's one bounded experiment (scripts/fused_step_ab.py).
-#ifndef SA_COND_LDS
-#define SA_COND_LDS 1  // 0: the COND pass reads its condition tables from global memory (A/B)
-#endif
-#ifndef SA_FUSED_STEP
-#define SA_FUSED_STEP 0
-#endif
-#if SA_FUSED_STEP
-static_assert(CG_WAVES == BLOCK_WAVES, "one workgroup shape for both passes");
-__global__ __launch_bounds__(64 * BLOCK_WAVES) void step_fused_kernel(FeatArgs args, int ngroups, int gcols,
-                                                                      int64_t nb, int64_t total) {
-  const int64_t L = xcd_logical_block();
-  if (L >= total) return;
-  const int64_t bi = L * nb / total;
-  if ((L + 1) * nb / total > bi) {
-    bool_colgroup_body<false, false, false, false>(args, ngroups, gcols, bi);
-  } else {
-    const int wv = threadIdx.x / WAVE;
-    const int64_t wave_base = args.row0 + ((L - bi) * BLOCK_WAVES + wv) * WAVE_ACTS;
-    num_features_body<false, false, 3, true, false, false>(args, wave_base, args.a.frames[0], args.ps, args.pc);
-  }
-}
-#endif
-
-// SA_NUM_STAGE = T > 0 (probe builds): the SPADL step pass with each workgroup's streamed inputs
-// -- coordinates, time and the two probabilities of T x 512 rows (56 B per row) plus the two rows
-// before -- loaded into LDS in one burst before any of the T tiles' stores; the tiles then read
-// those columns from LDS.  The experiment on the read / write turnaround of the numeric pass
-// (profiles/r03_numeric_pass_ab.md): does separating a CU's reads from its stores in time help?
-#ifndef SA_NUM_STAGE
-#define SA_NUM_STAGE 0
-#endif
-#if SA_NUM_STAGE > 0
-constexpr int STG_T = SA_NUM_STAGE;
-constexpr int STG_ROWS = STG_T * BLOCK_ACTS + 2;
-constexpr int STG_NP = (STG_ROWS / 2 + 255) / 256;  // row pairs per thread per column
-__global__ __launch_bounds__(256) void num_staged_kernel(FeatArgs args) {
-  extern __shared__ __attribute__((aligned(16))) double stg[];  // [7][STG_ROWS]
-  const sa_frame& G = args.a.frames[0];
-  const int64_t n = args.a.n;
-  const int64_t row0 = xcd_logical_block() * (int64_t)(STG_T * BLOCK_ACTS);
-  if (row0 >= n) return;
-  const int64_t lo = row0 - 2;  // LDS row i = row lo + i
-  const int64_t hi = min(n, row0 + (int64_t)STG_T * BLOCK_ACTS);
-  const double* src[7] = {G.c0, G.c1, G.c2, G.c3, G.time_seconds, args.ps, args.pc};
-  const int ncol = args.ps ? 7 : 5;
-  for (int c = 0; c < ncol; ++c) {  // every load of the column before its LDS stores
-    f64x2 v[STG_NP];
-#pragma unroll
-    for (int q = 0; q < STG_NP; ++q) {
-      const int pr = q * 256 + threadIdx.x;
-      const int64_t r = lo + 2 * (int64_t)pr;
-      v[q] = f64x2{0.0, 0.0};
-      if (pr < STG_ROWS / 2 && r >= 0) {
-        if (r + 1 < hi) v[q] = ld_stream(reinterpret_cast<const f64x2*>(src[c] + r));
-        else if (r < hi) v[q][0] = src[c][r];
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < STG_NP; ++q) {
-      const int pr = q * 256 + threadIdx.x;
-      if (pr < STG_ROWS / 2) *reinterpret_cast<f64x2*>(stg + c * STG_ROWS + 2 * pr) = v[q];
-    }
-  }
-  __syncthreads();
-  sa_frame F = G;
-  F.c0 = stg - lo;
-  F.c1 = stg + STG_ROWS - lo;
-  F.c2 = stg + 2 * STG_ROWS - lo;
-  F.c3 = stg + 3 * STG_ROWS - lo;
-  F.time_seconds = stg + 4 * STG_ROWS - lo;
-  const double* ps = args.ps ? stg + 5 * STG_ROWS - lo : nullptr;
-  const double* pc = args.ps ? stg + 6 * STG_ROWS - lo : nullptr;
-  const int wv = threadIdx.x / WAVE;
-#pragma unroll 1
-  for (int t = 0; t < STG_T; ++t)
-    num_features_body<false, false, 3, true>(args, row0 + (int64_t)t * BLOCK_ACTS + wv * WAVE_ACTS, F, ps, pc);
-}
-#endif
 
 // ------------------------------------------------------------------------------ goalscore
 // features.py:505-539 / atomic/vaep/features.py:229-260: per segment, teamA = team of the
@@ -2106,16 +1962,227 @@ __global__ __launch_bounds__(256) void prefetch_rows_kernel(sa_actions A, const 
   if (h == 0x5A5A5A5A5A5A5A5Aull) sink[0] = (uint32_t)h;  // never in practice: keeps the loads
 }
 
-static int launch_features(const sa_actions* a, const sa_feature_plan* plan, const sa_block* bool_out,
-                           const sa_block* f64_out, const sa_block* i64_out, int32_t xt_l,
-                           int32_t xt_w, uint32_t* xt_cells, void* stream, uint8_t* bits = nullptr,
-                           int64_t bits_stride = 0, int32_t n_bits = 0, const TailArgs* tail = nullptr,
-                           bool num32 = false, const FeatArgs* cond = nullptr);
+// Argument checks shared by the entry points (each keeps its own order of checks).
+// The label columns: leading dimension and alignment.
+static int check_label_outputs(int64_t n, const uint8_t* scores, const uint8_t* concedes,
+                               const uint8_t* goal_from_shot, int64_t ld) {
+  if (ld % 16 != 0 || ld < ((n + 15) / 16) * 16)
+    return fail(SA_EINVAL, "ld must be a multiple of 16 and >= round_up(n, 16)");
+  if (!aligned16(scores) || !aligned16(concedes) || !aligned16(goal_from_shot))
+    return fail(SA_EINVAL, "label outputs must be 16-byte aligned");
+  return SA_OK;
+}
+
+// The formula's probabilities and outputs; `length` is the entry point's padded output length as
+// its message words it ("round_up(n, 4)" for the formula alone, "round_up(n, 16)" beside labels).
+template <typename T>
+static int check_formula_args(const T* ps, const T* pc, const T* off, const T* def, const T* val,
+                              const char* length) {
+  if (!ps || !pc || !off || !def || !val) return fail(SA_EINVAL, "null probability/output pointer");
+  if (!aligned16(off) || !aligned16(def) || !aligned16(val))
+    return fail(SA_EINVAL, "formula outputs must be 16-byte aligned (length >= %s)", length);
+  return SA_OK;
+}
+
+// The bool bitmaps (one bit per action, 16 actions per u16 word).
+static int check_bool_bits(int64_t n, const uint8_t* bool_bits, int64_t bits_stride, int32_t n_bool_cols) {
+  if (!bool_bits || n_bool_cols < 1 || bits_stride < 2 * ((n + 15) / 16) || bits_stride % 2 ||
+      ((uintptr_t)bool_bits & 1u))
+    return fail(SA_EINVAL, "bool bitmaps: even stride of at least ceil(n/16)*2 bytes, 2-byte aligned");
+  return SA_OK;
+}
+
+struct FeatReq {  // what one feature pass writes; an entry point fills the fields it uses
+  const sa_block *bool_out, *f64_out, *i64_out;  // the three blocks (f64 / i64: float32 when num32)
+  int32_t xt_l, xt_w;       // with xt_cells: the xT cell code of every action
+  uint32_t* xt_cells;
+  uint8_t* bits;            // the bool features as bitmaps instead of bool_out
+  int64_t bits_stride;      // bytes per bitmap
+  int32_t n_bits;           // bitmaps (the bool columns)
+  const TailArgs* tail;     // labels + f64 formula in the numeric pass
+  bool num32;               // float32 numeric blocks
+  const FeatArgs* cond;     // the condition tables: the numeric columns as condition bitmaps
+};
+
+static int launch_features(const sa_actions* a, const sa_feature_plan* plan, const FeatReq& q, void* stream) {
+  const sa_block *bool_out = q.bool_out, *f64_out = q.f64_out, *i64_out = q.i64_out;
+  uint8_t* const bits = q.bits;
+  const TailArgs* const tail = q.tail;
+  const FeatArgs* const cond = q.cond;
+  int rc = check_actions(a, true);
+  if (rc) return rc;
+  if (!plan) return fail(SA_EINVAL, "null plan");
+  const int K = plan->nb_prev_actions;
+  if (K < 1) return fail(SA_EINVAL, "nb_prev_actions must be >= 1");
+  if (a->n_frames > 1 && a->n_frames != K)
+    return fail(SA_EINVAL, "explicit mode needs n_frames == nb_prev_actions");
+  bool wb = false, wf = false, wi = false, wn = false;
+  for (int x = 0; x < SA_XFN_COUNT; ++x) {
+    wb |= plan->bool_col[x] >= 0;
+    wf |= plan->f64_col[x] >= 0;
+    wi |= plan->i64_col[x] >= 0;
+    wn |= plan->f64_col[x] >= 0 || (plan->i64_col[x] >= 0 && x != SA_XFN_GOALSCORE);
+  }
+  if (wb && !bits && (rc = check_block(bool_out, a->n, SA_BOOL_TILE_QUANTUM, "bool"))) return rc;
+  if (wf && (rc = check_block(f64_out, a->n, SA_NUM_TILE_QUANTUM, "f64"))) return rc;
+  if (wi && (rc = check_block(i64_out, a->n, SA_NUM_TILE_QUANTUM, "i64"))) return rc;
+  for (int x = 0; x < SA_XFN_COUNT; ++x) {
+    if ((wb && plan->bool_col[x] >= (bits ? q.n_bits : bool_out->n_cols)) || (wf && plan->f64_col[x] >= f64_out->n_cols) ||
+        (wi && plan->i64_col[x] >= i64_out->n_cols))
+      return fail(SA_EINVAL, "plan column offset beyond the block's column count");
+  }
+  if (a->atomic) {
+    const int spadl_only[] = {SA_XFN_RESULT, SA_XFN_RESULT_ONEHOT, SA_XFN_ACTIONTYPE_RESULT_ONEHOT,
+                              SA_XFN_STARTLOCATION, SA_XFN_ENDLOCATION, SA_XFN_STARTPOLAR,
+                              SA_XFN_ENDPOLAR, SA_XFN_MOVEMENT, SA_XFN_SPACE_DELTA};
+    for (int x : spadl_only)
+      if (plan->bool_col[x] >= 0 || plan->f64_col[x] >= 0 || plan->i64_col[x] >= 0)
+        return fail(SA_EINVAL, "transformer %d is not defined for atomic actions", x);
+  } else {
+    const int atomic_only[] = {SA_XFN_LOCATION, SA_XFN_POLAR, SA_XFN_MOVEMENT_POLAR, SA_XFN_DIRECTION};
+    for (int x : atomic_only)
+      if (plan->bool_col[x] >= 0 || plan->f64_col[x] >= 0 || plan->i64_col[x] >= 0)
+        return fail(SA_EINVAL, "transformer %d is only defined for atomic actions", x);
+  }
+  if (a->n == 0) return SA_OK;
+  hipStream_t st = (hipStream_t)stream;
+  FeatArgs args{*a,
+                *plan,
+                wb && !bits ? (uint8_t*)bool_out->data : nullptr,
+                wf ? (double*)f64_out->data : nullptr,
+                wi ? (int64_t*)i64_out->data : nullptr,
+                wb ? (bits ? (int64_t)q.n_bits : bool_out->n_cols) : 0,
+                wf ? f64_out->n_cols : 0,
+                wi ? i64_out->n_cols : 0,
+                wb && !bits ? bool_out->tile_rows : BOOL_TILE,
+                wf ? f64_out->tile_rows : 16,
+                wi ? i64_out->tile_rows : 16,
+                q.xt_cells,
+                q.xt_l,
+                q.xt_w,
+                (wb || cond) ? (uint16_t*)bits : nullptr,  // COND: the condition rows even with no bool column
+                q.bits_stride / 2,
+                tail ? tail->nr : 0,
+                tail ? tail->sc : nullptr,
+                tail ? tail->co : nullptr,
+                tail ? tail->gfs : nullptr,
+                tail ? tail->ps : nullptr,
+                tail ? tail->pc : nullptr,
+                tail ? tail->off : nullptr,
+                tail ? tail->def : nullptr,
+                tail ? tail->val : nullptr,
+                tail ? (aligned16(tail->ps) && aligned16(tail->pc)) : false,
+                cond ? cond->cond_fstart : nullptr,
+                cond ? cond->cond_istart : nullptr,
+                cond ? cond->cond_thr : nullptr,
+                cond ? cond->cond_dl : nullptr,
+                cond ? cond->cond_row0 : 0};
+  args.cond_n = cond ? cond->cond_n : 0;
+  const dim3 grid(xcd_grid((a->n + BLOCK_ACTS - 1) / BLOCK_ACTS)), block(BLOCK_WAVES * WAVE);
+  const bool expl = a->n_frames > 1, atomic = a->atomic != 0;
+  if (wb) {  // one wave per (tile, group of ~32 columns), XCD-contiguous sweep order
+    const int ng = (int)((args.Cb + SA_CG_COLS - 1) / SA_CG_COLS);
+    const int gc = (int)((args.Cb + ng - 1) / ng);
+    const int64_t waves = (a->n + BOOL_TILE - 1) / BOOL_TILE * ng;
+    const dim3 cgrid(xcd_grid((waves + CG_WAVES - 1) / CG_WAVES)), cblock(WAVE * CG_WAVES);
+    const bool wide = !expl && K > BOOL_HALO + 1;  // windows past the register halo
+#define SA_BOOL_LAUNCH(ATOMIC, EXPLICIT, BITS, WIDE) \
+  hipLaunchKernelGGL((bool_colgroup_kernel<ATOMIC, EXPLICIT, BITS, WIDE>), cgrid, cblock, 0, st, args, ng, gc)
+    if (bits) {  // the on-device VAEP.rate: SPADL or atomic, windowed, as bitmaps
+      if (wide && atomic)
+        SA_BOOL_LAUNCH(true, false, true, true);
+      else if (wide)
+        SA_BOOL_LAUNCH(false, false, true, true);
+      else if (atomic)
+        SA_BOOL_LAUNCH(true, false, true, false);
+      else
+        SA_BOOL_LAUNCH(false, false, true, false);
+    } else if (atomic) {
+      if (expl)
+        SA_BOOL_LAUNCH(true, true, false, false);
+      else if (wide)
+        SA_BOOL_LAUNCH(true, false, false, true);
+      else
+        SA_BOOL_LAUNCH(true, false, false, false);
+    } else {
+      if (expl)
+        SA_BOOL_LAUNCH(false, true, false, false);
+      else if (wide)
+        SA_BOOL_LAUNCH(false, false, false, true);
+      else
+        SA_BOOL_LAUNCH(false, false, false, false);
+    }
+#undef SA_BOOL_LAUNCH
+    rc = check_launch("bool_colgroup_kernel");
+    if (rc) return rc;
+  }
+  const int gc = plan->i64_col[SA_XFN_GOALSCORE];
+  if (wn || q.xt_cells || tail || (gc >= 0 && !expl)) {  // windowed mode: goalscore fused into this pass
+    const bool fast = !expl && K <= 3;  // register-resident windows (KF = 3)
+    // num_features_kernel<ATOMIC, EXPLICIT, KF, TAIL, N32, COND> on grid G
+#define SA_NUM_LAUNCH(G, ...) hipLaunchKernelGGL((num_features_kernel<__VA_ARGS__>), G, block, 0, st, args)
+    if (cond && cond_lds_bytes(args.Cf, args.Ci, args.cond_n) <= COND_LDS_MAX) {
+      const size_t lds = (size_t)cond_lds_bytes(args.Cf, args.Ci, args.cond_n);
+      if (atomic)
+        hipLaunchKernelGGL(num_cond_lds_kernel<true>, grid, block, lds, st, args);
+      else
+        hipLaunchKernelGGL(num_cond_lds_kernel<false>, grid, block, lds, st, args);
+    } else if (cond) {  // windowed, K <= 3 (checked by sa_vaep_features_conditions)
+      if (atomic)
+        SA_NUM_LAUNCH(grid, true, false, 3, false, false, true);
+      else
+        SA_NUM_LAUNCH(grid, false, false, 3, false, false, true);
+    } else if (q.num32) {  // windowed, K <= 3 (checked by sa_vaep_features_bits_f32)
+      if (atomic)
+        SA_NUM_LAUNCH(grid, true, false, 3, false, true);
+      else
+        SA_NUM_LAUNCH(grid, false, false, 3, false, true);
+    } else if (tail && tail->chunk > 0 && !atomic) {  // sa_vaep_step_f64_chunked (probe)
+      for (int64_t c0 = 0; c0 < a->n; c0 += tail->chunk) {
+        const int64_t c1 = c0 + tail->chunk < a->n ? c0 + tail->chunk : a->n;
+        if (tail->prefetch) {
+          const int64_t th = (c1 - c0 + 3) / 4;
+          hipLaunchKernelGGL(prefetch_rows_kernel, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, st, *a,
+                             tail->ps, tail->pc, c0, c1, q.xt_cells);
+        }
+        args.row0 = c0;
+        args.row_end = c1;
+        const dim3 cg(xcd_grid((c1 - c0 + BLOCK_ACTS - 1) / BLOCK_ACTS));
+        SA_NUM_LAUNCH(cg, false, false, 3, true);
+      }
+    } else if (tail) {  // windowed, K <= 3 (checked by sa_vaep_step_f64)
+      if (atomic)
+        SA_NUM_LAUNCH(grid, true, false, 3, true);
+      else
+        SA_NUM_LAUNCH(grid, false, false, 3, true);
+    } else if (atomic) {
+      if (expl)
+        SA_NUM_LAUNCH(grid, true, true, 0);
+      else if (fast)
+        SA_NUM_LAUNCH(grid, true, false, 3);
+      else
+        SA_NUM_LAUNCH(grid, true, false, 0);
+    } else {
+      if (expl)
+        SA_NUM_LAUNCH(grid, false, true, 0);
+      else if (fast)
+        SA_NUM_LAUNCH(grid, false, false, 3);
+      else
+        SA_NUM_LAUNCH(grid, false, false, 0);
+    }
+#undef SA_NUM_LAUNCH
+    rc = check_launch("num_features_kernel");
+    if (rc) return rc;
+  }
+  if (gc >= 0 && expl) rc = sa_vaep_goalscore(a, i64_out, gc, stream);  // explicit frames: own scan
+  return rc;
+}
 
 extern "C" int sa_vaep_features(const sa_actions* a, const sa_feature_plan* plan,
                                 const sa_block* bool_out, const sa_block* f64_out,
                                 const sa_block* i64_out, void* stream) {
-  return launch_features(a, plan, bool_out, f64_out, i64_out, 0, 0, nullptr, stream);
+  const FeatReq q{bool_out, f64_out, i64_out};
+  return launch_features(a, plan, q, stream);
 }
 
 extern "C" int sa_vaep_features_xt(const sa_actions* a, const sa_feature_plan* plan,
@@ -2127,33 +2194,31 @@ extern "C" int sa_vaep_features_xt(const sa_actions* a, const sa_feature_plan* p
   if (xt_l < 1 || xt_w < 1 || (int64_t)xt_l * xt_w > SA_XT_CELLS_MAX_C)
     return fail(SA_EINVAL, "xT cell codes need 1 <= l * w <= %d", SA_XT_CELLS_MAX_C);
   if (!xt_cells || !aligned16(xt_cells)) return fail(SA_EINVAL, "xt_cells must be 16-byte aligned");
-  return launch_features(a, plan, bool_out, f64_out, i64_out, xt_l, xt_w, xt_cells, stream);
+  const FeatReq q{bool_out, f64_out, i64_out, xt_l, xt_w, xt_cells};
+  return launch_features(a, plan, q, stream);
 }
 
 extern "C" int sa_vaep_features_bits(const sa_actions* a, const sa_feature_plan* plan, uint8_t* bool_bits,
                                      int64_t bits_stride, int32_t n_bool_cols, const sa_block* f64_out,
                                      const sa_block* i64_out, void* stream) {
   if (!a) return fail(SA_EINVAL, "null sa_actions");
-  if (!bool_bits || n_bool_cols < 1 || bits_stride < 2 * ((a->n + 15) / 16) || bits_stride % 2 ||
-      ((uintptr_t)bool_bits & 1u))
-    return fail(SA_EINVAL, "bool bitmaps: even stride of at least ceil(n/16)*2 bytes, 2-byte aligned");
+  if (int rc = check_bool_bits(a->n, bool_bits, bits_stride, n_bool_cols)) return rc;
   if (a->n_frames != 1) return fail(SA_EINVAL, "bool bitmaps: windowed mode only");
-  return launch_features(a, plan, nullptr, f64_out, i64_out, 0, 0, nullptr, stream, bool_bits, bits_stride,
-                         n_bool_cols);
+  const FeatReq q{nullptr, f64_out, i64_out, 0, 0, nullptr, bool_bits, bits_stride, n_bool_cols};
+  return launch_features(a, plan, q, stream);
 }
 
 extern "C" int sa_vaep_features_bits_f32(const sa_actions* a, const sa_feature_plan* plan, uint8_t* bool_bits,
                                          int64_t bits_stride, int32_t n_bool_cols, const sa_block* f32_out,
                                          const sa_block* i32f_out, void* stream) {
   if (!a) return fail(SA_EINVAL, "null sa_actions");
-  if (!bool_bits || n_bool_cols < 1 || bits_stride < 2 * ((a->n + 15) / 16) || bits_stride % 2 ||
-      ((uintptr_t)bool_bits & 1u))
-    return fail(SA_EINVAL, "bool bitmaps: even stride of at least ceil(n/16)*2 bytes, 2-byte aligned");
+  if (int rc = check_bool_bits(a->n, bool_bits, bits_stride, n_bool_cols)) return rc;
   if (a->n_frames != 1) return fail(SA_EINVAL, "bool bitmaps: windowed mode only");
   if (!plan || plan->nb_prev_actions > 3)
     return fail(SA_EINVAL, "float32 numeric blocks: nb_prev_actions <= 3 (use sa_vaep_features_bits)");
-  return launch_features(a, plan, nullptr, f32_out, i32f_out, 0, 0, nullptr, stream, bool_bits, bits_stride,
-                         n_bool_cols, nullptr, true);
+  FeatReq q{nullptr, f32_out, i32f_out, 0, 0, nullptr, bool_bits, bits_stride, n_bool_cols};
+  q.num32 = true;
+  return launch_features(a, plan, q, stream);
 }
 
 extern "C" int sa_vaep_features_conditions(const sa_actions* a, const sa_feature_plan* plan, uint8_t* bits,
@@ -2180,8 +2245,9 @@ extern "C" int sa_vaep_features_conditions(const sa_actions* a, const sa_feature
   c.cond_dl = cond_dl;
   c.cond_row0 = n_bool_cols;
   c.cond_n = n_cond;
-  return launch_features(a, plan, nullptr, &fz, &iz, 0, 0, nullptr, stream, bits, bits_stride, n_bool_cols, nullptr,
-                         false, &c);
+  FeatReq q{nullptr, &fz, &iz, 0, 0, nullptr, bits, bits_stride, n_bool_cols};
+  q.cond = &c;
+  return launch_features(a, plan, q, stream);
 }
 
 extern "C" int sa_vaep_step_f64(const sa_actions* a, const sa_feature_plan* plan, const sa_block* bool_out,
@@ -2194,33 +2260,29 @@ extern "C" int sa_vaep_step_f64(const sa_actions* a, const sa_feature_plan* plan
   if (rc) return rc;
   if (!plan) return fail(SA_EINVAL, "null plan");
   if (nr_actions < 1) return fail(SA_EINVAL, "nr_actions must be >= 1");
-  if (ld % 16 != 0 || ld < ((a->n + 15) / 16) * 16)
-    return fail(SA_EINVAL, "ld must be a multiple of 16 and >= round_up(n, 16)");
-  if (!aligned16(scores) || !aligned16(concedes) || !aligned16(goal_from_shot))
-    return fail(SA_EINVAL, "label outputs must be 16-byte aligned");
+  if ((rc = check_label_outputs(a->n, scores, concedes, goal_from_shot, ld))) return rc;
   const bool formula = p_scores || p_concedes || off || def || val;  // all NULL: labels only
-  if (formula && (!p_scores || !p_concedes || !off || !def || !val))
-    return fail(SA_EINVAL, "null probability/output pointer");
-  if (!aligned16(off) || !aligned16(def) || !aligned16(val))
-    return fail(SA_EINVAL, "formula outputs must be 16-byte aligned (length >= round_up(n, 16))");
+  if (formula && (rc = check_formula_args(p_scores, p_concedes, off, def, val, "round_up(n, 16)"))) return rc;
   if (xt_cells) {
     if (a->atomic) return fail(SA_EINVAL, "xT cells need SPADL actions");
     if (xt_l < 1 || xt_w < 1 || (int64_t)xt_l * xt_w > SA_XT_CELLS_MAX_C)
       return fail(SA_EINVAL, "xT cell codes need 1 <= l * w <= %d", SA_XT_CELLS_MAX_C);
     if (!aligned16(xt_cells)) return fail(SA_EINVAL, "xt_cells must be 16-byte aligned");
   }
+  FeatReq q{bool_out, f64_out, i64_out, xt_l, xt_w, xt_cells};
   // no fused form: the separate launches.  Atomic actions always take them: their numeric pass
   // (136 VGPRs, 3 waves per SIMD) loses more to the tail's registers than the tail's launch
   // costs (cfg3, 4.0e7 atomic actions: 3.89 ms separate vs 4.35 ms fused, scripts/atomic_ab.py,
   // profiles/r03_atomic_ab.json)
   if (a->atomic || plan->nb_prev_actions > 3 || nr_actions > SA_STEP_MAX_NR) {
-    if ((rc = launch_features(a, plan, bool_out, f64_out, i64_out, xt_l, xt_w, xt_cells, stream))) return rc;
+    if ((rc = launch_features(a, plan, q, stream))) return rc;
     if (!formula) return sa_vaep_labels(a, nr_actions, scores, concedes, goal_from_shot, ld, stream);
     return sa_vaep_labels_formula_f64(a, nr_actions, scores, concedes, goal_from_shot, ld, p_scores,
                                       p_concedes, off, def, val, stream);
   }
   const TailArgs t{nr_actions, scores, concedes, goal_from_shot, p_scores, p_concedes, off, def, val, 0, 0};
-  return launch_features(a, plan, bool_out, f64_out, i64_out, xt_l, xt_w, xt_cells, stream, nullptr, 0, 0, &t);
+  q.tail = &t;
+  return launch_features(a, plan, q, stream);
 }
 
 extern "C" int sa_vaep_step_f64_chunked(const sa_actions* a, const sa_feature_plan* plan, const sa_block* bool_out,
@@ -2252,190 +2314,9 @@ extern "C" int sa_vaep_step_f64_chunked(const sa_actions* a, const sa_feature_pl
     return fail(SA_EINVAL, "bad xT cell code arguments");
   const TailArgs t{nr_actions, scores, concedes, goal_from_shot, p_scores, p_concedes, off, def, val, chunk_rows,
                    prefetch};
-  return launch_features(a, plan, bool_out, f64_out, i64_out, xt_l, xt_w, xt_cells, stream, nullptr, 0, 0, &t);
-}
-
-static int launch_features(const sa_actions* a, const sa_feature_plan* plan, const sa_block* bool_out,
-                           const sa_block* f64_out, const sa_block* i64_out, int32_t xt_l,
-                           int32_t xt_w, uint32_t* xt_cells, void* stream, uint8_t* bits,
-                           int64_t bits_stride, int32_t n_bits, const TailArgs* tail, bool num32,
-                           const FeatArgs* cond) {
-  int rc = check_actions(a, true);
-  if (rc) return rc;
-  if (!plan) return fail(SA_EINVAL, "null plan");
-  const int K = plan->nb_prev_actions;
-  if (K < 1) return fail(SA_EINVAL, "nb_prev_actions must be >= 1");
-  if (a->n_frames > 1 && a->n_frames != K)
-    return fail(SA_EINVAL, "explicit mode needs n_frames == nb_prev_actions");
-  bool wb = false, wf = false, wi = false, wn = false;
-  for (int x = 0; x < SA_XFN_COUNT; ++x) {
-    wb |= plan->bool_col[x] >= 0;
-    wf |= plan->f64_col[x] >= 0;
-    wi |= plan->i64_col[x] >= 0;
-    wn |= plan->f64_col[x] >= 0 || (plan->i64_col[x] >= 0 && x != SA_XFN_GOALSCORE);
-  }
-  if (wb && !bits && (rc = check_block(bool_out, a->n, SA_BOOL_TILE_QUANTUM, "bool"))) return rc;
-  if (wf && (rc = check_block(f64_out, a->n, SA_NUM_TILE_QUANTUM, "f64"))) return rc;
-  if (wi && (rc = check_block(i64_out, a->n, SA_NUM_TILE_QUANTUM, "i64"))) return rc;
-  for (int x = 0; x < SA_XFN_COUNT; ++x) {
-    if ((wb && plan->bool_col[x] >= (bits ? n_bits : bool_out->n_cols)) || (wf && plan->f64_col[x] >= f64_out->n_cols) ||
-        (wi && plan->i64_col[x] >= i64_out->n_cols))
-      return fail(SA_EINVAL, "plan column offset beyond the block's column count");
-  }
-  if (a->atomic) {
-    const int spadl_only[] = {SA_XFN_RESULT, SA_XFN_RESULT_ONEHOT, SA_XFN_ACTIONTYPE_RESULT_ONEHOT,
-                              SA_XFN_STARTLOCATION, SA_XFN_ENDLOCATION, SA_XFN_STARTPOLAR,
-                              SA_XFN_ENDPOLAR, SA_XFN_MOVEMENT, SA_XFN_SPACE_DELTA};
-    for (int x : spadl_only)
-      if (plan->bool_col[x] >= 0 || plan->f64_col[x] >= 0 || plan->i64_col[x] >= 0)
-        return fail(SA_EINVAL, "transformer %d is not defined for atomic actions", x);
-  } else {
-    const int atomic_only[] = {SA_XFN_LOCATION, SA_XFN_POLAR, SA_XFN_MOVEMENT_POLAR, SA_XFN_DIRECTION};
-    for (int x : atomic_only)
-      if (plan->bool_col[x] >= 0 || plan->f64_col[x] >= 0 || plan->i64_col[x] >= 0)
-        return fail(SA_EINVAL, "transformer %d is only defined for atomic actions", x);
-  }
-  if (a->n == 0) return SA_OK;
-  hipStream_t st = (hipStream_t)stream;
-  FeatArgs args{*a,
-                *plan,
-                wb && !bits ? (uint8_t*)bool_out->data : nullptr,
-                wf ? (double*)f64_out->data : nullptr,
-                wi ? (int64_t*)i64_out->data : nullptr,
-                wb ? (bits ? (int64_t)n_bits : bool_out->n_cols) : 0,
-                wf ? f64_out->n_cols : 0,
-                wi ? i64_out->n_cols : 0,
-                wb && !bits ? bool_out->tile_rows : BOOL_TILE,
-                wf ? f64_out->tile_rows : 16,
-                wi ? i64_out->tile_rows : 16,
-                xt_cells,
-                xt_l,
-                xt_w,
-                (wb || cond) ? (uint16_t*)bits : nullptr,  // COND: the condition rows even with no bool column
-                bits_stride / 2,
-                tail ? tail->nr : 0,
-                tail ? tail->sc : nullptr,
-                tail ? tail->co : nullptr,
-                tail ? tail->gfs : nullptr,
-                tail ? tail->ps : nullptr,
-                tail ? tail->pc : nullptr,
-                tail ? tail->off : nullptr,
-                tail ? tail->def : nullptr,
-                tail ? tail->val : nullptr,
-                tail ? (aligned16(tail->ps) && aligned16(tail->pc)) : false,
-                cond ? cond->cond_fstart : nullptr,
-                cond ? cond->cond_istart : nullptr,
-                cond ? cond->cond_thr : nullptr,
-                cond ? cond->cond_dl : nullptr,
-                cond ? cond->cond_row0 : 0};
-  args.cond_n = cond ? cond->cond_n : 0;
-  const dim3 grid(xcd_grid((a->n + BLOCK_ACTS - 1) / BLOCK_ACTS)), block(BLOCK_WAVES * WAVE);
-  const bool expl = a->n_frames > 1;
-  if (wb) {  // one wave per (tile, group of ~32 columns), XCD-contiguous sweep order
-    const int ng = (int)((args.Cb + SA_CG_COLS - 1) / SA_CG_COLS);
-    const int gc = (int)((args.Cb + ng - 1) / ng);
-    const int64_t waves = (a->n + BOOL_TILE - 1) / BOOL_TILE * ng;
-    const dim3 cgrid(xcd_grid((waves + CG_WAVES - 1) / CG_WAVES)), cblock(WAVE * CG_WAVES);
-    const bool wide = !expl && K > BOOL_HALO + 1;  // windows past the register halo
-#if SA_FUSED_STEP
-    if (!bits && !wide && !expl && !a->atomic && tail && tail->chunk == 0 && !cond && !num32) {
-      const int64_t nb = cgrid.x, nn = (a->n + BLOCK_ACTS - 1) / BLOCK_ACTS;
-      hipLaunchKernelGGL(step_fused_kernel, dim3(xcd_grid(nb + nn)), cblock, 0, st, args, ng, gc, nb, nb + nn);
-      return check_launch("step_fused_kernel");
-    }
-#endif
-    if (bits) {  // the on-device VAEP.rate: SPADL or atomic, windowed, as bitmaps
-      if (wide) {
-        if (a->atomic)
-          hipLaunchKernelGGL((bool_colgroup_kernel<true, false, true, true>), cgrid, cblock, 0, st, args, ng, gc);
-        else
-          hipLaunchKernelGGL((bool_colgroup_kernel<false, false, true, true>), cgrid, cblock, 0, st, args, ng, gc);
-      } else if (a->atomic) {
-        hipLaunchKernelGGL((bool_colgroup_kernel<true, false, true>), cgrid, cblock, 0, st, args, ng, gc);
-      } else {
-        hipLaunchKernelGGL((bool_colgroup_kernel<false, false, true>), cgrid, cblock, 0, st, args, ng, gc);
-      }
-    } else if (a->atomic) {
-      if (expl)
-        hipLaunchKernelGGL((bool_colgroup_kernel<true, true, false>), cgrid, cblock, 0, st, args, ng, gc);
-      else if (wide)
-        hipLaunchKernelGGL((bool_colgroup_kernel<true, false, false, true>), cgrid, cblock, 0, st, args, ng, gc);
-      else
-        hipLaunchKernelGGL((bool_colgroup_kernel<true, false, false>), cgrid, cblock, 0, st, args, ng, gc);
-    } else {
-      if (expl)
-        hipLaunchKernelGGL((bool_colgroup_kernel<false, true, false>), cgrid, cblock, 0, st, args, ng, gc);
-      else if (wide)
-        hipLaunchKernelGGL((bool_colgroup_kernel<false, false, false, true>), cgrid, cblock, 0, st, args, ng, gc);
-      else
-        hipLaunchKernelGGL((bool_colgroup_kernel<false, false, false>), cgrid, cblock, 0, st, args, ng, gc);
-    }
-    rc = check_launch("bool_colgroup_kernel");
-    if (rc) return rc;
-  }
-  const int gc = plan->i64_col[SA_XFN_GOALSCORE];
-  if (wn || xt_cells || tail || (gc >= 0 && !expl)) {  // windowed mode: goalscore fused into this pass
-    const bool fast = !expl && K <= 3;  // register-resident windows (KF = 3)
-    if (cond && SA_COND_LDS && cond_lds_bytes(args.Cf, args.Ci, args.cond_n) <= COND_LDS_MAX) {
-      const size_t lds = (size_t)cond_lds_bytes(args.Cf, args.Ci, args.cond_n);
-      if (a->atomic)
-        hipLaunchKernelGGL(num_cond_lds_kernel<true>, grid, block, lds, st, args);
-      else
-        hipLaunchKernelGGL(num_cond_lds_kernel<false>, grid, block, lds, st, args);
-    } else if (cond) {  // windowed, K <= 3 (checked by sa_vaep_features_conditions)
-      if (a->atomic)
-        hipLaunchKernelGGL((num_features_kernel<true, false, 3, false, false, true>), grid, block, 0, st, args);
-      else
-        hipLaunchKernelGGL((num_features_kernel<false, false, 3, false, false, true>), grid, block, 0, st, args);
-    } else if (num32) {  // windowed, K <= 3 (checked by sa_vaep_features_bits_f32)
-      if (a->atomic)
-        hipLaunchKernelGGL((num_features_kernel<true, false, 3, false, true>), grid, block, 0, st, args);
-      else
-        hipLaunchKernelGGL((num_features_kernel<false, false, 3, false, true>), grid, block, 0, st, args);
-    } else if (tail && tail->chunk > 0 && !a->atomic) {  // sa_vaep_step_f64_chunked (probe)
-      for (int64_t c0 = 0; c0 < a->n; c0 += tail->chunk) {
-        const int64_t c1 = c0 + tail->chunk < a->n ? c0 + tail->chunk : a->n;
-        if (tail->prefetch) {
-          const int64_t th = (c1 - c0 + 3) / 4;
-          hipLaunchKernelGGL(prefetch_rows_kernel, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, st, *a,
-                             tail->ps, tail->pc, c0, c1, xt_cells);
-        }
-        args.row0 = c0;
-        args.row_end = c1;
-        const dim3 cg(xcd_grid((c1 - c0 + BLOCK_ACTS - 1) / BLOCK_ACTS));
-        hipLaunchKernelGGL((num_features_kernel<false, false, 3, true>), cg, block, 0, st, args);
-      }
-    } else if (tail) {  // windowed, K <= 3 (checked by sa_vaep_step_f64)
-#if SA_NUM_STAGE > 0
-      if (!a->atomic && (!tail->ps || (aligned16(tail->ps) && aligned16(tail->pc)))) {
-        const dim3 sg(xcd_grid((a->n + STG_T * BLOCK_ACTS - 1) / (STG_T * BLOCK_ACTS)));
-        hipLaunchKernelGGL(num_staged_kernel, sg, block, sizeof(double) * 7 * STG_ROWS, st, args);
-      } else
-#endif
-      if (a->atomic)
-        hipLaunchKernelGGL((num_features_kernel<true, false, 3, true>), grid, block, 0, st, args);
-      else
-        hipLaunchKernelGGL((num_features_kernel<false, false, 3, true>), grid, block, 0, st, args);
-    } else if (a->atomic) {
-      if (expl)
-        hipLaunchKernelGGL((num_features_kernel<true, true, 0>), grid, block, 0, st, args);
-      else if (fast)
-        hipLaunchKernelGGL((num_features_kernel<true, false, 3>), grid, block, 0, st, args);
-      else
-        hipLaunchKernelGGL((num_features_kernel<true, false, 0>), grid, block, 0, st, args);
-    } else {
-      if (expl)
-        hipLaunchKernelGGL((num_features_kernel<false, true, 0>), grid, block, 0, st, args);
-      else if (fast)
-        hipLaunchKernelGGL((num_features_kernel<false, false, 3>), grid, block, 0, st, args);
-      else
-        hipLaunchKernelGGL((num_features_kernel<false, false, 0>), grid, block, 0, st, args);
-    }
-    rc = check_launch("num_features_kernel");
-    if (rc) return rc;
-  }
-  if (gc >= 0 && expl) rc = sa_vaep_goalscore(a, i64_out, gc, stream);  // explicit frames: own scan
-  return rc;
+  FeatReq q{bool_out, f64_out, i64_out, xt_l, xt_w, xt_cells};
+  q.tail = &t;
+  return launch_features(a, plan, q, stream);
 }
 
 extern "C" int sa_vaep_goalscore(const sa_actions* a, const sa_block* i64_out, int32_t col,
@@ -2462,10 +2343,7 @@ extern "C" int sa_vaep_labels(const sa_actions* a, int32_t nr_actions, uint8_t* 
   int rc = check_actions(a, false);
   if (rc) return rc;
   if (nr_actions < 1) return fail(SA_EINVAL, "nr_actions must be >= 1");
-  if (ld % 16 != 0 || ld < ((a->n + 15) / 16) * 16)
-    return fail(SA_EINVAL, "ld must be a multiple of 16 and >= round_up(n, 16)");
-  if (!aligned16(scores) || !aligned16(concedes) || !aligned16(goal_from_shot))
-    return fail(SA_EINVAL, "label outputs must be 16-byte aligned");
+  if ((rc = check_label_outputs(a->n, scores, concedes, goal_from_shot, ld))) return rc;
   if (a->n == 0) return SA_OK;
   const int64_t lanes = (a->n + LANE_ACTS - 1) / LANE_ACTS;
   const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
@@ -2484,9 +2362,7 @@ static int launch_formula(const sa_actions* a, const T* ps, const T* pc, T* off,
                           void* stream) {
   int rc = check_actions(a, false);
   if (rc) return rc;
-  if (!ps || !pc || !off || !def || !val) return fail(SA_EINVAL, "null probability/output pointer");
-  if (!aligned16(off) || !aligned16(def) || !aligned16(val))
-    return fail(SA_EINVAL, "formula outputs must be 16-byte aligned (length >= round_up(n, 4))");
+  if ((rc = check_formula_args(ps, pc, off, def, val, "round_up(n, 4)"))) return rc;
   if (a->n == 0) return SA_OK;
   constexpr int V = 16 / sizeof(T);
   const int64_t lanes = (a->n + V - 1) / V;
@@ -2518,13 +2394,8 @@ static int launch_labels_formula(const sa_actions* a, int32_t nr_actions, uint8_
   int rc = check_actions(a, false);
   if (rc) return rc;
   if (nr_actions < 1) return fail(SA_EINVAL, "nr_actions must be >= 1");
-  if (ld % 16 != 0 || ld < ((a->n + 15) / 16) * 16)
-    return fail(SA_EINVAL, "ld must be a multiple of 16 and >= round_up(n, 16)");
-  if (!aligned16(scores) || !aligned16(concedes) || !aligned16(goal_from_shot))
-    return fail(SA_EINVAL, "label outputs must be 16-byte aligned");
-  if (!ps || !pc || !off || !def || !val) return fail(SA_EINVAL, "null probability/output pointer");
-  if (!aligned16(off) || !aligned16(def) || !aligned16(val))
-    return fail(SA_EINVAL, "formula outputs must be 16-byte aligned (length >= round_up(n, 16))");
+  if ((rc = check_label_outputs(a->n, scores, concedes, goal_from_shot, ld))) return rc;
+  if ((rc = check_formula_args(ps, pc, off, def, val, "round_up(n, 16)"))) return rc;
   if (a->n == 0) return SA_OK;
   const int64_t waves = (a->n + WAVE * LANE_ACTS - 1) / (WAVE * LANE_ACTS);
   const dim3 grid((unsigned)((waves + 3) / 4)), block(256);

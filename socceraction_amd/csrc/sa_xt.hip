@@ -20,15 +20,6 @@
 #ifndef SA_XC_UC
 #define SA_XC_UC 8  // count pass from cell codes: codes per thread per pass, all loaded first
 #endif
-#ifndef SA_XT_BANDS
-#define SA_XT_BANDS 1  // grids the band-owned count holds (sa_xt_large.hip); 0: XC_VEC / XC_GLOBAL atomics
-#endif
-#ifndef SA_XT_COMPACT
-#define SA_XT_COMPACT 1  // large-grid solve over the compact count rows (0: xt_iter_kernel on the dense rows)
-#endif
-#ifndef SA_XT_WIDE
-#define SA_XT_WIDE 1  // C <= 197: XC_WIDE count pass (0: the 32k-action XC_SMALL workgroups)
-#endif
 
 namespace sa {
 
@@ -1011,7 +1002,7 @@ static int launch_count(const sa_actions& A, const uint32_t* cells, int64_t n, i
       hipLaunchKernelGGL((xt_count_kernel<MODE, false>), GRID, BLOCK, LDS, st, A, nullptr, n, l, w, us,   \
                          ug, um, trans, err_flags, (int64_t)(CHUNK), codes);                            \
   } while (0)
-  if (SA_XT_WIDE && wide_lds <= 150 * 1024 && !shared) {
+  if (wide_lds <= 150 * 1024 && !shared) {
     // one workgroup per CU (or fewer when there are few actions: >= 4096 actions each)
     const int cus = device_cus(current_device());
     int64_t blocks = (n + 4095) / 4096;
@@ -1020,7 +1011,7 @@ static int launch_count(const sa_actions& A, const uint32_t* cells, int64_t n, i
     SA_COUNT_LAUNCH(XC_WIDE, dim3((unsigned)blocks), dim3(XT_WIDE_THREADS), wide_lds, chunk);
   } else if (small_lds <= 80 * 1024) {
     SA_COUNT_LAUNCH(XC_SMALL, dim3(wg_blocks), dim3(XT_THREADS), small_lds, XT_SMALL_ACTS);
-  } else if (SA_XT_BANDS && xt_band_ok(C) && n <= INT32_MAX) {
+  } else if (xt_band_ok(C) && n <= INT32_MAX) {
     // band-owned count (sa_xt_large.hip): no global atomics into the C x C table
     return xt_count_bands(A, cells, n, l, w, shot, goal, move, trans, err_flags, codes, st);
   } else if (vec_lds <= 120 * 1024) {
@@ -1146,7 +1137,7 @@ static int solve_ex(const int64_t* shot, const int64_t* goal, const int64_t* mov
     return fail(SA_EINVAL, "null pointer");
   if (flags & ~SA_XT_SOLVE_EXACT) return fail(SA_EINVAL, "unknown flags");
   if (!ell_in != !row_len_in) return fail(SA_EINVAL, "ell and row_len come together");
-  if (ell_in && (C <= XT_SOLVE_MAX_C || !SA_XT_COMPACT || !xt_compact_ok(C) || !aligned16(ell_in)))
+  if (ell_in && (C <= XT_SOLVE_MAX_C || !xt_compact_ok(C) || !aligned16(ell_in)))
     return fail(SA_EINVAL, "a prebuilt compact form is for %d < C <= the compact limit (16-byte aligned)",
                 XT_SOLVE_MAX_C);
   if (path) *path = SA_XT_PATH_SEQUENTIAL;
@@ -1184,7 +1175,7 @@ static int solve_ex(const int64_t* shot, const int64_t* goal, const int64_t* mov
     if (!rc) rc = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
   } else if (!rc) {
     // the compact form of the count rows, built once (sa_xt_large.hip): [ell | row_len]
-    const bool compact = SA_XT_COMPACT && xt_compact_ok(C);
+    const bool compact = xt_compact_ok(C);
     rc = check_hip(hipMemsetAsync(heatmaps, 0, sizeof(double) * C, st), "memset");
     if (!rc && !compact)  // the dense loop's flags (the compact solve keeps its own)
       rc = check_hip(hipMemsetAsync(dflags, 0, sizeof(int32_t) * (max_iter + 1), st), "memset");

@@ -29,7 +29,6 @@
 //    int32 rows.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -39,9 +38,6 @@
 namespace sa {
 
 // ============================================================================ band-owned count
-#ifndef SA_XK_PROBE
-#define SA_XK_PROBE 0  // diagnostic builds (wrong counts): 1 = no band histogram, 2 = no key stores
-#endif
 #ifndef SA_XK_THREADS
 #define SA_XK_THREADS 1024  // K1 workgroup (118 VGPRs with the rate operands: one per CU, 16 waves; 512: the same, r04ae)
 #endif
@@ -50,12 +46,6 @@ constexpr int XK_THREADS = SA_XK_THREADS;
 #define SA_XK_U 2  // K1 actions per thread per pass (coordinates; even; 4: 146.5 vs 143.4 us per 16M, r06k2)
 #endif
 static_assert(SA_XK_U >= 2 && SA_XK_U % 2 == 0 && SA_XK_U <= 16, "SA_XK_U");
-#ifndef SA_XK_PIPE
-#define SA_XK_PIPE 0  // 1: K1's coordinate passes software-pipelined (the next pass's loads issued
-#endif                //    before this pass's arithmetic; two register buffers, alternating)
-#ifndef SA_XK_BALANCE
-#define SA_XK_BALANCE 1  // K1 regions per batch rounded up to whole rounds of the CUs (shorter regions)
-#endif
 #ifndef SA_XK_NT
 #define SA_XK_NT 3  // bit 0: non-temporal coordinate / id loads in K1, bit 1: non-temporal operand stores
                     // (read once per fit; cfg5 batch 0.263 -> 0.251 ms, profiles/r04_xt_count_ab.md)
@@ -71,13 +61,8 @@ __device__ __forceinline__ void xk_st(T* p, T v) {
   else *p = v;
 }
 constexpr int XK_CHUNK = 32768;     // actions per K1 workgroup = key capacity of its region
-constexpr int XS_THREADS = 1024;    // K3 workgroup
-#ifndef SA_XS_SPLIT
-#define SA_XS_SPLIT 1  // K3 workgroups per K1 region (2 / 4 parts: two per CU, slower; r04_xt_count_ab.md)
-#endif
-constexpr int XS_SPLIT = SA_XS_SPLIT;
-constexpr int XS_PART = XK_CHUNK / XS_SPLIT;  // keys per K3 workgroup
-constexpr int XS_PER = XS_PART / XS_THREADS;
+constexpr int XS_THREADS = 1024;    // K3 workgroup: one per K1 region
+constexpr int XS_PER = XK_CHUNK / XS_THREADS;  // keys per K3 thread
 constexpr int XB_THREADS = 1024;    // K4 workgroup
 #ifndef SA_XB_RMAX
 #define SA_XB_RMAX 8  // start cells per band at most (105 x 68: 5 = the most 160 KB of LDS holds)
@@ -101,8 +86,8 @@ constexpr uint32_t XB_NONE = 0xFFFFFFFFu;
 typedef uint16_t xb_key_t;
 static_assert((XB_LDS_MAX - XB_LDS_STATIC) / 4 < 0xFFFFu, "a band's bins fit 16-bit bucket keys");
 constexpr uint32_t XE_CNT_ESC_K4 = 0xFFFFu;  // = XE_CNT_ESC: a count >= 65535 is read from the dense row
-static_assert(XS_PER * XS_THREADS * XS_SPLIT == XK_CHUNK && XS_PER >= 1, "K3 holds one part of a K1 region");
-static_assert(XS_PART * 4 + 2 * XB_NB_MAX * 4 + 256 <= XB_LDS_MAX, "K3 LDS");
+static_assert(XS_PER * XS_THREADS == XK_CHUNK && XS_PER >= 1, "K3 holds a K1 region");
+static_assert(XK_CHUNK * 4 + 2 * XB_NB_MAX * 4 + 256 <= XB_LDS_MAX, "K3 LDS");
 
 struct XbShape {
   int C;           // cells
@@ -213,104 +198,13 @@ __global__ __launch_bounds__(XK_THREADS) void xt_keys_kernel(sa_actions A, const
       if (has[u]) {
         const uint32_t pos = wbase + lane_rank(m[u]);
         SA_DGUARD(pos < XK_CHUNK, pos, continue);
-        if (!(SA_XK_PROBE & 2)) out[pos] = key[u];
-        if (!(SA_XK_PROBE & 1)) atomicAdd(&bh[band_of(key[u], S.magic)], 1u);
+        out[pos] = key[u];
+        atomicAdd(&bh[band_of(key[u], S.magic)], 1u);
       }
       wbase += (uint32_t)__popcll(m[u]);
     }
   };
-  if constexpr (!CELLS && SA_XK_PIPE) {
-    if (vec) {  // wave-uniform
-      constexpr int Q = U / 2;  // pairs per thread per pass
-      struct Raw {
-        f64x2 a[Q], b[Q], c[Q], d[Q];
-        uint32_t ty[Q], rs[Q];
-      };
-      auto load = [&](Raw& R, int64_t base) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-          const int64_t j = base + 2 * ((int64_t)q * XK_THREADS + threadIdx.x);
-          const int64_t jc = j + 1 < end ? j : ((end - 2) & ~(int64_t)1);  // a whole aligned pair
-          R.a[q] = xk_ld(reinterpret_cast<const f64x2*>(F.c0 + jc));
-          R.b[q] = xk_ld(reinterpret_cast<const f64x2*>(F.c1 + jc));
-          R.c[q] = xk_ld(reinterpret_cast<const f64x2*>(F.c2 + jc));
-          R.d[q] = xk_ld(reinterpret_cast<const f64x2*>(F.c3 + jc));
-          R.ty[q] = xk_ld(reinterpret_cast<const uint16_t*>(F.type_id + jc));
-          R.rs[q] = xk_ld(reinterpret_cast<const uint16_t*>(F.result_id + jc));
-        }
-      };
-      auto pass = [&](const Raw& R, int64_t base) {
-        int tt[U], rr[U];
-        double sx[U], sy[U], ex[U], ey[U];
-        int64_t jj[U];
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-          const int64_t j = base + 2 * ((int64_t)q * XK_THREADS + threadIdx.x);
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const int u = 2 * q + e;
-            jj[u] = j + e;
-            sx[u] = R.a[q][e];
-            sy[u] = R.b[q][e];
-            ex[u] = R.c[q][e];
-            ey[u] = R.d[q][e];
-            tt[u] = (int)((R.ty[q] >> (8 * e)) & 0xFF);
-            rr[u] = (int)((R.rs[q] >> (8 * e)) & 0xFF);
-          }
-          if (j + 1 >= end) {  // the batch's odd last action (or none): scalar, the rest not counted
-            const int64_t k = j < end ? j : end - 1;
-            sx[2 * q] = F.c0[k];
-            sy[2 * q] = F.c1[k];
-            ex[2 * q] = F.c2[k];
-            ey[2 * q] = F.c3[k];
-            tt[2 * q] = j < end ? (int)F.type_id[k] : -1;
-            rr[2 * q] = F.result_id[k];
-            tt[2 * q + 1] = -1;
-          }
-        }
-        BinQ bq[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) bq[u] = bin_q(sx[u], sy[u], ex[u], ey[u]);
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-          const int u = 2 * q;
-          const int64_t j = jj[u];
-          if (RO.codes && tt[u] >= 0) {
-            const uint32_t c0 = rate_code_q(tt[u], rr[u], sx[u], sy[u], ex[u], ey[u], bq[u], l, w);
-            if (tt[u + 1] >= 0)
-              *reinterpret_cast<uint2*>(RO.codes + j) = make_uint2(
-                  c0, rate_code_q(tt[u + 1], rr[u + 1], sx[u + 1], sy[u + 1], ex[u + 1], ey[u + 1], bq[u + 1], l, w));
-            else
-              RO.codes[j] = c0;
-          }
-          if (RO.icodes && tt[u] >= 0) {
-            const uint64_t c0 = rate_icode_q(tt[u], rr[u], sx[u], sy[u], ex[u], ey[u], bq[u], RO.L, RO.W);
-            if (tt[u + 1] >= 0)
-              xk_st(reinterpret_cast<u64x2*>(RO.icodes + j),
-                    u64x2{c0, rate_icode_q(tt[u + 1], rr[u + 1], sx[u + 1], sy[u + 1], ex[u + 1], ey[u + 1], bq[u + 1],
-                                           RO.L, RO.W)});
-            else
-              RO.icodes[j] = c0;
-          }
-        }
-        XtAct act[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) act[u] = act_from_row_q(tt[u], rr[u], sx[u], sy[u], ex[u], ey[u], bq[u], l, w);
-        emit_keys(act);
-      };
-      const int64_t step = (int64_t)U * XK_THREADS;
-      Raw ra, rb;  // alternate: no register copy of a load in flight
-      load(ra, begin);
-      for (int64_t base = begin; base < end; base += 2 * step) {  // wave-uniform bounds
-        if (base + step < end) load(rb, base + step);
-        pass(ra, base);
-        if (base + step >= end) break;
-        if (base + 2 * step < end) load(ra, base + 2 * step);
-        pass(rb, base + step);
-      }
-    }
-  }
-  for (int64_t base = begin; base < end && !(!CELLS && SA_XK_PIPE && vec); base += (int64_t)U * XK_THREADS) {
+  for (int64_t base = begin; base < end; base += (int64_t)U * XK_THREADS) {
     XtAct act[U];
     if (CELLS) {
       uint32_t cv[U];
@@ -464,7 +358,7 @@ __device__ uint32_t block_scan(uint32_t* a, int n, uint32_t* ws) {
 __device__ uint32_t block_scan_1024(uint32_t* a, int n, uint32_t* ws) { return block_scan<1024>(a, n, ws); }
 
 
-// K3: XS_SPLIT workgroups per K1 region, one per part of its keys (<= XS_PART, XS_PER per thread in registers), ranked
+// K3: one workgroup per K1 region: its keys (<= XK_CHUNK, XS_PER per thread in registers) are ranked
 // within their band by LDS atomics, each band's run gets its place in the band's bucket by ONE
 // global atomic on the band cursor, the keys are sorted by band in LDS, and thread i writes the
 // sorted key i -- consecutive threads of a run write consecutive words.
@@ -477,7 +371,7 @@ __global__ __launch_bounds__(XS_THREADS) void xt_keys_scatter_kernel(const uint3
   extern __shared__ uint32_t sm[];
   uint32_t* bh = sm;              // [NB] keys per band, then the local run offsets
   uint32_t* bb = sm + S.NB;       // [NB] the bands' offsets, then the runs' places in the buckets
-  uint32_t* sorted = sm + 2 * S.NB;  // [XS_PART]
+  uint32_t* sorted = sm + 2 * S.NB;  // [XK_CHUNK]
   __shared__ uint32_t ws[17];
   // the band offsets: every workgroup scans K1's band counts itself (5.7 KB at cfg5, from L2)
   // instead of waiting for a one-workgroup scan launch; the first writes them out for K4
@@ -488,10 +382,9 @@ __global__ __launch_bounds__(XS_THREADS) void xt_keys_scatter_kernel(const uint3
     for (int b = threadIdx.x; b < S.NB; b += XS_THREADS) band_off[b] = bb[b];
     if (threadIdx.x == 0) band_off[S.NB] = total;
   }
-  const int region = blockIdx.x / XS_SPLIT, part = blockIdx.x % XS_SPLIT;
-  const uint32_t rc = region_cnt[region], p0 = (uint32_t)part * XS_PART;
-  const uint32_t cnt = rc > p0 ? min(rc - p0, (uint32_t)XS_PART) : 0u;
-  const uint32_t* in = keys + (int64_t)region * XK_CHUNK + p0;
+  const int region = blockIdx.x;
+  const uint32_t cnt = min(region_cnt[region], (uint32_t)XK_CHUNK);
+  const uint32_t* in = keys + (int64_t)region * XK_CHUNK;
   for (int b = threadIdx.x; b < S.NB; b += XS_THREADS) bh[b] = 0;
   uint32_t k[XS_PER], rk[XS_PER];
 #pragma unroll
@@ -782,35 +675,19 @@ constexpr int XE_KC = 128;                   // entries per row per chunk
 constexpr int XE_PAIRS = XE_RPW / 2;         // row pairs per product wave (a 16-B load per pair)
 constexpr int XE_PITCH = XE_KC + 2;          // prod row pitch (doubles): 16-B aligned rows whose
                                              // 16-B chain reads hit every bank once per 16 lanes
-constexpr int XE_CT_MAX = 256;               // counts whose quotient is tabulated: CT = the largest
-                                             // power of two <= 256 whose table fits next to x
 #ifndef SA_XE_DEPTH
 #define SA_XE_DEPTH 4                        // chunks of entries in flight per product lane
 #endif
-#ifndef SA_XE_NTL
-#define SA_XE_NTL 0                          // 1: non-temporal entry loads
-#endif
 constexpr int XE_DEPTH = SA_XE_DEPTH;
-#ifndef SA_XE_QDIV
-#define SA_XE_QDIV 1                         // 1: quotients cnt / move by a corrected product with
-#endif                                       //    the row's reciprocal; 0: per-row LDS table
 constexpr int XE_THREADS = (XE_P + 1) * 64;  // + the chain wave
 constexpr int XE_XMAX = 9472;                // x (C doubles) staged in LDS
 constexpr int XE_BUILD_ROWS = 16;            // build: rows per workgroup (one wave each)
 constexpr uint32_t XE_CNT_ESC = 0xFFFFu;     // count >= 65535: read from the dense row
-#ifndef SA_XE_PROBE
-#define SA_XE_PROBE 0  // diagnostic builds (wrong values): 1 = no products,
-#endif                 // 4 = idle product waves (no loads, no LDS writes; the chain then reads LDS
-                       // nobody wrote and may be folded away: no chain timing), 8 = no division path,
-                       // 16 = workgroup 0's phase times (wall clock ticks) in x_next[0..3],
-                       // 32 = its work / barrier clocks per wave in x_next[40..43], 64 = product
-                       // waves without LDS traffic (x = the column, no product stores)
 static_assert(XE_KC == 128 && XE_PAIRS * 2 * XE_P == XE_S, "xt_iter_ell_kernel shape: 32 lanes x 4 entries per row chunk");
 static_assert(XE_THREADS <= 1024 && XE_S <= 64, "xt_iter_ell_kernel shape");
 constexpr size_t XE_LDS_STATIC = (size_t)XE_S * (2 * XE_PITCH + 2) * 8 + XE_S * 4;
 constexpr size_t XE_LDS_MAX = 160 * 1024;
-static_assert((size_t)XE_XMAX * 8 + (size_t)XE_S * 16 * 8 + XE_LDS_STATIC <= XE_LDS_MAX,
-              "xt_iter_ell_kernel LDS: x and a 16-count quotient table");
+static_assert((size_t)XE_XMAX * 8 + XE_LDS_STATIC <= XE_LDS_MAX, "xt_iter_ell_kernel LDS: x");
 static_assert(XE_DEPTH >= 1 && XE_DEPTH <= 8, "SA_XE_DEPTH");
 
 // A compact row's pitch in entries: C rounded up to whole chunks (room for a dense row).
@@ -856,13 +733,14 @@ __global__ __launch_bounds__(XE_BUILD_ROWS * 64) void xt_ell_build_kernel(const 
 // operations (sa_xt.hip), without its per-chunk compaction of the dense rows.  One workgroup per
 // slice of 32 rows.  Per chunk of KC entries per row, each product wave loads its 4 rows'
 // entries (256 contiguous bytes per load; DEPTH - 1 chunks ahead), forms the products -- the
-// quotient cnt / move[row] (QDIV: y = cnt * r, r = 1 / move[row] rounded; then
+// quotient cnt / move[row] (y = cnt * r, r = 1 / move[row] rounded; then
 // y + r * (cnt - y * move) by two fmas, Markstein's correction: the correctly rounded quotient, the
 // division's own bits -- scripts/check_quotient.c checks it exhaustively for cnt < 65536 against
 // 6000 + 6001 divisors and on 4e8 random pairs up to 2^53; no LDS read, no table), times x at
 // the column -- and writes them to prod[row][k]; the chain wave (lane = row) then adds its row's products strictly in order.  One barrier per
 // chunk, two buffers; a row shorter than the slice's longest costs nothing past its end (its
-// product lanes and its chain lane skip those chunks).
+// product lanes and its chain lane skip those chunks).  ct is unused (always 0): it sized a
+// rejected quotient table and stays so that the kernel's argument list is what it was.
 __global__ __launch_bounds__(XE_THREADS) void xt_iter_ell_kernel(const uint32_t* __restrict__ ell,
                                                                  const int32_t* __restrict__ row_len,
                                                                  const int32_t* __restrict__ cnt_rows,
@@ -874,11 +752,7 @@ __global__ __launch_bounds__(XE_THREADS) void xt_iter_ell_kernel(const uint32_t*
                                                                  double* __restrict__ xo, const int32_t* flag_prev,
                                                                  int32_t* __restrict__ flag_out) {
   if (flag_prev && __hip_atomic_load(flag_prev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
-#if SA_XE_PROBE & 16
-  const long long t_entry = wall_clock64();
-#endif
-  extern __shared__ __attribute__((aligned(16))) double xs[];  // [C] x, then tq [S][ct]
-  [[maybe_unused]] double* tq = xs + C;                        // tq[i * ct + q] = q / move[row i]
+  extern __shared__ __attribute__((aligned(16))) double xs[];  // [C] x
   __shared__ double prod[2][XE_S * XE_PITCH];
   __shared__ double mvs[XE_S], rcp[XE_S];
   __shared__ int lens[XE_S];
@@ -902,28 +776,13 @@ __global__ __launch_bounds__(XE_THREADS) void xt_iter_ell_kernel(const uint32_t*
     lens[t] = len0;
   }
   __syncthreads();
-#if !SA_XE_QDIV
-  const int lct = __builtin_ctz(ct);  // ct: a power of two
-  for (int e = t; e < XE_S * ct; e += XE_THREADS) {
-    const int q = e & (ct - 1);
-    tq[e] = q == 0 ? 0.0 : (double)q / mvs[e >> lct];  // a count of 0 is a zero term (T = 0)
-  }
-  __syncthreads();
-#endif
   int len = 0;
 #pragma unroll
   for (int i = 0; i < XE_S; ++i) len = max(len, lens[i]);
-#if SA_XE_PROBE & 16
-  const long long t_setup = wall_clock64();
-#endif
   const int nch = (len + XE_KC - 1) / XE_KC;
   const int nchp = (nch + XE_DEPTH - 1) / XE_DEPTH * XE_DEPTH;  // chunks past nch: +0 terms
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (wv < XE_P) {  // ---- product waves
-#if SA_XE_PROBE & 4
-    for (int j = 0; j < nchp; ++j) __syncthreads();
-    return;
-#endif
     // wave wv owns rows wv + 8 q (q < 4) as two pairs: half = lane / 32 takes row
     // wv + 8 (2 p + half) of pair p, lane l = lane % 32 its entries l + 32 u (u < 4) of each
     // chunk (one 16-B load of slots 4 l..4 l + 3: a wave instruction fetches 1 KiB, two rows'
@@ -956,18 +815,14 @@ __global__ __launch_bounds__(XE_THREADS) void xt_iter_ell_kernel(const uint32_t*
 #pragma unroll
       for (int p = 0; p < XE_PAIRS; ++p) {
         const int k = min(j, jmax[p]) * XE_KC + 4 * l32;
-#if SA_XE_NTL
-        d[p] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(Er[p] + k));
-#else  // default policy: the compact rows (~70 MB at cfg5) stay in the Infinity Cache across iterations
+        // default cache policy: the compact rows (~70 MB at cfg5) stay in the Infinity Cache across iterations
         d[p] = *reinterpret_cast<const u32x4*>(Er[p] + k);
-#endif
       }
     };
     auto products = [&](const u32x4 (&E)[XE_PAIRS], int j) {
       double* pr = prod[j & 1];
-      // every LDS read of the chunk first (x at the column; without QDIV the quotient from the
-      // table at min(cnt, ct - 1); entries past a row's end are 0: T = 0, x[0]), then the rare
-      // escaped counts (without QDIV: counts >= ct), then the products: no branch between a read
+      // every LDS read of the chunk first (x at the column; entries past a row's end are 0:
+      // T = 0, x[0]), then the rare escaped counts, then the products: no branch between a read
       // and its use, so the reads overlap
       double tv[XE_PAIRS][4], xv[XE_PAIRS][4];
       uint32_t en[XE_PAIRS][4];
@@ -982,27 +837,18 @@ __global__ __launch_bounds__(XE_THREADS) void xt_iter_ell_kernel(const uint32_t*
           en[p][u] = j * XE_KC + 32 * u + l32 < lr[p] ? E[p][u] : 0u;
           const uint32_t cnt = en[p][u] >> 16, col = en[p][u] & 0xFFFFu;
           SA_DCHECK((int)col < C, col);
-#if SA_XE_PROBE & 64
-          xv[p][u] = (double)col;
-#else
           xv[p][u] = xs[col < (uint32_t)C ? col : 0u];
-#endif
-#if SA_XE_QDIV
           const double q = (double)cnt, y = q * rq[p];  // a count of 0 is a zero term (T = 0)
           tv[p][u] = __builtin_fma(__builtin_fma(-y, mq[p], q), rq[p], y);
           big |= cnt == XE_CNT_ESC;
-#else
-          tv[p][u] = tq[ir[p] * ct + min(cnt, (uint32_t)ct - 1u)];
-          big |= cnt >= (uint32_t)ct;
-#endif
         }
-      if (__builtin_expect(__ballot(big) != 0, 0) && !(SA_XE_PROBE & 8)) {
+      if (__builtin_expect(__ballot(big) != 0, 0)) {
 #pragma unroll
         for (int p = 0; p < XE_PAIRS; ++p)
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             const uint32_t cnt = en[p][u] >> 16, col = en[p][u] & 0xFFFFu;
-            if (live[p] && cnt >= (uint32_t)(SA_XE_QDIV ? XE_CNT_ESC : ct)) {
+            if (live[p] && cnt >= XE_CNT_ESC) {
               const int32_t c32 = cnt == XE_CNT_ESC ? cnt_rows[(int64_t)(row0 + ir[p]) * C + col] : (int32_t)cnt;
               tv[p][u] = (double)c32 / mq[p];
             }
@@ -1014,47 +860,21 @@ __global__ __launch_bounds__(XE_THREADS) void xt_iter_ell_kernel(const uint32_t*
         double* dst = pr + ir[p] * XE_PITCH + l32;
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-#if SA_XE_PROBE & 64
-          if (tv[p][u] * xv[p][u] == -1.0) dst[32 * u] = 0.0;
-#elif SA_XE_PROBE & 1
-          dst[32 * u] = 0.0 * tv[p][u];
-#else
           dst[32 * u] = tv[p][u] * xv[p][u];
-#endif
       }
     };
 #pragma unroll
     for (int d = 0; d < XE_DEPTH; ++d) ld(e[d], d);
     asm volatile("" ::: "memory");
-#if SA_XE_PROBE & 32
-    long long pw_work = 0, pw_bar = 0, pw_t = clock64();
-#endif
     for (int j0 = 0; j0 < nchp; j0 += XE_DEPTH) {
 #pragma unroll
       for (int d = 0; d < XE_DEPTH; ++d) {
         products(e[d], j0 + d);
         ld(e[d], j0 + d + XE_DEPTH);  // past the last chunk: harmless clamped re-reads
         asm volatile("" ::: "memory");
-#if SA_XE_PROBE & 32
-        const long long t1 = clock64();
-        pw_work += t1 - pw_t;
-#endif
         __syncthreads();
-#if SA_XE_PROBE & 32
-        pw_t = clock64();
-        pw_bar += pw_t - t1;
-#endif
       }
     }
-#if SA_XE_PROBE & 32
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      xo[40] = (double)pw_work;
-      xo[41] = (double)pw_bar;
-    }
-#endif
-#if SA_XE_PROBE & 16
-    if (blockIdx.x == 0 && threadIdx.x == 0) xo[3] = (double)(wall_clock64() - t_entry);
-#endif
   } else {  // ---- chain wave: lane i adds row i's products strictly left to right
     // the critical path of the launch (the longest row's adds): first claim on its SIMD's issue
     // slots over the two product waves sharing it (MI355X_MICROARCH.md: priority, then age)
@@ -1065,21 +885,8 @@ __global__ __launch_bounds__(XE_THREADS) void xt_iter_ell_kernel(const uint32_t*
     // dependent f64 add (scratch microbenchmarks: 10.35 clocks per add fed from LDS, 5.2 from
     // registers) -- the longest row's ~6000 adds bound the launch
     double acc = 0.0;
-#if SA_XE_PROBE & 32
-    long long cw_work = 0, cw_bar = 0, cw_t = clock64();
-#endif
     for (int j = 0; j < nchp; ++j) {
-#if SA_XE_PROBE & 32
-      {
-        const long long t1 = clock64();
-        cw_work += t1 - cw_t;
-        __syncthreads();
-        cw_t = clock64();
-        cw_bar += cw_t - t1;
-      }
-#else
       __syncthreads();
-#endif
       if (j * XE_KC >= li) continue;  // row ended (or idle lane): no reads, no +0 adds
       const f64x2* pr = reinterpret_cast<const f64x2*>(prod[j & 1] + i * XE_PITCH);
       constexpr int G = 16;  // 16-B reads (two products each) issued a group ahead of their adds
@@ -1107,19 +914,6 @@ __global__ __launch_bounds__(XE_THREADS) void xt_iter_ell_kernel(const uint32_t*
       xo[row0 + lane] = nx;
       if ((nx - x[rr]) > eps) atomicOr(flag_out, 1);  // np.any(diff > eps): NaN is False
     }
-#if SA_XE_PROBE & 32  // shader clocks of work / barrier wait, chain wave (42, 43), product wave 0 (40, 41)
-    if (blockIdx.x == 0 && lane == 0) {
-      xo[42] = (double)(cw_work + (clock64() - cw_t));
-      xo[43] = (double)cw_bar;
-    }
-#endif
-#if SA_XE_PROBE & 16  // wall clock (100 MHz) ticks from entry: setup done, chain done, (3) products done
-    if (blockIdx.x == 0 && lane == 0) {
-      xo[0] = (double)nchp;
-      xo[1] = (double)(t_setup - t_entry);
-      xo[2] = (double)(wall_clock64() - t_entry);
-    }
-#endif
   }
 }
 
@@ -1186,17 +980,7 @@ constexpr long long XF_SPIN_TICKS_FIRST = 5000000;
 // cell moved by more than eps)
 constexpr int XF_ABORT = 1, XF_AMB = 2, XF_NITER = 3, XF_TOP = 32, XF_GRP = 64, XF_GEN = 64 + 8 * 32,
               XF_FLAGS = 64 + 16 * 32;
-#ifndef SA_XF_PROBE
-#define SA_XF_PROBE 0  // 1: workgroup 0's wall-clock ticks per phase in control words 4..7 (stderr);
-#endif                 // diagnostic builds (wrong values): 2 = conflict-free x reads, 4 = no lane tree
-__device__ __forceinline__ uint32_t xf_col(uint32_t e, int q) {
-#if SA_XF_PROBE & 2
-  return (uint32_t)((threadIdx.x & 63) + 64 * q) + (e & 0x10000u ? 1u : 0u);
-#else
-  (void)q;
-  return e & 0xFFFFu;
-#endif
-}
+__device__ __forceinline__ uint32_t xf_col(uint32_t e) { return e & 0xFFFFu; }
 typedef uint32_t __attribute__((address_space(1))) xf_gu32;
 typedef unsigned long long __attribute__((address_space(1))) xf_gu64;
 
@@ -1261,7 +1045,7 @@ __device__ __forceinline__ bool xf_has_esc(const u32x4& e) {
 
 // Cross-lane moves without LDS (DPP and gfx950's v_permlane16_swap): a reduction through
 // ds_bpermute paid the LDS latency at every one of its dependent levels (5.3 of 8.7 us per
-// iteration at cfg5, probe build SA_XF_PROBE & 4).
+// iteration at cfg5, measured with a probe build without the lane tree).
 template <int CTRL>
 __device__ __forceinline__ double xf_dpp(double v) {  // DPP row op on both dwords
   const long long b = __double_as_longlong(v);
@@ -1317,7 +1101,7 @@ __device__ __forceinline__ double xf_group(const u32x4 (&e)[XF_G], const double*
 #pragma unroll
   for (int p = 0; p < XF_PAIR; ++p)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) xa[p][q] = xs[xf_col(e[p][q], q)];
+    for (int q = 0; q < 4; ++q) xa[p][q] = xs[xf_col(e[p][q])];
 #pragma unroll
   for (int s = 0; s < XF_G / XF_PAIR; ++s) {
     double(&cur)[XF_PAIR][4] = (s & 1) ? xb : xa;
@@ -1326,7 +1110,7 @@ __device__ __forceinline__ double xf_group(const u32x4 (&e)[XF_G], const double*
 #pragma unroll
       for (int p = 0; p < XF_PAIR; ++p)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) nxt[p][q] = xs[xf_col(e[(s + 1) * XF_PAIR + p][q], q)];
+        for (int q = 0; q < 4; ++q) nxt[p][q] = xs[xf_col(e[(s + 1) * XF_PAIR + p][q])];
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -1339,14 +1123,7 @@ __device__ __forceinline__ double xf_group(const u32x4 (&e)[XF_G], const double*
     }
     __builtin_amdgcn_sched_barrier(0);
   }
-#if SA_XF_PROBE & 4
-  double z = 0.0;
-#pragma unroll
-  for (int k = 0; k < XF_G; ++k) z += v[k];
-  return z;
-#else
   return xf_reduce8(v, l32);
-#endif
 }
 
 __global__ __launch_bounds__(XF_THREADS) void xt_solve_reordered_kernel(
@@ -1363,9 +1140,6 @@ __global__ __launch_bounds__(XF_THREADS) void xt_solve_reordered_kernel(
   uint32_t* scan = reinterpret_cast<uint32_t*>(xs);  // prologue: units of every row, scanned
   __shared__ uint32_t ws[XF_THREADS / 64 + 1];
   __shared__ int s_ra, s_rb;
-#if SA_XF_PROBE
-  const long long k_entry = wall_clock64();
-#endif
   const int t = threadIdx.x, G = gridDim.x, g = blockIdx.x;
   const int l32 = t & 31, hw = t >> 5;
   const int pe = xe_pitch(C);
@@ -1430,17 +1204,6 @@ __global__ __launch_bounds__(XF_THREADS) void xt_solve_reordered_kernel(
     return;
   }
 
-#if SA_XF_PROBE
-  long long pt[5] = {0, 0, 0, 0, 0}, pc = k_entry;  // prologue, stage, units, rows, barrier
-  auto tick = [&](int ph) {
-    const long long n = wall_clock64();
-    pt[ph] += n - pc;
-    pc = n;
-  };
-  tick(0);
-#else
-  auto tick = [](int) {};
-#endif
   constexpr double u = 0x1p-53;
   const double delta = (2.0 * (double)C + 16.0) * u;
   double ebound = 0.0;  // relative distance of x_t from the reference's x_t (bound)
@@ -1467,7 +1230,6 @@ __global__ __launch_bounds__(XF_THREADS) void xt_solve_reordered_kernel(
       }
     }
     __syncthreads();
-    tick(1);
     // ---- unit sums of the half-wave: registers, LDS, then re-read ones
 #pragma unroll
     for (int k0 = 0; k0 < XF_KREG; k0 += XF_G) {
@@ -1494,7 +1256,6 @@ __global__ __launch_bounds__(XF_THREADS) void xt_solve_reordered_kernel(
       if ((l32 & 3) == 0 && k < hn) part[hb + k] = s;
     }
     __syncthreads();
-    tick(2);
     // ---- rows, 8 lanes each: lane j sums units j, j + 8, ... in order, a fixed 8-lane tree; / move,
     // the reference's gs + pmove * (.) and its decision
     const double enext = (ebound + delta) * (1.0 + 0x1p-20);
@@ -1538,7 +1299,6 @@ __global__ __launch_bounds__(XF_THREADS) void xt_solve_reordered_kernel(
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its stores
     const int any_up = __syncthreads_or(up), any_amb = __syncthreads_or(amb);
-    tick(3);
 #if SA_DEBUG
     // sa_debug_xt_solve_abort: the last workgroup leaves without arriving (workgroup-uniform),
     // as if it never got a CU; the others' bounded polls time out and take the abort exit
@@ -1563,7 +1323,6 @@ __global__ __launch_bounds__(XF_THREADS) void xt_solve_reordered_kernel(
       if (go) xf_wait(ctrl, ctrl + XF_GEN + 32 * grp, epoch, it == 0 ? XF_SPIN_TICKS_FIRST : XF_SPIN_TICKS);
     }
     __syncthreads();
-    tick(4);
     const uint32_t flag = xf_ld32(ctrl + XF_FLAGS + it);
     const uint32_t stop = xf_ld32(ctrl + XF_ABORT) | xf_ld32(ctrl + XF_AMB);
     if (stop) break;  // every workgroup reads the same words behind the same barrier
@@ -1573,20 +1332,7 @@ __global__ __launch_bounds__(XF_THREADS) void xt_solve_reordered_kernel(
       break;
     }
   }
-#if SA_XF_PROBE
-  if (t == 0) {  // the slowest workgroup's unit phase and the most units of one workgroup
-    atomicMax(ctrl + XF_FLAGS + max_iter + 1, (int32_t)pt[2]);
-    atomicMax(ctrl + XF_FLAGS + max_iter + 2, nu);
-    atomicMax(ctrl + XF_FLAGS + max_iter + 3, (int32_t)pt[1]);
-  }
-#endif
-  if (g == 0 && t == 0) {
-    ctrl[XF_NITER] = n_iter;
-#if SA_XF_PROBE
-    for (int q = 0; q < 4; ++q) ctrl[4 + q] = (int32_t)pt[q + 1];
-    ctrl[XF_FLAGS + max_iter] = (int32_t)pt[0];
-#endif
-  }
+  if (g == 0 && t == 0) ctrl[XF_NITER] = n_iter;
 }
 
 }  // namespace sa
@@ -1629,7 +1375,7 @@ static int bucket_batch(const sa_actions& A, const uint32_t* cells, int64_t n, i
   // K1 runs one workgroup per CU: a batch's regions in whole rounds of the CUs (16M actions:
   // 489 regions of 32768 -> 512 of 31,488; a 4M tail: 123 -> 256), regions of >= 4096 actions
   int64_t regions = (n + XK_CHUNK - 1) / XK_CHUNK, chunk = XK_CHUNK;
-  if (SA_XK_BALANCE && n > 0) {
+  if (n > 0) {
     const int64_t G = device_cus(current_device());
     const int64_t r = (regions + G - 1) / G * G;
     chunk = ((n + r - 1) / r + 255) & ~(int64_t)255;
@@ -1667,8 +1413,8 @@ static int bucket_batch(const sa_actions& A, const uint32_t* cells, int64_t n, i
     rc = check_launch("xt_keys_kernel");
   }
   if (!rc) {
-    const size_t lds = ((size_t)2 * S.NB + XS_PART) * 4;
-    hipLaunchKernelGGL(xt_keys_scatter_kernel, dim3((unsigned)(regions * XS_SPLIT)), dim3(XS_THREADS), lds, st, keys,
+    const size_t lds = ((size_t)2 * S.NB + XK_CHUNK) * 4;
+    hipLaunchKernelGGL(xt_keys_scatter_kernel, dim3((unsigned)regions), dim3(XS_THREADS), lds, st, keys,
                        region_cnt, S, band_cnt, band_off, cursor, buckets);
     rc = check_launch("xt_keys_scatter_kernel");
   }
@@ -1742,11 +1488,9 @@ int xt_compact_iterate(const uint32_t* ell, const int32_t* row_len, const int32_
                        double* xo, const int32_t* flag_prev, int32_t* flag_out, hipStream_t st) {
   const int ns = (nrows + XE_S - 1) / XE_S;
   if (ns == 0) return SA_OK;
-  int ct = SA_XE_QDIV ? 0 : XE_CT_MAX;  // the quotient table: as many counts as fit next to x
-  while (ct > 16 && (size_t)C * 8 + (size_t)XE_S * ct * 8 + XE_LDS_STATIC > XE_LDS_MAX) ct >>= 1;
-  hipLaunchKernelGGL(xt_iter_ell_kernel, dim3((unsigned)ns), dim3(XE_THREADS), ((size_t)C + (size_t)XE_S * ct) * 8, st,
-                     ell, row_len, cnt_rows, reinterpret_cast<const unsigned long long*>(move), gs, pmove, C, rb,
-                     nrows, ct, eps, x, xo, flag_prev, flag_out);
+  hipLaunchKernelGGL(xt_iter_ell_kernel, dim3((unsigned)ns), dim3(XE_THREADS), (size_t)C * 8, st, ell, row_len,
+                     cnt_rows, reinterpret_cast<const unsigned long long*>(move), gs, pmove, C, rb, nrows, 0, eps, x,
+                     xo, flag_prev, flag_out);
   return check_launch("xt_iter_ell_kernel");
 }
 
@@ -1819,14 +1563,6 @@ static int xt_solve_reordered(const uint32_t* ell, const int32_t* row_len, const
     hook->ran = true;
   }
   if (!rc) rc = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-#if SA_XF_PROBE
-  int32_t pro[4] = {0, 0, 0, 0};
-  if (!rc) rc = check_hip(hipMemcpy(pro, ctrl + XF_FLAGS + max_iter, 16, hipMemcpyDeviceToHost), "copy probe");
-  fprintf(stderr,
-          "xf_probe C=%d G=%d kreg=%d iters=%d ticks(10ns) wg0: prologue %d stage %d units %d rows %d barrier %d; "
-          "max over wgs: units %d stage %d, units per wg %d (register capacity %d)\n",
-          C, G, XF_KREG, h[XF_NITER], pro[0], h[4], h[5], h[6], h[7], pro[1], pro[3], pro[2], XF_HALVES * XF_KREG);
-#endif
   scratch_release(sc, st);
   if (rc) return rc;
   if (h[XF_ABORT])  // 1: a barrier timed out; 2 / 4: a bound or an escaped count (not launchable)

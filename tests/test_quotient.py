@@ -1,4 +1,4 @@
-"""The compact xT iteration's quotient (xt_iter_ell_kernel, SA_XE_QDIV): cnt / move formed as a
+"""The compact xT iteration's quotient (xt_iter_ell_kernel): cnt / move formed as a
 reciprocal product plus one fma correction must be the IEEE quotient bit for bit (the reference
 divides, xthreat.py:_get_transition_matrix); so must the binning's x / 105 and y / 68 (bin_quot,
 sa_common.h; xthreat.py:_get_cell_indexes).  scripts/check_quotient.c checks the identity on
