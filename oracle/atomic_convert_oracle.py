@@ -90,17 +90,18 @@ def _extra_from_passes(f):
     return _merge(f, e)
 
 
-def _add_dribbles(f):
-    """spadl/base.py:54-93 (``shift(-1, fill_value=0)``: the last row's next is all zeros)."""
+def _add_dribbles(f, min_length=3.0, max_length=60.0, max_duration=10.0):
+    """spadl/base.py:54-93 (``shift(-1, fill_value=0)``: the last row's next is all zeros); the
+    three thresholds are the reference's module globals (base.py:49-51)."""
     nx, _ = _next(f, fill=0)
     same_team = f['team_id'] == nx['team_id']
     dx = f['end_x'] - nx['start_x']
     dy = f['end_y'] - nx['start_y']
     d2 = dx ** 2 + dy ** 2
-    far = d2 >= 3.0 ** 2
-    near = d2 <= 60.0 ** 2
+    far = d2 >= min_length ** 2
+    near = d2 <= max_length ** 2
     dt = nx['time_seconds'] - f['time_seconds']
-    idx = same_team & far & near & (dt < 10.0) & (f['period_id'] == nx['period_id'])
+    idx = same_team & far & near & (dt < max_duration) & (f['period_id'] == nx['period_id'])
     p = {c: v[idx] for c, v in f.items()}
     q = {c: v[idx] for c, v in nx.items()}
     d = {}
@@ -158,15 +159,17 @@ def _extra_from_fouls(f):
     return _merge(f, e)
 
 
-def add_dribbles(cols: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+def add_dribbles(cols: Dict[str, np.ndarray], min_length: float = 3.0, max_length: float = 60.0,
+                 max_duration: float = 10.0) -> Dict[str, np.ndarray]:
     """spadl/base.py:54-93 on its own (the SPADL converters' last step): the SPADL columns of
-    COLS in, the same columns out with action_id reset to int64 positions."""
+    COLS in, the same columns out with action_id reset to int64 positions.  The thresholds
+    default to the reference's module globals."""
     f = {c: np.asarray(cols[c]) for c in COLS}
     f['action_id'] = f['action_id'].astype(np.float64)
     f['original_event_id'] = f['original_event_id'].astype(object)
     if len(f['type_id']) == 0:
         return {c: (v.astype(np.int64) if c == 'action_id' else v) for c, v in f.items()}
-    f = _add_dribbles(f)
+    f = _add_dribbles(f, min_length, max_length, max_duration)
     f['action_id'] = f['action_id'].astype(np.int64)
     return f
 

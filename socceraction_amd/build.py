@@ -5,6 +5,10 @@
 Flags: ``-O3 --offload-arch=gfx950 -ffp-contract=off``.  ``-ffp-contract=off`` is a
 parity requirement: numpy evaluates ``dx**2 + dy**2`` and the xT dot products with a
 separately rounded multiply and add, so the kernels must not fuse them into FMAs.
+tests/test_gpu_thresholds.py holds it on the device: its dribble frames carry pairs on which a
+fused ``dx*dx + dy*dy`` decides the 3 m / 60 m rule differently (test_dribble_thresholds_*), and
+its binning tests (test_binning_edges_*) hold ``x / 105 * l`` -- by a division and by
+``bin_quot``'s reciprocal and two explicit FMAs -- to the reference at the cell edges.
 
 Every build embeds a build id -- a hash of the sources, headers, flags and defines -- as
 ``sa_build_id()`` and as a ``sa-build-id:<hash>`` marker in the file.  A library is rebuilt

@@ -4,7 +4,9 @@ divides, xthreat.py:_get_transition_matrix); so must the binning's x / 105 and y
 sa_common.h; xthreat.py:_get_cell_indexes).  scripts/check_quotient.c checks the identity on
 the host in double arithmetic -- the same operations the kernel issues (v_rcp-free division for
 the reciprocal, v_mul_f64, two v_fma_f64).  A reduced sweep here; the full one (every count
-< 65536 x 12001 divisors + 4e8 random pairs) is the program's default."""
+< 65536 x 12001 divisors + 4e8 random pairs) is the program's default.  On the device the
+binning identity is held by tests/test_gpu_thresholds.py (test_binning_edges_*: coordinates on
+the cell edges +-2 ulp through every kernel that bins, against the oracle and the reference)."""
 import os
 import shutil
 import subprocess
