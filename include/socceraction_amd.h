@@ -780,6 +780,87 @@ int sa_auc_keys(const uint8_t* y, const void* p, int32_t f32, int64_t n, int32_t
 int sa_auc_count(const uint8_t* y, const void* p, int32_t f32, int64_t n, const void* sorted_keys,
                  int64_t m, int32_t minority, uint64_t* u2, void* stream);
 
+/* ---- boosted-tree training ------------------------------------------------------
+ * Reproducible histogram gradient boosting (binary logistic loss, depth-limited trees, xgboost's
+ * `hist` rules) on the device feature blocks: VAEP.fit's learner='device' (reference
+ * vaep/base.py:139-213 delegates to a host learner).  The arithmetic contract is DESIGN.md §3
+ * "Boosted-tree training": float32 cuts, bin(x) = #{i : cut_i <= x32} with NaN -> 255, gradients
+ * quantised to int32 at scale 2^30, int64 histograms, float64 gains, ties to the lowest feature
+ * then the lowest cut.  Every sum is an integer sum, so the model is the same bit for bit from
+ * run to run and for any row order.  All pointers are device pointers; every entry validates
+ * its arguments before any HIP call (SA_EINVAL) and enqueues on `stream` without synchronising.
+ *
+ * Features are numbered 0 .. n_features-1 in model order.  cut_start [n_features + 1] and cuts
+ * hold every feature's ascending float32 cuts (at most SA_BOOST_MAX_CUTS; a bool feature has
+ * the single cut 0.5).  Numeric feature number num_feat[r] is row r of the feature-major bin
+ * matrix bins [n_num, ld] (ld >= n, a multiple of 4; 4-byte aligned); bool feature number
+ * bit_feat[c] is row bit_rows[c] of the Arrow bitmaps `bits` (bits_stride bytes per row, a
+ * multiple of 8, bit i of 64-bit word w = row 64w + i; 8-byte aligned).
+ * A row's node (uint8 [ld], 4-byte aligned) is its heap index in the round's tree (root 0,
+ * children 2k + 1 and 2k + 2), SA_BOOST_NO_NODE for a row that takes no part.  A level is the
+ * node range node0 = n_nodes - 1, n_nodes = 2^level <= SA_BOOST_MAX_LEVEL_NODES.
+ * hist [n_nodes, n_features, 256, 2] int64 (caller-zeroed per level): the sums of gq and hq per
+ * (level-local node, feature, bin).  tree: the round's 2^(max_depth+1) - 1 nodes (caller-zeroed).
+ *
+ * sa_boost_bin: the numeric features' bins from the f64 / i64 blocks (f32 != 0: both blocks hold
+ *   float32); slots[r] = (1 << 24 | f64 column) or (2 << 24 | i64 column); x32 is the value the
+ *   tree predictor compares ((float)x, for an i64 column (float)(double)x).
+ * sa_boost_grad: p = 1 / (1 + expf(-margin)); with gq: g = p - y, h = p (1 - p) in float32,
+ *   gq = (int32)rint(g 2^30), hq likewise.  p and node are optional; node is set to 0, or to
+ *   SA_BOOST_NO_NODE where row_mask (optional) is 0.
+ * sa_boost_hist_bits: ADDS the set-bit sums of every bool feature into bin 1, then sets bin 0 to
+ *   the node's total minus bin 1.  add_totals != 0: the nodes' totals are first added to
+ *   tree[node0 + k].G / .H (level 0); otherwise they are read from there.
+ * sa_boost_hist_bins: ADDS the numeric features' histograms.
+ * sa_boost_split: for every existing node of the level its leaf value (float)(eta * -(G / (H +
+ *   lambda))) and, unless leaf_only, its best split -- over the cuts i with both children's
+ *   hessian sums >= min_child_weight, gain = ((GL*GL)/(HL+lambda) + (GR*GR)/(HR+lambda)) -
+ *   (G*G)/(H+lambda) in float64, the maximum with ties to the lowest feature then the lowest
+ *   cut, taken iff > gamma -- with its children's totals written to their records.  best_gain /
+ *   best_cut [n_nodes * n_features]: scratch.  leaf_only allows n_nodes up to 64.
+ * sa_boost_advance: margin == NULL: every row in a split node of the level moves to a child
+ *   (bit set, or bin > cut: the right one); fmap[f] = bitmap row, or 1 << 24 | bin-matrix row.
+ *   margin != NULL: margin[j] += tree[node[j]].value for every participating row. */
+#define SA_BOOST_MAX_DEPTH 6
+#define SA_BOOST_MAX_CUTS 254
+#define SA_BOOST_MISSING_BIN 255
+#define SA_BOOST_NO_NODE 255
+#define SA_BOOST_MAX_LEVEL_NODES 32
+#define SA_BOOST_BIN_TILE 1024
+#define SA_BOOST_BITS_TILE 2048
+#define SA_BOOST_BINS_TILE 1024
+#define SA_BOOST_FEATURE_GROUP 4
+typedef struct sa_boost_node {
+  int64_t G, H;      /* sums of gq, hq over the node's rows */
+  double gain;       /* of its split (0 for a leaf) */
+  int32_t feature;   /* -1 = leaf */
+  int32_t cut;       /* cut index: bin <= cut goes left */
+  float thr;         /* cuts[cut_start[feature] + cut] */
+  float value;       /* leaf value (every existing node has one) */
+  int32_t exists;
+  int32_t pad;
+} sa_boost_node;
+int sa_boost_bin(const sa_block* f64_blk, const sa_block* i64_blk, int32_t f32, const int32_t* slots,
+                 const int32_t* num_feat, const int32_t* cut_start, const float* cuts, int32_t n_num,
+                 int64_t n, uint8_t* bins, int64_t ld, void* stream);
+int sa_boost_grad(const float* margin, const uint8_t* y, const uint8_t* row_mask, int64_t n,
+                  int32_t* gq, int32_t* hq, float* p, uint8_t* node, void* stream);
+int sa_boost_hist_bits(const uint64_t* bits, int64_t bits_stride, const int32_t* bit_rows,
+                       const int32_t* bit_feat, int32_t n_bool, const int32_t* gq, const int32_t* hq,
+                       const uint8_t* node, int64_t n, int32_t node0, int32_t n_nodes,
+                       int32_t n_features, int64_t* hist, sa_boost_node* tree, int32_t add_totals,
+                       void* stream);
+int sa_boost_hist_bins(const uint8_t* bins, int64_t ld, const int32_t* num_feat, int32_t n_num,
+                       const int32_t* gq, const int32_t* hq, const uint8_t* node, int64_t n,
+                       int32_t node0, int32_t n_nodes, int32_t n_features, int64_t* hist, void* stream);
+int sa_boost_split(const int64_t* hist, const int32_t* cut_start, const float* cuts, int32_t n_features,
+                   int32_t node0, int32_t n_nodes, int32_t leaf_only, double reg_lambda,
+                   double min_child_weight, double gamma, double learning_rate, double* best_gain,
+                   int32_t* best_cut, sa_boost_node* tree, void* stream);
+int sa_boost_advance(const sa_boost_node* tree, int32_t node0, int32_t n_nodes, const int32_t* fmap,
+                     const uint64_t* bits, int64_t bits_stride, const uint8_t* bins, int64_t ld,
+                     int64_t n, uint8_t* node, float* margin, void* stream);
+
 /* ---- runtime ------------------------------------------------------------------ */
 int sa_abi_version(void);
 const char* sa_last_error(void);

@@ -1,0 +1,137 @@
+"""One device fit of both VAEP learners (socceraction_amd.boost, default parameters: 100 rounds,
+depth 3) on the synthetic cfg2-shaped batch of `--games` games, timed per kernel family with HIP
+events -- bin, grad, hist_bits, hist_bins, split, advance -- plus the wall clock of the whole
+``VAEP.fit_batch`` call, and as a reference point (not a pass mark) scikit-learn's
+HistGradientBoostingClassifier with the same shape on the host's CPUs on the same rows copied
+out, with the copy-out time.
+
+One warm-up fit (2 rounds) precedes everything timed.  The per-family figures come from one
+instrumented fit per learner (an event pair around every launch: the sum over the fit and the
+median launch); the wall clock is the median of `--reps` uninstrumented ``fit_batch`` calls.  The
+histogram kernels are also held against the bytes a level has to read (bitmaps n_bool / 8, bins
+F_num, gradients and node 9 bytes per row).
+
+    python scripts/boost_time.py [--games 1000] [--reps 3] [--sklearn] [--out FILE]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from socceraction_amd import batch as B, boost, ops, synthetic  # noqa: E402
+from socceraction_amd.vaep import VAEP  # noqa: E402
+
+HBM_BYTES_PER_S = 8e12
+FAMILIES = ('grad', 'hist_bits', 'hist_bins', 'split', 'advance')
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--games', type=int, default=1000)
+    ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--sklearn', action='store_true')
+    ap.add_argument('--out', default='')
+    args = ap.parse_args()
+    d = synthetic.spadl_games(args.games, seed=2)
+    actions, games = synthetic.to_frame(d), synthetic.games_frame(d)
+    model = VAEP()
+    known, _ = model._split_xfns()
+    home_of = games.set_index('game_id')['home_team_id']
+    ab = B.ActionBatch.from_frame(actions, home_team_id=home_of, segments='game')
+    n = ab.n
+    res = {'device': torch.cuda.get_device_name(0), 'games': args.games, 'rows': n, 'reps': args.reps,
+           'params': dict(boost.DEFAULTS), 'hbm_bytes_per_s_for_floors': HBM_BYTES_PER_S}
+    # ---- warm-up, and the model is the same from run to run
+    VAEP().fit_batch(games, actions, tree_params=dict(n_estimators=2))
+    fb = ops.features(ab, known, 3, bool_bits=True)
+    lb = ops.labels(ab)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    cuts = boost.make_cuts(fb)
+    torch.cuda.synchronize()
+    res['make_cuts_ms'] = round((time.perf_counter() - t0) * 1e3, 2)
+    e0.record()
+    data = boost.bin_blocks(fb, cuts)
+    e1.record()
+    torch.cuda.synchronize()
+    n_bool, f_num = len(data.bit_feat), len(data.num_feat)
+    res.update(n_bool=n_bool, f_num=f_num, bin_ms=round(e0.elapsed_time(e1), 3))
+    res['bin_GBs'] = round(n * (8 * f_num + f_num) / e0.elapsed_time(e1) * 1e-6, 1)
+    bytes_level = {'hist_bits': n * (n_bool / 8 + 9), 'hist_bins': n * (f_num + 9)}
+    res['bytes_per_row_per_level'] = {'bitmaps': n_bool / 8, 'bins': f_num, 'gradients_and_node': 9}
+    jsons = {}
+    for col in ('scores', 'concedes'):
+        clf = boost.DeviceGBTClassifier()
+        clf._events = []
+        t0 = time.perf_counter()
+        clf.fit_binned(data, getattr(lb, col))
+        torch.cuda.synchronize()
+        wall = (time.perf_counter() - t0) * 1e3
+        per = {f: [a.elapsed_time(b) for fam, a, b in clf._events if fam == f] for f in FAMILIES}
+        entry = {'instrumented_fit_wall_ms': round(wall, 1),
+                 'sum_ms': {f: round(sum(v), 2) for f, v in per.items()},
+                 'launches': {f: len(v) for f, v in per.items()},
+                 'median_launch_ms': {f: round(statistics.median(v), 4) for f, v in per.items() if v}}
+        for f, nbytes in bytes_level.items():
+            ms = statistics.median(per[f])
+            entry.setdefault('median_GBs', {})[f] = round(nbytes / ms * 1e-6, 1)
+            entry.setdefault('fraction_of_hbm_rate', {})[f] = round(nbytes / ms * 1e3 / HBM_BYTES_PER_S, 4)
+        # LDS integer atomics a level issues for the numeric bins (two per feature and row), per second
+        entry['lds_atomics_per_s'] = {
+            'hist_bins': round(2 * f_num * n / (statistics.median(per['hist_bins']) * 1e-3), 0)}
+        clf._events = None
+        jsons[col] = json.dumps(clf.to_xgboost_json())
+        entry['split_nodes'] = int((clf.trees_['feature'] >= 0).sum())
+        res[col] = entry
+        print(col, json.dumps(entry), flush=True)
+    # ---- the call a user makes
+    walls = []
+    for _ in range(args.reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        m = VAEP().fit_batch(games, actions)
+        torch.cuda.synchronize()
+        walls.append(round((time.perf_counter() - t0) * 1e3, 1))
+    res['fit_batch_wall_ms'] = walls
+    res['fit_batch_wall_ms_median'] = statistics.median(walls)
+    res['run_to_run_equal'] = all(json.dumps(m._VAEP__models[c].to_xgboost_json()) == jsons[c] for c in jsons)
+    res['train_scores'] = {c: {k: v[k] for k in ('log_loss', 'log_loss_baseline', 'auroc')}
+                           for c, v in m.score_batch(games, actions).items()}
+    line = json.dumps(res)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(json.dumps(res, indent=1) + '\n')
+    if args.sklearn:  # the reference point: the rows copied out, one label, the host's CPUs
+        from sklearn.ensemble import HistGradientBoostingClassifier
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        X = ops.features(ab, known, 3).to_frame()
+        y = lb.scores[:n].cpu().numpy()
+        t1 = time.perf_counter()
+        sk = HistGradientBoostingClassifier(max_iter=100, max_depth=3, learning_rate=0.3, l2_regularization=1.0,
+                                            max_leaf_nodes=None, min_samples_leaf=1, early_stopping=False)
+        sk.fit(X, y)
+        t2 = time.perf_counter()
+        res['sklearn_one_label'] = {'copy_out_ms': round((t1 - t0) * 1e3, 1), 'fit_ms': round((t2 - t1) * 1e3, 1),
+                                    'cpus': int(os.environ.get('OMP_NUM_THREADS', 0)) or None}
+        line = json.dumps(res)
+        if args.out:
+            with open(args.out, 'w') as f:
+                f.write(json.dumps(res, indent=1) + '\n')
+    print(line)
+    if not res['run_to_run_equal']:
+        raise SystemExit(3)
+
+
+if __name__ == '__main__':
+    main()

@@ -40,6 +40,10 @@ SA_METRIC_BRIER_EXP, SA_METRIC_LOGLOSS_EXP = 1, 6  # scale exponents of the scor
 SA_METRIC_CHUNK_ROWS = 4096
 SA_METRIC_ERR_NAN, SA_METRIC_ERR_RANGE, SA_METRIC_ERR_LABEL = 1, 2, 4
 SA_AUC_LDS_SAMPLE = 1024  # sorted minority keys sa_auc_count keeps in LDS
+# boosted-tree training (sa_boost.hip; mirrors include/socceraction_amd.h)
+SA_BOOST_MAX_DEPTH, SA_BOOST_MAX_CUTS, SA_BOOST_MISSING_BIN, SA_BOOST_NO_NODE = 6, 254, 255, 255
+SA_BOOST_MAX_LEVEL_NODES, SA_BOOST_FEATURE_GROUP = 32, 4
+SA_BOOST_BIN_TILE, SA_BOOST_BITS_TILE, SA_BOOST_BINS_TILE = 1024, 2048, 1024
 SA_OK, SA_EINVAL, SA_EHIP, SA_EDATA, SA_ENOMEM = 0, -1, -2, -3, -4
 
 # enum sa_xfn (order matters: mirrors include/socceraction_amd.h)
@@ -258,6 +262,20 @@ _SIGNATURES = {
                                    ctypes.c_int64, _p, _p]),
     'sa_auc_count': (ctypes.c_int, [_p, _p, ctypes.c_int32, ctypes.c_int64, _p, ctypes.c_int64,
                                     ctypes.c_int32, _p, _p]),
+    'sa_boost_bin': (ctypes.c_int, [ctypes.POINTER(SaBlock), ctypes.POINTER(SaBlock), ctypes.c_int32, _p, _p, _p,
+                                    _p, ctypes.c_int32, ctypes.c_int64, _p, ctypes.c_int64, _p]),
+    'sa_boost_grad': (ctypes.c_int, [_p, _p, _p, ctypes.c_int64, _p, _p, _p, _p, _p]),
+    'sa_boost_hist_bits': (ctypes.c_int, [_p, ctypes.c_int64, _p, _p, ctypes.c_int32, _p, _p, _p,
+                                          ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                          _p, _p, ctypes.c_int32, _p]),
+    'sa_boost_hist_bins': (ctypes.c_int, [_p, ctypes.c_int64, _p, ctypes.c_int32, _p, _p, _p,
+                                          ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                          _p, _p]),
+    'sa_boost_split': (ctypes.c_int, [_p, _p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                      ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                      ctypes.c_double, _p, _p, _p, _p]),
+    'sa_boost_advance': (ctypes.c_int, [_p, ctypes.c_int32, ctypes.c_int32, _p, _p, ctypes.c_int64, _p,
+                                        ctypes.c_int64, ctypes.c_int64, _p, _p, _p]),
     'sa_device_alloc': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
     'sa_device_free': (ctypes.c_int, [_p]),
     'sa_copy2d_async': (ctypes.c_int, [_p, ctypes.c_int64, _p, ctypes.c_int64, ctypes.c_int64,

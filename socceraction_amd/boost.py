@@ -1,0 +1,663 @@
+"""Reproducible histogram gradient boosting on the device feature blocks (``learner='device'``).
+
+``VAEP.fit`` (reference vaep/base.py:139-213) hands the feature frame to xgboost, catboost or
+lightgbm on the host.  This module trains the same kind of model -- binary logistic gradient
+boosting, depth-limited trees, xgboost's ``hist`` rules (float32 values, ``x < threshold`` goes
+left) -- where the features already are, with the kernels of ``csrc/sa_boost.hip``, and exports it
+in the xgboost-1.6 JSON shape that :meth:`socceraction_amd.trees.TreeEnsemble.from_xgboost_json`
+reads, so the device ``rate`` paths consume it unchanged.
+
+The arithmetic contract (DESIGN.md §3 "Boosted-tree training"; ``tests/boost_reference.py``
+restates it in numpy): float32 cuts, ``bin(x) = #{i : cut_i <= x32}`` with NaN -> 255, gradients
+quantised to int32 at scale 2^30, int64 histograms, float64 gains, ties to the lowest feature then
+the lowest cut.  Every sum is an integer sum: the model is the same bit for bit from run to run
+and for any row order.  No early stopping, subsampling, sample weights, categorical splits or
+learned default directions (missing values always go right).
+"""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+from typing import Any, Dict, List, Optional, Sequence
+
+import numpy as np
+
+from . import _native
+
+NODE_DTYPE = np.dtype([('G', '<i8'), ('H', '<i8'), ('gain', '<f8'), ('feature', '<i4'), ('cut', '<i4'),
+                       ('thr', '<f4'), ('value', '<f4'), ('exists', '<i4'), ('pad', '<i4')])
+assert NODE_DTYPE.itemsize == 48
+MAX_CUTS = _native.SA_BOOST_MAX_CUTS
+MISSING_BIN = _native.SA_BOOST_MISSING_BIN
+NO_NODE = _native.SA_BOOST_NO_NODE
+MAX_DEPTH = _native.SA_BOOST_MAX_DEPTH
+SAMPLE_ROWS = 65536
+GRAD_SCALE = 2 ** 30
+DEFAULTS = dict(n_estimators=100, max_depth=3, learning_rate=0.3, reg_lambda=1.0, min_child_weight=1.0,
+                gamma=0.0, base_score=0.5)
+
+
+# ----------------------------------------------------------------------------- cuts (host)
+def sample_rows(n: int) -> np.ndarray:
+    """The deterministic row sample the cuts are chosen from: rows ``floor(i * n / S)``,
+    ``i < S = min(n, 65536)``."""
+    S = min(int(n), SAMPLE_ROWS)
+    if S <= 0:
+        return np.zeros(0, np.int64)
+    return (np.arange(S, dtype=np.int64) * int(n)) // S
+
+
+def cast32(col) -> np.ndarray:
+    """A host column as the float32 values the tree predictor compares (csrc/sa_trees.hip's
+    ``(float)feature_value(...)``: an integer column goes int64 -> double -> float)."""
+    col = np.asarray(col)
+    if col.dtype == np.float32:
+        return col
+    if col.dtype.kind in 'iu':
+        return col.astype(np.int64).astype(np.float64).astype(np.float32)
+    with np.errstate(over='ignore'):  # a double beyond float32's range becomes +-inf
+        return col.astype(np.float64).astype(np.float32)
+
+
+def cuts_from_sample(sample, is_bool: bool = False) -> np.ndarray:
+    """One feature's strictly ascending float32 cuts (at most 254) from its sampled values: a
+    bool feature has the single cut 0.5; a sample of at most 255 distinct non-NaN values gives
+    every distinct value but the smallest; otherwise the values at ranks ``floor(i * L / 255)``,
+    ``i = 1..254``, of the sorted sample of length L, deduplicated, without the sample minimum."""
+    if is_bool:
+        return np.array([0.5], np.float32)
+    s = cast32(sample).ravel()
+    s = np.sort(s[~np.isnan(s)])
+    if not len(s):
+        return np.zeros(0, np.float32)
+    u = np.unique(s)
+    if len(u) <= MAX_CUTS + 1:
+        return u[1:].astype(np.float32)
+    L = len(s)
+    c = np.unique(s[(np.arange(1, MAX_CUTS + 1, dtype=np.int64) * L) // (MAX_CUTS + 1)])
+    return c[c > s[0]].astype(np.float32)
+
+
+def bin_values(x32, cuts) -> np.ndarray:
+    """``bin(x) = #{i : cut_i <= x32}``, NaN -> 255 (host statement of ``sa_boost_bin``)."""
+    x32 = np.asarray(x32, np.float32)
+    b = np.searchsorted(np.asarray(cuts, np.float32), x32, side='right').astype(np.uint8)
+    b[np.isnan(x32)] = MISSING_BIN
+    return b
+
+
+def _host_columns(X):
+    """``(names, [column arrays])`` of a host frame or 2-D array."""
+    if hasattr(X, 'columns'):
+        return [str(c) for c in X.columns], [X[c].to_numpy() for c in X.columns]
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError('X must be two-dimensional')
+    return [f'f{j}' for j in range(X.shape[1])], [X[:, j] for j in range(X.shape[1])]
+
+
+def _kind(col: np.ndarray) -> str:
+    return 'b' if col.dtype == np.bool_ else ('i' if col.dtype.kind in 'iu' else 'f')
+
+
+def make_cuts(data, rows=None) -> List[np.ndarray]:
+    """Every feature's cuts (model order) from the deterministic row sample of ``data``: device
+    feature blocks (``ops.FeatureBlocks``; the sample is gathered on the device and copied back
+    once) or a host frame / 2-D array.  ``rows``: the training rows (indices) the sample is
+    taken from, default all."""
+    if hasattr(data, 'plan'):
+        return _make_cuts_blocks(data, rows)
+    names, cols = _host_columns(data)
+    n = len(cols[0]) if cols else 0
+    sel = None if rows is None else np.asarray(rows, np.int64)
+    idx = sample_rows(n if sel is None else len(sel))
+    if sel is not None:
+        idx = sel[idx]
+    return [cuts_from_sample(c[idx], _kind(c) == 'b') for c in cols]
+
+
+def _make_cuts_blocks(blocks, rows=None) -> List[np.ndarray]:
+    import torch
+    dev = blocks.device
+    sel = None if rows is None else torch.as_tensor(rows, device=dev).to(torch.int64)
+    idx = torch.from_numpy(sample_rows(blocks.n if sel is None else sel.numel())).to(dev)
+    if sel is not None:
+        idx = sel[idx]
+    parts = []
+    for t in (blocks.f64_block, blocks.i64_block):
+        R = t.shape[2]
+        v = t[idx // R, :, idx % R]  # [S, C]
+        if v.dtype == torch.int64:
+            v = v.to(torch.float64)
+        parts.append(v.to(torch.float32))
+    nf = parts[0].shape[1]
+    host = torch.cat(parts, 1).cpu().numpy() if len(idx) else np.zeros((0, nf + parts[1].shape[1]), np.float32)
+    out = []
+    for _, kind, col in blocks.plan.order:
+        if kind == 'b':
+            out.append(cuts_from_sample(None, True))
+        else:
+            out.append(cuts_from_sample(host[:, col if kind == 'f' else nf + col]))
+    return out
+
+
+def check_cuts(cuts: Sequence[np.ndarray], n_features: int) -> List[np.ndarray]:
+    if len(cuts) != n_features:
+        raise ValueError(f'{len(cuts)} cut lists for {n_features} features')
+    out = []
+    for f, c in enumerate(cuts):
+        c = np.asarray(c, np.float32).ravel()
+        if len(c) > MAX_CUTS or np.isnan(c).any() or (len(c) > 1 and not (np.diff(c) > 0).all()):
+            raise ValueError(f'feature {f}: cuts must be at most {MAX_CUTS} strictly ascending float32 values')
+        out.append(c)
+    return out
+
+
+# ----------------------------------------------------------------------------- export (host)
+def trees_to_xgboost_json(trees: np.ndarray, feature_names: Sequence[str], base_score: float = 0.5) -> dict:
+    """Node tables ``[n_trees, 2^(max_depth+1) - 1]`` (:data:`NODE_DTYPE`, heap order) as an
+    xgboost-1.6-shaped ``binary:logistic`` gbtree JSON model: each tree's existing nodes in heap
+    order, ``default_left = 0`` everywhere (missing goes right)."""
+    out = []
+    for t, tab in enumerate(np.asarray(trees)):
+        heap = np.flatnonzero(tab['exists'] != 0)
+        if not len(heap):
+            heap = np.array([0])
+        new = {int(h): i for i, h in enumerate(heap)}
+        m = len(heap)
+        left, right, parent = [-1] * m, [-1] * m, [2147483647] * m
+        sidx, cond, gains, hess, bw = [0] * m, [0.0] * m, [0.0] * m, [0.0] * m, [0.0] * m
+        for h, i in new.items():
+            nd = tab[h]
+            bw[i] = float(nd['value'])
+            hess[i] = float(nd['H']) / GRAD_SCALE
+            if nd['feature'] >= 0 and nd['exists']:
+                left[i], right[i] = new[2 * h + 1], new[2 * h + 2]
+                parent[left[i]] = parent[right[i]] = i
+                sidx[i] = int(nd['feature'])
+                cond[i] = float(nd['thr'])
+                gains[i] = float(nd['gain'])
+            else:
+                cond[i] = float(nd['value'])
+        out.append({'left_children': left, 'right_children': right, 'parents': parent,
+                    'split_indices': sidx, 'split_conditions': cond, 'default_left': [0] * m,
+                    'split_type': [0] * m, 'base_weights': bw, 'loss_changes': gains, 'sum_hessian': hess,
+                    'categories': [], 'categories_nodes': [], 'categories_segments': [], 'categories_sizes': [],
+                    'tree_param': {'num_deleted': '0', 'num_feature': str(len(feature_names)),
+                                   'num_nodes': str(m), 'size_leaf_vector': '0'}, 'id': t})
+    return {'learner': {
+        'attributes': {}, 'feature_names': [str(c) for c in feature_names], 'feature_types': [],
+        'objective': {'name': 'binary:logistic', 'reg_loss_param': {'scale_pos_weight': '1'}},
+        'gradient_booster': {'name': 'gbtree', 'model': {
+            'gbtree_model_param': {'num_parallel_tree': '1', 'num_trees': str(len(out)), 'size_leaf_vector': '0'},
+            'trees': out, 'tree_info': [0] * len(out)}},
+        'learner_model_param': {'base_score': repr(float(base_score)), 'num_feature': str(len(feature_names)),
+                                'num_class': '0', 'num_target': '1'}}, 'version': [1, 6, 2]}
+
+
+def base_margin(base_score: float) -> np.float32:
+    """The float32 base margin of ``base_score`` as ``TreeEnsemble.from_xgboost_json`` computes it."""
+    p = np.float32(float(base_score))
+    return np.float32(-np.log(np.float32(1.0) / p - np.float32(1.0)))
+
+
+def predict_tables(trees: np.ndarray, X32: np.ndarray, base_score: float = 0.5) -> np.ndarray:
+    """Host ``P(class 1)`` (float32) of node tables on float32 values ``X32 [n, F]``: the
+    predictor's walk (``x < thr`` left, NaN right), leaves added in tree order in float32."""
+    n = X32.shape[0]
+    m = np.full(n, base_margin(base_score), np.float32)
+    rows = np.arange(n)
+    for tab in np.asarray(trees):
+        node = np.zeros(n, np.int64)
+        while True:
+            f = tab['feature'][node]
+            live = f >= 0
+            if not live.any():
+                break
+            with np.errstate(invalid='ignore'):
+                left = X32[rows[live], f[live]] < tab['thr'][node[live]]
+            node[live] = 2 * node[live] + 2 - left
+        m = (m + tab['value'][node]).astype(np.float32)
+    with np.errstate(over='ignore'):
+        return (np.float32(1.0) / (np.float32(1.0) + np.exp(-m))).astype(np.float32)
+
+
+# ----------------------------------------------------------------------------- binned data (device)
+@dataclass
+class BinnedData:
+    """The trainer's view of a feature table: the numeric features as a feature-major uint8 bin
+    matrix ``bins [F_num, ld]``, the bool features as the Arrow bitmaps ``bits [rows, words]``
+    (never expanded to bytes), every feature's cuts, and the maps between feature numbers and
+    rows of the two."""
+
+    n: int
+    ld: int
+    names: List[str]
+    cuts: List[np.ndarray]
+    bits: Any
+    bins: Any
+    bit_rows: np.ndarray
+    bit_feat: np.ndarray
+    num_feat: np.ndarray
+    fmap: np.ndarray
+    dev: Dict[str, Any]
+
+    @property
+    def n_features(self) -> int:
+        return len(self.names)
+
+    @property
+    def device(self):
+        return self.bins.device
+
+    def host_bins(self) -> np.ndarray:
+        """``[F, n]`` uint8 bins of every feature (a bool feature: its bit) on the host."""
+        out = np.zeros((self.n_features, self.n), np.uint8)
+        if len(self.num_feat):
+            out[self.num_feat] = self.bins[:, :self.n].cpu().numpy()
+        if len(self.bit_feat):
+            raw = self.bits.cpu().numpy().view(np.uint8)
+            un = np.unpackbits(raw, axis=1, bitorder='little')[:, :self.n]
+            out[self.bit_feat] = un[self.bit_rows]
+        return out
+
+
+def _ld(n: int) -> int:
+    return max(16, (n + 15) // 16 * 16)
+
+
+def _bin(names, kinds_cols, bits, f_blk, i_blk, f32: bool, n: int, cuts) -> BinnedData:
+    """kinds_cols[f] = (kind, column in its block / bitmap row)."""
+    import torch
+
+    from .batch import stream_handle
+    dev = f_blk.device
+    F = len(names)
+    cuts = check_cuts(cuts, F)
+    ld = _ld(n)
+    cut_start = np.zeros(F + 1, np.int32)
+    cut_start[1:] = np.cumsum([len(c) for c in cuts])
+    flat = np.concatenate(cuts + [np.zeros(1, np.float32)]).astype(np.float32)
+    bool_f = [f for f, (k, _) in enumerate(kinds_cols) if k == 'b']
+    num_f = [f for f, (k, _) in enumerate(kinds_cols) if k != 'b']
+    for f in bool_f:
+        if len(cuts[f]) != 1 or cuts[f][0] != np.float32(0.5):
+            raise ValueError(f'feature {f} is a bool feature: its only cut is 0.5')
+    bit_rows = np.array([kinds_cols[f][1] for f in bool_f], np.int32)
+    bit_feat = np.array(bool_f, np.int32)
+    num_feat = np.array(num_f, np.int32)
+    slots = np.array([((1 if kinds_cols[f][0] == 'f' else 2) << 24) | kinds_cols[f][1] for f in num_f], np.int32)
+    fmap = np.zeros(F, np.int32)
+    fmap[bit_feat] = bit_rows
+    fmap[num_feat] = (1 << 24) | np.arange(len(num_f), dtype=np.int32)
+    if bool_f and (bits is None or bits.dtype != torch.int64 or bits.shape[1] * 64 < n):
+        raise ValueError('the bool features must come as bitmaps (ops.features(..., bool_bits=True))')
+    t = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)  # noqa: E731
+    d = {'cut_start': t(cut_start), 'cuts': t(flat), 'bit_rows': t(bit_rows) if bool_f else None,
+         'bit_feat': t(bit_feat) if bool_f else None, 'num_feat': t(num_feat) if num_f else None,
+         'fmap': t(fmap), 'slots': t(slots) if num_f else None}
+    bins = torch.empty((max(len(num_f), 1), ld), dtype=torch.uint8, device=dev)
+    if num_f and n:
+        blk = []
+        for tns in (f_blk, i_blk):
+            b = _native.SaBlock()
+            b.data = tns.data_ptr() if tns.numel() else None
+            b.n_cols, b.tile_rows = tns.shape[1], tns.shape[2]
+            blk.append(b)
+        _native.check(_native.lib().sa_boost_bin(
+            ctypes.byref(blk[0]), ctypes.byref(blk[1]), int(f32), d['slots'].data_ptr(), d['num_feat'].data_ptr(),
+            d['cut_start'].data_ptr(), d['cuts'].data_ptr(), len(num_f), n, bins.data_ptr(), ld, stream_handle()))
+    return BinnedData(n, ld, list(names), cuts, bits if bool_f else None, bins, bit_rows, bit_feat, num_feat,
+                      fmap, d)
+
+
+def bin_blocks(blocks, cuts: Optional[Sequence[np.ndarray]] = None, rows=None) -> BinnedData:
+    """Bin device feature blocks (``ops.features(..., bool_bits=True)``; float64 / int64 or
+    float32 numeric blocks): ``sa_boost_bin`` for the numeric features, the bitmaps as they are.
+    ``cuts``: explicit cut lists (model order), default :func:`make_cuts` on ``rows``."""
+    plan = blocks.plan
+    if plan.n_bool and blocks.bool_bits is None:
+        raise ValueError('the bool features must come as bitmaps (ops.features(..., bool_bits=True))')
+    if cuts is None:
+        cuts = make_cuts(blocks, rows)
+    kc = [(kind, col) for _, kind, col in plan.order]
+    return _bin(list(plan.names), kc, blocks.bool_bits, blocks.f64_block, blocks.i64_block, blocks.num32,
+                blocks.n, cuts)
+
+
+def bin_host(X, cuts: Optional[Sequence[np.ndarray]] = None, rows=None, device=None) -> BinnedData:
+    """Upload a host frame / 2-D array -- bool columns as bitmaps, float and integer columns as
+    float64 / int64 blocks -- and bin it with the same kernel."""
+    import torch
+    names, cols = _host_columns(X)
+    n = len(cols[0]) if cols else 0
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    if cuts is None:
+        cuts = make_cuts(X, rows)
+    ld = _ld(n)
+    kinds = [_kind(c) for c in cols]
+    kc, per = [], {'b': [], 'f': [], 'i': []}
+    for k, c in zip(kinds, cols):
+        kc.append((k, len(per[k])))
+        per[k].append(c)
+    words = max(1, (n + 63) // 64)
+    hb = np.zeros((max(len(per['b']), 1), words * 8), np.uint8)
+    for r, c in enumerate(per['b']):
+        pk = np.packbits(c.astype(bool), bitorder='little')
+        hb[r, :len(pk)] = pk
+    hf = np.zeros((1, len(per['f']), ld), np.float64)
+    for r, c in enumerate(per['f']):
+        hf[0, r, :n] = c
+    hi = np.zeros((1, len(per['i']), ld), np.int64)
+    for r, c in enumerate(per['i']):
+        hi[0, r, :n] = c
+    return _bin(names, kc, torch.from_numpy(hb.view(np.int64)).to(dev), torch.from_numpy(hf).to(dev),
+                torch.from_numpy(hi).to(dev), False, n, cuts)
+
+
+# ----------------------------------------------------------------------------- single kernels
+def _stream():
+    from .batch import stream_handle
+    return stream_handle()
+
+
+def gradients(margin, y, row_mask=None):
+    """``sa_boost_grad`` on device columns: ``(gq, hq, p)`` -- int32, int32, float32."""
+    import torch
+    n = margin.numel()
+    margin = margin.to(torch.float32).contiguous()
+    y = y.view(torch.uint8) if y.dtype == torch.bool else y.to(torch.uint8)
+    gq = torch.empty(max(n, 1), dtype=torch.int32, device=margin.device)
+    hq = torch.empty_like(gq)
+    p = torch.empty(max(n, 1), dtype=torch.float32, device=margin.device)
+    _native.check(_native.lib().sa_boost_grad(margin.data_ptr(), y.contiguous().data_ptr(),
+                                              None if row_mask is None else row_mask.data_ptr(), n,
+                                              gq.data_ptr(), hq.data_ptr(), p.data_ptr(), None, _stream()))
+    return gq[:n], hq[:n], p[:n]
+
+
+def _level(n_nodes: int) -> int:
+    if n_nodes < 1 or n_nodes > _native.SA_BOOST_MAX_LEVEL_NODES or n_nodes & (n_nodes - 1):
+        raise ValueError('a level has 1, 2, 4, ... 32 nodes')
+    return n_nodes - 1
+
+
+def _pad(t, ld, dtype, fill=0):
+    import torch
+    out = torch.full((ld,), fill, dtype=dtype, device=t.device)
+    out[:t.numel()] = t.to(dtype)
+    return out
+
+
+def _hist_level(data: BinnedData, gq, hq, node, node0: int, n_nodes: int, hist, tree, add_totals: bool,
+                launch=None) -> None:
+    """Both histogram kernels of one level into the zeroed ``hist``."""
+    lib, d, F = _native.lib(), data.dev, data.n_features
+    run = launch or (lambda family, fn, *a: _native.check(fn(*a)))
+    nb = len(data.bit_feat)
+    run('hist_bits', lib.sa_boost_hist_bits, data.bits.data_ptr() if nb else None,
+        data.bits.shape[1] * 8 if nb else 0, d['bit_rows'].data_ptr() if nb else None,
+        d['bit_feat'].data_ptr() if nb else None, nb, gq.data_ptr(), hq.data_ptr(), node.data_ptr(), data.n,
+        node0, n_nodes, F, hist.data_ptr(), tree.data_ptr(), int(add_totals), _stream())
+    nn = len(data.num_feat)
+    if nn:
+        run('hist_bins', lib.sa_boost_hist_bins, data.bins.data_ptr(), data.ld, d['num_feat'].data_ptr(), nn,
+            gq.data_ptr(), hq.data_ptr(), node.data_ptr(), data.n, node0, n_nodes, F, hist.data_ptr(), _stream())
+
+
+def histograms(data: BinnedData, gq, hq, node, n_nodes: int, return_totals: bool = False):
+    """The dense ``[n_nodes, F, 256, 2]`` int64 histogram of one level: ``node`` holds every row's
+    level-local node (0 .. n_nodes-1; ``NO_NODE`` = the row takes no part)."""
+    import torch
+    node0 = _level(n_nodes)
+    dev = data.device
+    nd = node.to(torch.int64)
+    heap = torch.where(nd == NO_NODE, nd, nd + node0).to(torch.uint8)
+    heap = _pad(heap, data.ld, torch.uint8, NO_NODE)
+    gq, hq = _pad(gq, data.ld, torch.int32), _pad(hq, data.ld, torch.int32)
+    hist = torch.zeros((n_nodes, data.n_features, 256, 2), dtype=torch.int64, device=dev)
+    tree = torch.zeros((4 * n_nodes, NODE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+    _hist_level(data, gq, hq, heap, node0, n_nodes, hist, tree, True)
+    if not return_totals:
+        return hist
+    tab = tree.cpu().numpy().view(NODE_DTYPE).reshape(-1)[node0:node0 + n_nodes]
+    return hist, np.stack([tab['G'], tab['H']], 1)
+
+
+def best_splits(hist, totals, cuts: Sequence[np.ndarray], reg_lambda: float = 1.0, min_child_weight: float = 1.0,
+                gamma: float = 0.0, learning_rate: float = 0.3) -> np.ndarray:
+    """``sa_boost_split`` on a level's histograms ``[n_nodes, F, 256, 2]`` and node totals
+    ``[n_nodes, 2]``: the level's node records (:data:`NODE_DTYPE`) and, after them, their
+    children's -- ``[3 * n_nodes]`` rows: the level, then the children level in heap order."""
+    import torch
+    n_nodes, F = hist.shape[0], hist.shape[1]
+    node0 = _level(n_nodes)
+    cuts = check_cuts(cuts, F)
+    dev = hist.device
+    cut_start = np.zeros(F + 1, np.int32)
+    cut_start[1:] = np.cumsum([len(c) for c in cuts])
+    flat = np.concatenate(list(cuts) + [np.zeros(1, np.float32)]).astype(np.float32)
+    tab = np.zeros(4 * n_nodes, NODE_DTYPE)
+    tot = np.asarray(totals, np.int64).reshape(n_nodes, 2)
+    tab['G'][node0:node0 + n_nodes] = tot[:, 0]
+    tab['H'][node0:node0 + n_nodes] = tot[:, 1]
+    tab['exists'][node0:node0 + n_nodes] = 1
+    tree = torch.from_numpy(tab.view(np.uint8).copy()).to(dev)
+    cs, cf = torch.from_numpy(cut_start).to(dev), torch.from_numpy(flat).to(dev)
+    bg = torch.empty(n_nodes * F, dtype=torch.float64, device=dev)
+    bc = torch.empty(n_nodes * F, dtype=torch.int32, device=dev)
+    _native.check(_native.lib().sa_boost_split(
+        hist.contiguous().data_ptr(), cs.data_ptr(), cf.data_ptr(), F, node0, n_nodes, 0, float(reg_lambda),
+        float(min_child_weight), float(gamma), float(learning_rate), bg.data_ptr(), bc.data_ptr(),
+        tree.data_ptr(), _stream()))
+    return tree.cpu().numpy().view(NODE_DTYPE).reshape(-1)[node0:node0 + 3 * n_nodes]
+
+
+# ----------------------------------------------------------------------------- the classifier
+def check_params(params: Dict[str, Any]) -> Dict[str, Any]:
+    unknown = set(params) - set(DEFAULTS)
+    if unknown:
+        raise ValueError(f'unknown parameters {sorted(unknown)} (known: {sorted(DEFAULTS)})')
+    p = {**DEFAULTS, **params}
+    if int(p['max_depth']) != p['max_depth'] or not 1 <= int(p['max_depth']) <= MAX_DEPTH:
+        raise ValueError(f'max_depth must be in 1..{MAX_DEPTH}')
+    if int(p['n_estimators']) < 0:
+        raise ValueError('n_estimators must not be negative')
+    if not p['reg_lambda'] >= 0 or not p['min_child_weight'] >= 0:
+        raise ValueError('reg_lambda and min_child_weight must not be negative')
+    if not 0.0 < float(p['base_score']) < 1.0:
+        raise ValueError('base_score must be inside (0, 1)')
+    return p
+
+
+class DeviceGBTClassifier:
+    """Binary logistic gradient boosting trained by ``csrc/sa_boost.hip`` (scikit-learn shaped).
+
+    Parameters (xgboost's names and defaults): ``n_estimators=100, max_depth=3 (1..6),
+    learning_rate=0.3, reg_lambda=1.0, min_child_weight=1.0, gamma=0.0, base_score=0.5``.
+    ``record=True`` keeps every round's probabilities and the margin after it (``record_['p']``,
+    ``record_['margin']``, ``[n_estimators, n]`` on the device) for tests on small tables.
+    After a fit: ``trees_`` (the node tables), ``cuts_``, ``feature_names_in_``, and on the device
+    the training rows' final ``margin_`` and probabilities ``p_``."""
+
+    def __init__(self, record: bool = False, **params) -> None:
+        p = check_params(params)
+        for k, v in p.items():
+            setattr(self, k, v)
+        self.record = bool(record)
+        self._events = None
+
+    def get_params(self, deep: bool = True) -> Dict[str, Any]:
+        return {k: getattr(self, k) for k in DEFAULTS}
+
+    # ------------------------------------------------------------------ fitting
+    def _launch(self, family, fn, *args) -> None:
+        if self._events is None:
+            _native.check(fn(*args))
+            return
+        import torch
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _native.check(fn(*args))
+        e1.record()
+        self._events.append((family, e0, e1))
+
+    def fit_binned(self, data: BinnedData, y_dev, rows=None) -> 'DeviceGBTClassifier':
+        """Fit on binned data and a device label column (uint8 / bool, at least n rows).  The
+        whole fit is enqueued on the current stream -- fixed launch sequences per level and per
+        round, no host synchronisation -- and the node tables of all trees are read back once."""
+        import torch
+        lib, d, dev = _native.lib(), data.dev, data.device
+        n, ld, F = data.n, data.ld, data.n_features
+        T, D = int(self.n_estimators), int(self.max_depth)
+        M = 2 ** (D + 1) - 1
+        y = y_dev.view(torch.uint8) if y_dev.dtype == torch.bool else y_dev
+        if y.dtype != torch.uint8 or y.numel() < n or y.device != dev:
+            raise ValueError('y_dev must be a uint8 / bool device column of at least n rows')
+        y = y.contiguous()
+        mask = None
+        if rows is not None:
+            rows = torch.as_tensor(rows, device=dev)
+            mask = torch.zeros(ld, dtype=torch.uint8, device=dev)
+            if rows.dtype == torch.bool:
+                mask[:n] = rows[:n].to(torch.uint8)
+            else:
+                mask[rows.to(torch.int64)] = 1
+        margin = torch.full((ld,), float(base_margin(self.base_score)), dtype=torch.float32, device=dev)
+        gq = torch.zeros(ld, dtype=torch.int32, device=dev)
+        hq = torch.zeros(ld, dtype=torch.int32, device=dev)
+        node = torch.full((ld,), NO_NODE, dtype=torch.uint8, device=dev)
+        p = torch.empty(ld, dtype=torch.float32, device=dev)
+        P = torch.empty((T, ld), dtype=torch.float32, device=dev) if self.record else None
+        Mrec = torch.empty((T, ld), dtype=torch.float32, device=dev) if self.record else None
+        trees = torch.zeros((max(T, 1), M, NODE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        top = 2 ** (D - 1)  # nodes of the deepest level that splits
+        hist = torch.empty((top, F, 256, 2), dtype=torch.int64, device=dev)
+        bg = torch.empty(top * F, dtype=torch.float64, device=dev)
+        bc = torch.empty(top * F, dtype=torch.int32, device=dev)
+        st = _stream()
+        nb = len(data.bit_feat)
+        bits_ptr = data.bits.data_ptr() if nb else None
+        bstride = data.bits.shape[1] * 8 if nb else 0
+        mptr = None if mask is None else mask.data_ptr()
+        run = self._launch
+        for t in range(T):
+            tree = trees[t]
+            pt = P[t] if P is not None else p
+            run('grad', lib.sa_boost_grad, margin.data_ptr(), y.data_ptr(), mptr, n, gq.data_ptr(), hq.data_ptr(),
+                pt.data_ptr(), node.data_ptr(), st)
+            for level in range(D):
+                nn = 2 ** level
+                node0 = nn - 1
+                h = hist[:nn]
+                h.zero_()
+                _hist_level(data, gq, hq, node, node0, nn, h, tree, level == 0, run)
+                run('split', lib.sa_boost_split, h.data_ptr(), d['cut_start'].data_ptr(), d['cuts'].data_ptr(), F,
+                    node0, nn, 0, float(self.reg_lambda), float(self.min_child_weight), float(self.gamma),
+                    float(self.learning_rate), bg.data_ptr(), bc.data_ptr(), tree.data_ptr(), st)
+                run('advance', lib.sa_boost_advance, tree.data_ptr(), node0, nn, d['fmap'].data_ptr(), bits_ptr,
+                    bstride, data.bins.data_ptr(), ld, n, node.data_ptr(), None, st)
+            run('split', lib.sa_boost_split, None, None, None, F, 2 ** D - 1, 2 ** D, 1, float(self.reg_lambda),
+                float(self.min_child_weight), float(self.gamma), float(self.learning_rate), None, None,
+                tree.data_ptr(), st)
+            run('advance', lib.sa_boost_advance, tree.data_ptr(), 0, 1, None, None, 0, None, ld, n,
+                node.data_ptr(), margin.data_ptr(), st)
+            if Mrec is not None:
+                Mrec[t].copy_(margin)
+        run('grad', lib.sa_boost_grad, margin.data_ptr(), None, None, n, None, None, p.data_ptr(), None, st)
+        self.trees_ = trees.cpu().numpy().view(NODE_DTYPE).reshape(max(T, 1), M)[:T].copy()  # the one read-back
+        self.cuts_ = data.cuts
+        self.feature_names_in_ = np.array(data.names, dtype=object)
+        self.n_features_in_ = F
+        self.classes_ = np.array([0, 1])
+        self.margin_, self.p_ = margin[:n], p[:n]
+        self.record_ = {'p': P[:, :n], 'margin': Mrec[:, :n]} if P is not None else None
+        self._ensemble = None
+        return self
+
+    def fit_blocks(self, blocks, y_dev, rows=None, cuts=None) -> 'DeviceGBTClassifier':
+        """Fit on device feature blocks (``ops.features(..., bool_bits=True)``) and a device label
+        column.  ``rows``: the training rows (indices or a bool mask), default all; ``cuts``:
+        explicit cut lists, default :func:`make_cuts` on the training rows."""
+        if rows is not None:
+            import torch
+            rows = torch.as_tensor(rows, device=blocks.device)
+            if rows.dtype == torch.bool:
+                rows = torch.nonzero(rows[:blocks.n]).reshape(-1)
+        return self.fit_binned(bin_blocks(blocks, cuts, rows), y_dev, rows)
+
+    def fit(self, X, y, cuts=None) -> 'DeviceGBTClassifier':
+        """Fit on a host frame or 2-D array: uploaded, binned and trained by the same kernels."""
+        import torch
+        data = bin_host(X, cuts)
+        yh = np.ascontiguousarray(np.asarray(y).astype(bool).astype(np.uint8).ravel())
+        if len(yh) != data.n:
+            raise ValueError('X and y have different lengths')
+        yd = torch.zeros(data.ld, dtype=torch.uint8, device=data.device)
+        yd[:data.n] = torch.from_numpy(yh).to(data.device)
+        return self.fit_binned(data, yd)
+
+    # ------------------------------------------------------------------ use
+    def _fitted(self) -> None:
+        if not hasattr(self, 'trees_'):
+            from sklearn.exceptions import NotFittedError
+            raise NotFittedError('this DeviceGBTClassifier is not fitted yet')
+
+    def to_xgboost_json(self) -> dict:
+        self._fitted()
+        return trees_to_xgboost_json(self.trees_, list(self.feature_names_in_), float(self.base_score))
+
+    def predict_proba(self, X) -> np.ndarray:
+        """Host ``[n, 2]`` float32 probabilities of a host frame (columns matched by name) or
+        array.  The columns are uploaded as feature blocks and walked by the device predictor
+        (``TreeEnsemble.predict_blocks``): the same probabilities, bit for bit, as the device
+        ``rate`` paths give.  (:func:`predict_tables` is the same walk in numpy.)"""
+        self._fitted()
+        import torch
+        from types import SimpleNamespace
+
+        from .ops import FeatureBlocks
+        from .trees import TreeEnsemble
+        if hasattr(X, 'columns'):
+            missing = [c for c in self.feature_names_in_ if c not in X.columns]
+            if missing:
+                raise ValueError(f'{" and ".join(missing)} are not available in the features dataframe')
+            cols = [X[c].to_numpy() for c in self.feature_names_in_]
+        else:
+            X = np.asarray(X)
+            cols = [X[:, j] for j in range(X.shape[1])]
+        if len(cols) != self.n_features_in_:
+            raise ValueError(f'X has {len(cols)} features, the model {self.n_features_in_}')
+        n = len(cols[0]) if cols else 0
+        if n == 0:
+            return np.zeros((0, 2), np.float32)
+        ld = _ld(n)
+        order, per = [], {'b': [], 'f': [], 'i': []}
+        for name, c in zip(self.feature_names_in_, cols):
+            k = _kind(c)
+            order.append((str(name), k, len(per[k])))
+            per[k].append(c)
+        dts = {'b': np.uint8, 'f': np.float64, 'i': np.int64}
+        dev = torch.device('cuda', torch.cuda.current_device())
+        blk = {}
+        for k in 'bfi':
+            h = np.zeros((1, len(per[k]), ld), dts[k])
+            for r, c in enumerate(per[k]):
+                h[0, r, :n] = c
+            blk[k] = torch.from_numpy(h).to(dev)
+        plan = SimpleNamespace(order=order, names=[o[0] for o in order], n_bool=len(per['b']),
+                               n_f64=len(per['f']), n_i64=len(per['i']))
+        te = getattr(self, '_ensemble', None)
+        if te is None:
+            te = self._ensemble = TreeEnsemble.from_xgboost_json(self.to_xgboost_json())
+        p1 = te.predict_blocks(FeatureBlocks(plan, n, ld, ld, blk['b'], blk['f'], blk['i']),
+                               method='gather').cpu().numpy()
+        return np.stack([np.float32(1.0) - p1, p1], 1)
+
+    def predict(self, X) -> np.ndarray:
+        return (self.predict_proba(X)[:, 1] > 0.5).astype(np.int64)
+
+
+__all__ = ['DeviceGBTClassifier', 'BinnedData', 'NODE_DTYPE', 'make_cuts', 'cuts_from_sample', 'sample_rows',
+           'cast32', 'bin_values', 'bin_blocks', 'bin_host', 'gradients', 'histograms', 'best_splits',
+           'trees_to_xgboost_json', 'predict_tables', 'base_margin', 'check_params']

@@ -1,0 +1,584 @@
+// Reproducible histogram gradient boosting on the VAEP feature blocks (gfx950): the `fit` between
+// `compute_features` / `compute_labels` and `rate` (reference vaep/base.py:139-213), trained where
+// the features already are.  Binary logistic loss, depth-limited trees on pre-binned features,
+// xgboost's `hist` rules (float32 values, `x < threshold` goes left, missing goes right).
+//
+// The arithmetic contract (DESIGN.md §3 "Boosted-tree training", restated in numpy in
+// tests/boost_reference.py) makes the trained model the same bit for bit from run to run and for
+// any row order: gradients are quantised to int32 at scale 2^30, every histogram is an int64 sum
+// (LDS integer atomics, then 64-bit integer global atomics: integer addition commutes), a split's
+// gain is a fixed sequence of IEEE float64 operations on those sums, and the arg-max is reduced in
+// index order (no float atomics anywhere).
+//
+// Data: numeric features as a feature-major uint8 bin matrix [F_num, ld] (sa_boost_bin); bool
+// features stay the Arrow bitmaps the feature pass writes (bit i of word w = row 64w + i): a bool
+// column's histogram is "bit set" (bin 1) against "node total minus bit set" (bin 0).  A row's
+// node is its heap index in the round's complete tree (root 0, children 2k+1 / 2k+2), one byte;
+// SA_BOOST_NO_NODE marks a row that takes no part (a held-out row).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "sa_common.h"
+#include "sa_internal.h"
+
+using namespace sa;
+
+namespace {
+typedef unsigned long long u64;
+constexpr int BINS = 256;
+constexpr int NO_NODE = SA_BOOST_NO_NODE;
+constexpr int BB_THREADS = 256;                       // sa_boost_bin: 4 rows per thread
+constexpr int BB_TILE = SA_BOOST_BIN_TILE;
+constexpr int HB_THREADS = 256;                       // sa_boost_hist_bits
+constexpr int HB_TILE = SA_BOOST_BITS_TILE;           // rows per workgroup
+constexpr int HB_WORDS = HB_TILE / 64;
+constexpr int HB_ACC_BYTES = 128 * 1024;              // LDS for the (column, node) sums of one pass
+constexpr int HN_THREADS = 256;                       // sa_boost_hist_bins: 4 rows per thread and step
+constexpr int HN_TILE = SA_BOOST_BINS_TILE;
+constexpr int HN_FG = SA_BOOST_FEATURE_GROUP;
+static_assert(BB_TILE == BB_THREADS * 4 && HN_TILE == HN_THREADS * 4 && HB_TILE % 64 == 0, "tile shapes");
+static_assert(sizeof(sa_boost_node) == 48, "sa_boost_node layout");
+
+__device__ __forceinline__ void add64(int64_t* p, int64_t v) { atomicAdd(reinterpret_cast<u64*>(p), (u64)v); }
+
+// ---------------------------------------------------------------------------------------- bins
+// bin(x) = #{i : c_i <= x32}, NaN -> 255.  One workgroup per (row tile, numeric feature); the
+// feature's cut table is staged in LDS and searched by bisection; 4 rows per thread, one 4-B store.
+template <int KIND>  // 0: f64 / i64 blocks, 1: float32 blocks
+__global__ __launch_bounds__(BB_THREADS) void boost_bin_kernel(sa_block Bf, sa_block Bi, const int32_t* __restrict__ slots,
+                                                                const int32_t* __restrict__ num_feat,
+                                                                const int32_t* __restrict__ cut_start,
+                                                                const float* __restrict__ cuts, int64_t n,
+                                                                uint8_t* __restrict__ bins, int64_t ld) {
+  __shared__ float lc[BINS];
+  const int r = blockIdx.y;
+  const int f = num_feat[r];
+  const int c0 = cut_start[f];
+  int m = cut_start[f + 1] - c0;
+  m = m < 0 ? 0 : (m > SA_BOOST_MAX_CUTS ? SA_BOOST_MAX_CUTS : m);
+  for (int i = threadIdx.x; i < m; i += BB_THREADS) lc[i] = cuts[c0 + i];
+  __syncthreads();
+  const int64_t j0 = (int64_t)blockIdx.x * BB_TILE + (int64_t)threadIdx.x * 4;
+  if (j0 >= n) return;
+  const int32_t slot = slots[r];
+  const bool isf = (slot >> 24) == 1;
+  const sa_block& B = isf ? Bf : Bi;
+  const int64_t col = slot & 0xFFFFFF;
+  SA_DGUARD(col < B.n_cols, col, return);
+  uint32_t packed = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int64_t j = j0 + q;
+    if (j >= n) break;  // the padding rows of the group: bin 0
+    const int64_t t = j / B.tile_rows;
+    const int64_t at = (t * B.n_cols + col) * B.tile_rows + (j - t * B.tile_rows);
+    float x;
+    if (KIND == 1)
+      x = ((const float*)B.data)[at];
+    else if (isf)
+      x = (float)((const double*)B.data)[at];
+    else
+      x = (float)(double)((const int64_t*)B.data)[at];  // the predictor's int64 -> double -> float
+    uint32_t b;
+    if (isnan(x)) {
+      b = SA_BOOST_MISSING_BIN;
+    } else {
+      int lo = 0, hi = m;  // the first cut > x
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (lc[mid] <= x)
+          lo = mid + 1;
+        else
+          hi = mid;
+      }
+      b = (uint32_t)lo;
+    }
+    packed |= b << (8 * q);
+  }
+  *reinterpret_cast<uint32_t*>(bins + (int64_t)r * ld + j0) = packed;
+}
+
+// ---------------------------------------------------------------------------------------- gradients
+__global__ __launch_bounds__(256) void boost_grad_kernel(const float* __restrict__ margin, const uint8_t* __restrict__ y,
+                                                          const uint8_t* __restrict__ mask, int64_t n,
+                                                          int32_t* __restrict__ gq, int32_t* __restrict__ hq,
+                                                          float* __restrict__ p_out, uint8_t* __restrict__ node) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const float m = margin[j];
+  const float p = 1.0f / (1.0f + expf(-m));
+  if (p_out) p_out[j] = p;
+  if (gq) {
+    const float yy = y[j] ? 1.0f : 0.0f;
+    const float g = p - yy;
+    const float h = p * (1.0f - p);
+    gq[j] = (int32_t)rintf(g * 1073741824.0f);
+    hq[j] = (int32_t)rintf(h * 1073741824.0f);
+  }
+  if (node) node[j] = (!mask || mask[j]) ? 0 : NO_NODE;
+}
+
+// ---------------------------------------------------------------------------------------- bitmaps
+// One workgroup per tile of HB_TILE rows: the rows' gq, hq and level-local node are staged in LDS
+// once; then work item (column c, word w) -- adjacent threads take adjacent words of one column:
+// coalesced 8-B loads, and a dense column's words spread over threads -- visits its set bits only
+// and adds the row's gradients to the LDS sums of (c, node) with LDS integer atomics.  The sums
+// of `cc` columns fit LDS at a time; each pass ends with one 64-bit global atomic per non-zero sum.
+__global__ __launch_bounds__(HB_THREADS) void boost_hist_bits_kernel(
+    const u64* __restrict__ bits, int64_t wstride, const int32_t* __restrict__ bit_rows,
+    const int32_t* __restrict__ bit_feat, int n_bool, const int32_t* __restrict__ gq, const int32_t* __restrict__ hq,
+    const uint8_t* __restrict__ node, int64_t n, int node0, int n_nodes, int F, int cc, int64_t* __restrict__ hist,
+    sa_boost_node* __restrict__ tree, int add_totals) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char hb_lds[];
+  u64* acc = reinterpret_cast<u64*>(hb_lds);                                // [cc][n_nodes][2]
+  int32_t* sg = reinterpret_cast<int32_t*>(hb_lds + (size_t)cc * n_nodes * 16);  // [HB_TILE]
+  int32_t* sh = sg + HB_TILE;
+  uint8_t* sn = reinterpret_cast<uint8_t*>(sh + HB_TILE);
+  __shared__ u64 ltot[2 * SA_BOOST_MAX_LEVEL_NODES];
+  const int tid = threadIdx.x;
+  const int64_t R0 = (int64_t)blockIdx.x * HB_TILE;
+  const int nacc = cc * n_nodes * 2;
+  for (int i = tid; i < nacc; i += HB_THREADS) acc[i] = 0;
+  if (tid < 2 * SA_BOOST_MAX_LEVEL_NODES) ltot[tid] = 0;
+  for (int i = tid; i < HB_TILE; i += HB_THREADS) {
+    const int64_t r = R0 + i;
+    int k = NO_NODE;
+    int32_t g = 0, h = 0;
+    if (r < n) {
+      const int nd = (int)node[r] - node0;
+      if (nd >= 0 && nd < n_nodes && node[r] != NO_NODE) {
+        k = nd;
+        g = gq[r];
+        h = hq[r];
+      }
+    }
+    sn[i] = (uint8_t)k;
+    sg[i] = g;
+    sh[i] = h;
+  }
+  __syncthreads();
+  if (add_totals) {  // the nodes' totals: this thread's rows, then one global atomic per node
+    for (int i = tid; i < HB_TILE; i += HB_THREADS) {
+      const int k = sn[i];
+      if (k == NO_NODE) continue;
+      if (sg[i]) atomicAdd(&ltot[2 * k], (u64)(int64_t)sg[i]);
+      if (sh[i]) atomicAdd(&ltot[2 * k + 1], (u64)(int64_t)sh[i]);
+    }
+    __syncthreads();
+    if (tid < 2 * n_nodes && ltot[tid]) {
+      sa_boost_node* t = tree + node0 + (tid >> 1);
+      add64((tid & 1) ? &t->H : &t->G, (int64_t)ltot[tid]);
+    }
+  }
+  const int64_t n_words = (n + 63) / 64;
+  for (int c0 = 0; c0 < n_bool; c0 += cc) {
+    const int ncol = n_bool - c0 < cc ? n_bool - c0 : cc;
+    for (int it = tid; it < ncol * HB_WORDS; it += HB_THREADS) {
+      const int c = it / HB_WORDS, w = it - c * HB_WORDS;
+      const int64_t gw = R0 / 64 + w;
+      if (gw >= n_words) continue;
+      u64 word = bits[(int64_t)bit_rows[c0 + c] * wstride + gw];
+      const int64_t rb = gw * 64;
+      if (rb + 64 > n) word &= (1ull << (n - rb)) - 1;  // rows >= n never count
+      u64* A = acc + (size_t)c * n_nodes * 2;
+      while (word) {
+        const int b = __builtin_ctzll(word);
+        word &= word - 1;
+        const int i = w * 64 + b;
+        const int k = sn[i];
+        if (k == NO_NODE) continue;
+        if (sg[i]) atomicAdd(&A[2 * k], (u64)(int64_t)sg[i]);
+        if (sh[i]) atomicAdd(&A[2 * k + 1], (u64)(int64_t)sh[i]);
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < ncol * n_nodes * 2; i += HB_THREADS) {
+      const u64 v = acc[i];
+      if (!v) continue;
+      acc[i] = 0;
+      const int c = i / (n_nodes * 2), rem = i - c * n_nodes * 2;
+      const int k = rem >> 1, f = bit_feat[c0 + c];
+      SA_DGUARD(f >= 0 && f < F, f, continue);
+      add64(hist + (((int64_t)k * F + f) * BINS + 1) * 2 + (rem & 1), (int64_t)v);
+    }
+    __syncthreads();
+  }
+}
+
+// bin 0 of every bool column = the node's total minus bin 1 (after the sums above are complete)
+__global__ __launch_bounds__(256) void boost_bits_fill_kernel(const int32_t* __restrict__ bit_feat, int n_bool,
+                                                               int node0, int n_nodes, int F, int64_t* __restrict__ hist,
+                                                               const sa_boost_node* __restrict__ tree) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_bool * n_nodes) return;
+  const int k = i / n_bool, f = bit_feat[i - k * n_bool];
+  SA_DGUARD(f >= 0 && f < F, f, return);
+  int64_t* h = hist + ((int64_t)k * F + f) * BINS * 2;
+  h[0] = tree[node0 + k].G - h[2];
+  h[1] = tree[node0 + k].H - h[3];
+}
+
+// ---------------------------------------------------------------------------------------- bins
+// Workgroup (x, y): feature group y (fg features), row steps x, x + gridDim.x, ...; an int64
+// histogram [fg][n_nodes][256][2] in LDS, filled with LDS integer atomics from coalesced 4-B
+// reads of 4 rows' bins, flushed once at the end with 64-bit global atomics (zero entries skipped).
+__global__ __launch_bounds__(HN_THREADS) void boost_hist_bins_kernel(
+    const uint8_t* __restrict__ bins, int64_t ld, const int32_t* __restrict__ num_feat, int n_num,
+    const int32_t* __restrict__ gq, const int32_t* __restrict__ hq, const uint8_t* __restrict__ node, int64_t n,
+    int node0, int n_nodes, int F, int fg, int64_t* __restrict__ hist) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char hn_lds[];
+  u64* H = reinterpret_cast<u64*>(hn_lds);  // [fg][n_nodes][256][2]
+  const int tid = threadIdx.x;
+  const int r0 = blockIdx.y * fg;
+  const int nf = n_num - r0 < fg ? n_num - r0 : fg;
+  const int nh = nf * n_nodes * BINS * 2;
+  for (int i = tid; i < nh; i += HN_THREADS) H[i] = 0;
+  __syncthreads();
+  const int64_t steps = (n + HN_TILE - 1) / HN_TILE;
+  for (int64_t s = blockIdx.x; s < steps; s += gridDim.x) {
+    const int64_t j0 = s * HN_TILE + (int64_t)tid * 4;
+    if (j0 >= n) continue;
+    const uint32_t nd4 = *reinterpret_cast<const uint32_t*>(node + j0);
+    int k[4];
+    int32_t g[4], h[4];
+    bool any = false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int raw = (int)((nd4 >> (8 * q)) & 0xFF);
+      const int nd = raw - node0;
+      const bool in = j0 + q < n && raw != NO_NODE && nd >= 0 && nd < n_nodes;
+      k[q] = in ? nd : -1;
+      g[q] = in ? gq[j0 + q] : 0;
+      h[q] = in ? hq[j0 + q] : 0;
+      any |= in;
+    }
+    if (!any) continue;
+    for (int fi = 0; fi < nf; ++fi) {
+      const uint32_t b4 = *reinterpret_cast<const uint32_t*>(bins + (int64_t)(r0 + fi) * ld + j0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (k[q] < 0) continue;
+        u64* e = H + ((size_t)(fi * n_nodes + k[q]) * BINS + ((b4 >> (8 * q)) & 0xFF)) * 2;
+        if (g[q]) atomicAdd(e, (u64)(int64_t)g[q]);
+        if (h[q]) atomicAdd(e + 1, (u64)(int64_t)h[q]);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < nh; i += HN_THREADS) {
+    const u64 v = H[i];
+    if (!v) continue;
+    const int fi = i / (n_nodes * BINS * 2), rem = i - fi * n_nodes * BINS * 2;
+    const int k = rem / (BINS * 2), e = rem - k * BINS * 2;
+    const int f = num_feat[r0 + fi];
+    SA_DGUARD(f >= 0 && f < F, f, continue);
+    add64(hist + ((int64_t)k * F + f) * BINS * 2 + e, (int64_t)v);
+  }
+}
+
+// ---------------------------------------------------------------------------------------- splits
+__device__ __forceinline__ double split_gain(double GL, double HL, double GR, double HR, double G, double H,
+                                             double lambda) {
+  return ((GL * GL) / (HL + lambda) + (GR * GR) / (HR + lambda)) - (G * G) / (H + lambda);
+}
+
+// a candidate (gain, index) beats another on a larger gain, then on the lower index
+__device__ __forceinline__ bool better(double ga, int ia, double gb, int ib) {
+  return ga > gb || (ga == gb && ia < ib);
+}
+
+// One workgroup per (node, feature): the inclusive scan over the feature's bins, the float64 gain
+// of every cut and the best cut (largest gain, then the lowest cut) -> best_gain / best_cut
+// (-inf / -1 when no cut is valid).
+__global__ __launch_bounds__(BINS) void boost_scan_kernel(const int64_t* __restrict__ hist,
+                                                           const int32_t* __restrict__ cut_start, int F, int node0,
+                                                           double lambda, double mcw,
+                                                           const sa_boost_node* __restrict__ tree,
+                                                           double* __restrict__ best_gain,
+                                                           int32_t* __restrict__ best_cut) {
+  __shared__ int64_t sg[2][BINS], sh[2][BINS];
+  __shared__ double rg[BINS];
+  __shared__ int ri[BINS];
+  const int k = blockIdx.y, f = blockIdx.x, i = threadIdx.x;
+  const sa_boost_node nd = tree[node0 + k];
+  if (!nd.exists && node0 != 0) {  // (the root always exists)
+    if (i == 0) {
+      best_gain[(int64_t)k * F + f] = -INFINITY;
+      best_cut[(int64_t)k * F + f] = -1;
+    }
+    return;
+  }
+  int m = cut_start[f + 1] - cut_start[f];
+  m = m < 0 ? 0 : (m > SA_BOOST_MAX_CUTS ? SA_BOOST_MAX_CUTS : m);
+  const int64_t* h = hist + ((int64_t)k * F + f) * BINS * 2;
+  sg[0][i] = h[2 * i];
+  sh[0][i] = h[2 * i + 1];
+  __syncthreads();
+  int cur = 0;
+  for (int d = 1; d < BINS; d <<= 1) {  // integer sums: any order gives the same prefix
+    sg[cur ^ 1][i] = sg[cur][i] + (i >= d ? sg[cur][i - d] : 0);
+    sh[cur ^ 1][i] = sh[cur][i] + (i >= d ? sh[cur][i - d] : 0);
+    cur ^= 1;
+    __syncthreads();
+  }
+  double gain = -INFINITY;
+  int idx = -1;
+  if (i < m) {
+    const int64_t gl = sg[cur][i], hl = sh[cur][i];
+    const double s = 9.313225746154785e-10;  // 2^-30
+    const double G = (double)nd.G * s, H = (double)nd.H * s;
+    const double GL = (double)gl * s, HL = (double)hl * s;
+    const double GR = (double)(nd.G - gl) * s, HR = (double)(nd.H - hl) * s;
+    if (HL >= mcw && HR >= mcw) {
+      const double v = split_gain(GL, HL, GR, HR, G, H, lambda);
+      if (!isnan(v)) {
+        gain = v;
+        idx = i;
+      }
+    }
+  }
+  rg[i] = gain;
+  ri[i] = idx;
+  __syncthreads();
+  for (int d = BINS / 2; d > 0; d >>= 1) {
+    if (i < d && ri[i + d] >= 0 && (ri[i] < 0 || better(rg[i + d], ri[i + d], rg[i], ri[i]))) {
+      rg[i] = rg[i + d];
+      ri[i] = ri[i + d];
+    }
+    __syncthreads();
+  }
+  if (i == 0) {
+    best_gain[(int64_t)k * F + f] = rg[0];
+    best_cut[(int64_t)k * F + f] = ri[0];
+  }
+}
+
+// One workgroup per node: the best feature (largest gain, then the lowest feature index), the
+// node's leaf value, and -- when it splits -- its record and its children's totals.
+__global__ __launch_bounds__(256) void boost_decide_kernel(const int64_t* __restrict__ hist,
+                                                            const int32_t* __restrict__ cut_start,
+                                                            const float* __restrict__ cuts, int F, int node0,
+                                                            int leaf_only, double lambda, double gamma, double eta,
+                                                            const double* __restrict__ best_gain,
+                                                            const int32_t* __restrict__ best_cut,
+                                                            sa_boost_node* __restrict__ tree) {
+  __shared__ double rg[256];
+  __shared__ int rf[256];
+  const int k = blockIdx.x, tid = threadIdx.x;
+  sa_boost_node* nd = tree + node0 + k;
+  if (!nd->exists && node0 != 0) return;  // (the root always exists)
+  double gain = -INFINITY;
+  int bf = -1;
+  if (!leaf_only)
+    for (int f = tid; f < F; f += 256) {  // ascending f: a later equal gain does not replace
+      const double v = best_gain[(int64_t)k * F + f];
+      if (best_cut[(int64_t)k * F + f] >= 0 && (bf < 0 || v > gain)) {
+        gain = v;
+        bf = f;
+      }
+    }
+  rg[tid] = gain;
+  rf[tid] = bf;
+  __syncthreads();
+  for (int d = 128; d > 0; d >>= 1) {
+    if (tid < d && rf[tid + d] >= 0 && (rf[tid] < 0 || better(rg[tid + d], rf[tid + d], rg[tid], rf[tid]))) {
+      rg[tid] = rg[tid + d];
+      rf[tid] = rf[tid + d];
+    }
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  const double s = 9.313225746154785e-10;  // 2^-30
+  const double G = (double)nd->G * s, H = (double)nd->H * s;
+  nd->value = (float)(eta * (-(G / (H + lambda))));
+  nd->exists = 1;
+  nd->feature = -1;
+  nd->cut = -1;
+  nd->thr = 0.0f;
+  nd->gain = 0.0;
+  const int f = rf[0];
+  if (leaf_only || f < 0 || !(rg[0] > gamma)) return;
+  const int cut = best_cut[(int64_t)k * F + f];
+  const int64_t* h = hist + ((int64_t)k * F + f) * BINS * 2;
+  int64_t gl = 0, hl = 0;
+  for (int b = 0; b <= cut; ++b) {
+    gl += h[2 * b];
+    hl += h[2 * b + 1];
+  }
+  nd->feature = f;
+  nd->cut = cut;
+  nd->thr = cuts[cut_start[f] + cut];
+  nd->gain = rg[0];
+  sa_boost_node* L = tree + 2 * (node0 + k) + 1;
+  L[0].G = gl;
+  L[0].H = hl;
+  L[0].exists = 1;
+  L[0].feature = -1;
+  L[1].G = nd->G - gl;
+  L[1].H = nd->H - hl;
+  L[1].exists = 1;
+  L[1].feature = -1;
+}
+
+// ---------------------------------------------------------------------------------------- advance
+// ADD = false: a row in a split node of the level moves to the child its bitmap bit or bin picks
+// (bit set / bin > cut: right).  ADD = true: every row's margin gains its node's leaf value.
+template <bool ADD>
+__global__ __launch_bounds__(256) void boost_advance_kernel(const sa_boost_node* __restrict__ tree, int node0,
+                                                             int n_nodes, const int32_t* __restrict__ fmap,
+                                                             const u64* __restrict__ bits, int64_t wstride,
+                                                             const uint8_t* __restrict__ bins, int64_t ld, int64_t n,
+                                                             uint8_t* __restrict__ node, float* __restrict__ margin) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int raw = node[j];
+  if (raw == NO_NODE) return;
+  if (ADD) {
+    margin[j] = margin[j] + tree[raw].value;
+    return;
+  }
+  const int nd = raw - node0;
+  if (nd < 0 || nd >= n_nodes) return;
+  const int f = tree[raw].feature;
+  if (f < 0) return;
+  const int32_t slot = fmap[f];
+  const int64_t row = slot & 0xFFFFFF;
+  bool right;
+  if ((slot >> 24) == 0)
+    right = (bits[row * wstride + (j >> 6)] >> (j & 63)) & 1;
+  else
+    right = (int)bins[row * ld + j] > tree[raw].cut;
+  node[j] = (uint8_t)(2 * raw + 1 + (right ? 1 : 0));
+}
+
+// level-local node range [node0, node0 + n_nodes): one whole level of the heap, at most 32 nodes
+bool level_ok(int node0, int n_nodes) {
+  return n_nodes >= 1 && n_nodes <= SA_BOOST_MAX_LEVEL_NODES && (n_nodes & (n_nodes - 1)) == 0 &&
+         node0 == n_nodes - 1;
+}
+}  // namespace
+
+extern "C" int sa_boost_bin(const sa_block* f64_blk, const sa_block* i64_blk, int32_t f32, const int32_t* slots,
+                            const int32_t* num_feat, const int32_t* cut_start, const float* cuts, int32_t n_num,
+                            int64_t n, uint8_t* bins, int64_t ld, void* stream) {
+  if (n < 0 || n_num < 0 || ld < n || ld % 4 != 0) return fail(SA_EINVAL, "sa_boost_bin: bad sizes");
+  if (n_num > 0 && (!slots || !num_feat || !cut_start || !cuts || !bins || ((uintptr_t)bins & 3u)))
+    return fail(SA_EINVAL, "sa_boost_bin: null or misaligned pointer");
+  sa_block z{nullptr, 0, 0, 16};
+  const sa_block Bf = f64_blk ? *f64_blk : z, Bi = i64_blk ? *i64_blk : z;
+  if (Bf.tile_rows < 1 || Bi.tile_rows < 1) return fail(SA_EINVAL, "sa_boost_bin: bad tile");
+  if (n == 0 || n_num == 0) return SA_OK;
+  const dim3 grid((unsigned)((n + BB_TILE - 1) / BB_TILE), (unsigned)n_num);
+  if (f32)
+    hipLaunchKernelGGL((boost_bin_kernel<1>), grid, dim3(BB_THREADS), 0, (hipStream_t)stream, Bf, Bi, slots, num_feat,
+                       cut_start, cuts, n, bins, ld);
+  else
+    hipLaunchKernelGGL((boost_bin_kernel<0>), grid, dim3(BB_THREADS), 0, (hipStream_t)stream, Bf, Bi, slots, num_feat,
+                       cut_start, cuts, n, bins, ld);
+  return check_launch("boost_bin_kernel");
+}
+
+extern "C" int sa_boost_grad(const float* margin, const uint8_t* y, const uint8_t* row_mask, int64_t n, int32_t* gq,
+                             int32_t* hq, float* p, uint8_t* node, void* stream) {
+  if (n < 0 || !margin || (gq && (!hq || !y)) || (!gq && hq))
+    return fail(SA_EINVAL, "sa_boost_grad: bad arguments");
+  if (n == 0) return SA_OK;
+  hipLaunchKernelGGL(boost_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, margin,
+                     y, row_mask, n, gq, hq, p, node);
+  return check_launch("boost_grad_kernel");
+}
+
+extern "C" int sa_boost_hist_bits(const uint64_t* bits, int64_t bits_stride, const int32_t* bit_rows,
+                                  const int32_t* bit_feat, int32_t n_bool, const int32_t* gq, const int32_t* hq,
+                                  const uint8_t* node, int64_t n, int32_t node0, int32_t n_nodes, int32_t n_features,
+                                  int64_t* hist, sa_boost_node* tree, int32_t add_totals, void* stream) {
+  if (n < 0 || n_bool < 0 || n_features < 1 || !level_ok(node0, n_nodes))
+    return fail(SA_EINVAL, "sa_boost_hist_bits: bad sizes");
+  if (!gq || !hq || !node || !hist || !tree) return fail(SA_EINVAL, "sa_boost_hist_bits: null pointer");
+  if (n_bool > 0 && (!bits || !bit_rows || !bit_feat || bits_stride % 8 || bits_stride < 8 * ((n + 63) / 64) ||
+                     ((uintptr_t)bits & 7u)))
+    return fail(SA_EINVAL, "sa_boost_hist_bits: bad bitmaps");
+  if (n == 0) return SA_OK;
+  int cc = HB_ACC_BYTES / (n_nodes * 16);
+  if (cc > n_bool) cc = n_bool;
+  if (cc < 1) cc = 1;
+  const size_t lds = (size_t)cc * n_nodes * 16 + (size_t)HB_TILE * 9;
+  hipLaunchKernelGGL(boost_hist_bits_kernel, dim3((unsigned)((n + HB_TILE - 1) / HB_TILE)), dim3(HB_THREADS), lds,
+                     (hipStream_t)stream, (const u64*)bits, bits_stride / 8, bit_rows, bit_feat, n_bool, gq, hq, node,
+                     n, node0, n_nodes, n_features, cc, hist, tree, add_totals);
+  if (int rc = check_launch("boost_hist_bits_kernel")) return rc;
+  if (n_bool == 0) return SA_OK;
+  const int items = n_bool * n_nodes;
+  hipLaunchKernelGGL(boost_bits_fill_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     bit_feat, n_bool, node0, n_nodes, n_features, hist, tree);
+  return check_launch("boost_bits_fill_kernel");
+}
+
+extern "C" int sa_boost_hist_bins(const uint8_t* bins, int64_t ld, const int32_t* num_feat, int32_t n_num,
+                                  const int32_t* gq, const int32_t* hq, const uint8_t* node, int64_t n, int32_t node0,
+                                  int32_t n_nodes, int32_t n_features, int64_t* hist, void* stream) {
+  if (n < 0 || n_num < 0 || n_features < 1 || ld < n || ld % 4 != 0 || !level_ok(node0, n_nodes))
+    return fail(SA_EINVAL, "sa_boost_hist_bins: bad sizes");
+  if (!gq || !hq || !node || !hist || ((uintptr_t)node & 3u))
+    return fail(SA_EINVAL, "sa_boost_hist_bins: null or misaligned pointer");
+  if (n_num > 0 && (!bins || !num_feat || ((uintptr_t)bins & 3u)))
+    return fail(SA_EINVAL, "sa_boost_hist_bins: null or misaligned bins");
+  if (n == 0 || n_num == 0) return SA_OK;
+  int fg = HN_FG;
+  while (fg > 1 && fg * n_nodes > 32) fg >>= 1;  // [fg][n_nodes][256][2] int64 <= 128 KB of LDS
+  const size_t lds = (size_t)fg * n_nodes * BINS * 16;
+  const int64_t steps = (n + HN_TILE - 1) / HN_TILE;
+  const int groups = (n_num + fg - 1) / fg;
+  int64_t gx = (int64_t)device_cus(current_device()) * 4 / groups;
+  if (gx < 8) gx = 8;
+  if (gx > steps) gx = steps;
+  hipLaunchKernelGGL(boost_hist_bins_kernel, dim3((unsigned)gx, (unsigned)groups), dim3(HN_THREADS), lds,
+                     (hipStream_t)stream, bins, ld, num_feat, n_num, gq, hq, node, n, node0, n_nodes, n_features, fg,
+                     hist);
+  return check_launch("boost_hist_bins_kernel");
+}
+
+extern "C" int sa_boost_split(const int64_t* hist, const int32_t* cut_start, const float* cuts, int32_t n_features,
+                              int32_t node0, int32_t n_nodes, int32_t leaf_only, double reg_lambda,
+                              double min_child_weight, double gamma, double learning_rate, double* best_gain,
+                              int32_t* best_cut, sa_boost_node* tree, void* stream) {
+  if (n_features < 1 || n_nodes < 1 || n_nodes > 2 * SA_BOOST_MAX_LEVEL_NODES || (n_nodes & (n_nodes - 1)) ||
+      node0 != n_nodes - 1)
+    return fail(SA_EINVAL, "sa_boost_split: bad sizes");
+  if (!tree || (!leaf_only && (!hist || !cut_start || !cuts || !best_gain || !best_cut)))
+    return fail(SA_EINVAL, "sa_boost_split: null pointer");
+  if (!leaf_only && n_nodes > SA_BOOST_MAX_LEVEL_NODES) return fail(SA_EINVAL, "sa_boost_split: level too deep");
+  if (!(reg_lambda >= 0.0) || !(min_child_weight >= 0.0) || std::isnan(gamma) || std::isnan(learning_rate))
+    return fail(SA_EINVAL, "sa_boost_split: bad parameters");
+  hipStream_t st = (hipStream_t)stream;
+  if (!leaf_only) {
+    hipLaunchKernelGGL(boost_scan_kernel, dim3((unsigned)n_features, (unsigned)n_nodes), dim3(BINS), 0, st, hist,
+                       cut_start, n_features, node0, reg_lambda, min_child_weight, tree, best_gain, best_cut);
+    if (int rc = check_launch("boost_scan_kernel")) return rc;
+  }
+  hipLaunchKernelGGL(boost_decide_kernel, dim3((unsigned)n_nodes), dim3(256), 0, st, hist, cut_start, cuts, n_features,
+                     node0, leaf_only, reg_lambda, gamma, learning_rate, best_gain, best_cut, tree);
+  return check_launch("boost_decide_kernel");
+}
+
+extern "C" int sa_boost_advance(const sa_boost_node* tree, int32_t node0, int32_t n_nodes, const int32_t* fmap,
+                                const uint64_t* bits, int64_t bits_stride, const uint8_t* bins, int64_t ld, int64_t n,
+                                uint8_t* node, float* margin, void* stream) {
+  if (n < 0 || !tree || !node) return fail(SA_EINVAL, "sa_boost_advance: bad arguments");
+  if (!margin) {
+    if (!level_ok(node0, n_nodes) || !fmap) return fail(SA_EINVAL, "sa_boost_advance: bad level");
+    if (bits && (bits_stride % 8 || bits_stride < 8 * ((n + 63) / 64) || ((uintptr_t)bits & 7u)))
+      return fail(SA_EINVAL, "sa_boost_advance: bad bitmaps");
+    if (bins && ld < n) return fail(SA_EINVAL, "sa_boost_advance: bad bins");
+  }
+  if (n == 0) return SA_OK;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  if (margin)
+    hipLaunchKernelGGL((boost_advance_kernel<true>), grid, block, 0, (hipStream_t)stream, tree, node0, n_nodes, fmap,
+                       (const u64*)bits, bits_stride / 8, bins, ld, n, node, margin);
+  else
+    hipLaunchKernelGGL((boost_advance_kernel<false>), grid, block, 0, (hipStream_t)stream, tree, node0, n_nodes, fmap,
+                       (const u64*)bits, bits_stride / 8, bins, ld, n, node, margin);
+  return check_launch("boost_advance_kernel");
+}

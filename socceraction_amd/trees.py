@@ -136,7 +136,9 @@ class TreeEnsemble:
         try:
             if type(model).__name__ == 'HistGradientBoostingClassifier':
                 return cls.from_sklearn(model)
-            if hasattr(model, 'get_booster'):          # xgboost.XGBClassifier
+            if hasattr(model, 'to_xgboost_json'):      # boost.DeviceGBTClassifier (fitted)
+                return cls.from_xgboost_json(model.to_xgboost_json())
+            if hasattr(model, 'get_booster'):         # xgboost.XGBClassifier
                 raw = json.loads(bytes(model.get_booster().save_raw('json')).decode())
                 return cls.from_xgboost_json(raw, xgb_classifier_iterations(model, raw))
             if hasattr(model, 'save_raw'):             # xgboost.Booster

@@ -6,7 +6,9 @@ actions are flattened once into HBM columns and every known transformer in ``xfn
 computed by ``sa_vaep_features`` (windowed game states + left-to-right flip in-kernel).
 The ``*_batch`` variants value many games per launch (one segment per game), which is
 the throughput path the benchmark measures. ``fit`` / ``score`` delegate to the same
-gradient-boosting learners as the reference (host-side, out of the kernel path).
+gradient-boosting learners as the reference (host-side, out of the kernel path);
+``fit(..., learner='device')`` and ``fit_batch`` train both learners on the device instead
+(:mod:`socceraction_amd.boost`).
 """
 from __future__ import annotations
 
@@ -207,6 +209,8 @@ class VAEP:
         if not set(cols).issubset(set(X.columns)):
             missing_cols = ' and '.join(set(cols).difference(X.columns))
             raise ValueError(f'{missing_cols} are not available in the features dataframe')
+        if learner == 'device':
+            return self._fit_device(X[cols], y, train_idx, val_idx, val_size, tree_params)
         X_train, y_train = X.iloc[train_idx][cols], y.iloc[train_idx]
         X_val, y_val = X.iloc[val_idx][cols], y.iloc[val_idx]
         for col in list(y.columns):
@@ -222,6 +226,68 @@ class VAEP:
                                                         tree_params, fit_params)
             else:
                 raise ValueError(f'A {learner} learner is not supported')
+        return self
+
+    # ---------------------------------------------------------------- learning (device)
+    def _fit_device(self, X, y, train_idx, val_idx, val_size, tree_params) -> 'VAEP':
+        """``fit(..., learner='device')``: one :class:`socceraction_amd.boost.DeviceGBTClassifier`
+        per label column on the reference's split of the rows.  The frame is uploaded and binned
+        once (cuts from the training rows); no early stopping: the held-out rows are scored once
+        after training (``self.device_eval_[col]``, :func:`socceraction_amd.metrics.binary_scores`)."""
+        from .. import boost, metrics
+        import torch
+        params = boost.check_params(dict(tree_params or {}))  # before any device call
+        train_idx = np.sort(np.asarray(train_idx, np.int64))
+        data = boost.bin_host(X, rows=train_idx)
+        rows = torch.from_numpy(train_idx).to(data.device)
+        self.device_eval_: Dict[str, Dict[str, float]] = {}
+        for col in list(y.columns):
+            yh = np.zeros(data.ld, np.uint8)
+            yh[:data.n] = y[col].to_numpy().astype(bool)
+            clf = boost.DeviceGBTClassifier(**params).fit_binned(data, torch.from_numpy(yh).to(data.device), rows)
+            self.__models[col] = clf
+            if val_size > 0 and len(val_idx):
+                p = clf.predict_proba(X.iloc[val_idx])[:, 1]
+                self.device_eval_[col] = metrics.binary_scores(y[col].to_numpy().astype(bool)[val_idx], p)
+        return self
+
+    def fit_batch(self, games: pd.DataFrame, actions: pd.DataFrame, learner: str = 'device',
+                  val_size: float = 0.0, nr_actions: int = 10,
+                  tree_params: Optional[Dict[str, Any]] = None) -> 'VAEP':
+        """Fit both learners on many games (contiguous per game) without the feature frame: one
+        ``ActionBatch``, the features as bitmaps plus numeric blocks and the labels all on the
+        device; only the cut sample and the finished trees cross the link.  ``val_size``: the
+        share of rows (the reference's random split) held out and scored once after training
+        into ``self.device_eval_``.  Built-in transformers only."""
+        from .. import boost, metrics
+        from ..trees import TreeEnsemble
+        import torch
+        if learner != 'device':
+            raise ValueError(f'A {learner} learner is not supported by fit_batch')
+        params = boost.check_params(dict(tree_params or {}))  # before any device call
+        known, unknown = self._split_xfns()
+        if unknown:
+            raise ValueError('fit_batch needs built-in feature transformers')
+        home_of = games.set_index('game_id')['home_team_id']
+        ab = ActionBatch.from_frame(actions, atomic=self._atomic, home_team_id=home_of, segments='game')
+        fb = ops.features(ab, known, self.nb_prev_actions, bool_bits=True)
+        lb = ops.labels(ab, int(nr_actions))
+        rows = val_rows = None
+        if val_size > 0:
+            idx = np.random.permutation(ab.n)
+            cut = math.floor(ab.n * (1 - val_size))
+            rows = torch.from_numpy(np.sort(idx[:cut])).to(ab.device)
+            val_rows = torch.from_numpy(np.sort(idx[cut + 1:])).to(ab.device)
+        data = boost.bin_blocks(fb, rows=rows)
+        self.device_eval_ = {}
+        for col in ('scores', 'concedes'):
+            ycol = getattr(lb, col)
+            clf = boost.DeviceGBTClassifier(**params).fit_binned(data, ycol, rows)
+            self.__models[col] = clf
+            if val_rows is not None and val_rows.numel():
+                p = TreeEnsemble.from_model(clf).predict_blocks(fb)
+                self.device_eval_[col] = metrics.binary_scores(ycol[:ab.n][val_rows].contiguous(),
+                                                               p[val_rows].contiguous())
         return self
 
     def _fit_xgboost(self, X, y, eval_set=None, tree_params=None, fit_params=None):
