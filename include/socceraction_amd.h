@@ -820,7 +820,18 @@ int sa_auc_count(const uint8_t* y, const void* p, int32_t f32, int64_t n, const 
  *   best_cut [n_nodes * n_features]: scratch.  leaf_only allows n_nodes up to 64.
  * sa_boost_advance: margin == NULL: every row in a split node of the level moves to a child
  *   (bit set, or bin > cut: the right one); fmap[f] = bitmap row, or 1 << 24 | bin-matrix row.
- *   margin != NULL: margin[j] += tree[node[j]].value for every participating row. */
+ *   margin != NULL: margin[j] += tree[node[j]].value for every participating row.
+ * sa_boost_apply: one finished tree (max_depth in 1..SA_BOOST_MAX_DEPTH, its 2^(max_depth+1) - 1
+ *   records) applied to a list of rows, for per-round held-out evaluation and for replaying
+ *   kept trees: list entry i is row rows[i] of the binned table (rows == NULL: row i), n_rows
+ *   entries, any order, repeats allowed.  From the root, at most max_depth steps, ending at the
+ *   first node whose feature < 0: bit set, or bin > cut (so the missing bin), goes right -- the
+ *   predictor's walk.  Then margin[i] += value of that node in float32 and, with p, p[i] = 1 /
+ *   (1 + expf(-margin[i])).  margin and p are COMPACT columns of n_rows entries, independent of
+ *   the trainer's.  bits or bins may be NULL when the table has no feature of that kind; an
+ *   entry whose row is outside [0, n) is never dereferenced and keeps its margin and p.  One
+ *   thread per entry, 256 per workgroup; the records' walk fields are staged in LDS once per
+ *   workgroup (12 bytes per node), the bitmap and bin reads are gathers by row. */
 #define SA_BOOST_MAX_DEPTH 6
 #define SA_BOOST_MAX_CUTS 254
 #define SA_BOOST_MISSING_BIN 255
@@ -860,6 +871,11 @@ int sa_boost_split(const int64_t* hist, const int32_t* cut_start, const float* c
 int sa_boost_advance(const sa_boost_node* tree, int32_t node0, int32_t n_nodes, const int32_t* fmap,
                      const uint64_t* bits, int64_t bits_stride, const uint8_t* bins, int64_t ld,
                      int64_t n, uint8_t* node, float* margin, void* stream);
+int sa_boost_apply(const sa_boost_node* tree, int32_t max_depth, const int32_t* fmap,
+                   const uint64_t* bits, int64_t bits_stride, const uint8_t* bins, int64_t ld,
+                   const int64_t* rows /* NULL: rows 0..n_rows-1 */, int64_t n_rows, int64_t n,
+                   float* margin /* [n_rows], updated in place */, float* p /* [n_rows] or NULL */,
+                   void* stream);
 
 /* ---- runtime ------------------------------------------------------------------ */
 int sa_abi_version(void);

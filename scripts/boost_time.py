@@ -11,17 +11,27 @@ median launch); the wall clock is the median of `--reps` uninstrumented ``fit_ba
 histogram kernels are also held against the bytes a level has to read (bitmaps n_bool / 8, bins
 F_num, gradients and node 9 bytes per row).
 
-    python scripts/boost_time.py [--games 1000] [--reps 3] [--sklearn] [--out FILE]
+With ``--val-size`` the reference's random split holds that share of the rows out and the
+instrumented fits evaluate them after every round (the families apply, metric and sort: the tree
+walk over the held-out rows, ``sa_metric_sums`` / ``sa_auc_keys`` / ``sa_auc_count``, and the sort
+of the minority keys); with ``--early-stopping-rounds`` training also stops by the rule, and the
+record carries ``n_rounds_run_``, ``best_iteration``, the host's looks at the metric table and the
+held-out scores per learner.
+
+    python scripts/boost_time.py [--games 1000] [--reps 3] [--val-size 0.25]
+        [--early-stopping-rounds 10] [--eval-metric auc|logloss] [--sklearn] [--out FILE]
 """
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import statistics
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,16 +41,24 @@ from socceraction_amd import batch as B, boost, ops, synthetic  # noqa: E402
 from socceraction_amd.vaep import VAEP  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
-FAMILIES = ('grad', 'hist_bits', 'hist_bins', 'split', 'advance')
+FAMILIES = ('grad', 'hist_bits', 'hist_bins', 'split', 'advance', 'apply', 'metric', 'sort')
+EVAL_FAMILIES = ('apply', 'metric', 'sort')
+SPLIT_SEED = 0
 
 
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument('--games', type=int, default=1000)
     ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--val-size', type=float, default=0.0)
+    ap.add_argument('--early-stopping-rounds', type=int, default=None)
+    ap.add_argument('--eval-metric', default='auc', choices=boost.EVAL_METRICS)
     ap.add_argument('--sklearn', action='store_true')
     ap.add_argument('--out', default='')
     args = ap.parse_args()
+    stop = dict(early_stopping_rounds=args.early_stopping_rounds, eval_metric=args.eval_metric)
+    if args.early_stopping_rounds is not None and not args.val_size > 0:
+        ap.error('--early-stopping-rounds needs --val-size')
     d = synthetic.spadl_games(args.games, seed=2)
     actions, games = synthetic.to_frame(d), synthetic.games_frame(d)
     model = VAEP()
@@ -49,15 +67,24 @@ def main() -> None:
     ab = B.ActionBatch.from_frame(actions, home_team_id=home_of, segments='game')
     n = ab.n
     res = {'device': torch.cuda.get_device_name(0), 'games': args.games, 'rows': n, 'reps': args.reps,
-           'params': dict(boost.DEFAULTS), 'hbm_bytes_per_s_for_floors': HBM_BYTES_PER_S}
+           'params': dict(boost.DEFAULTS), 'hbm_bytes_per_s_for_floors': HBM_BYTES_PER_S,
+           'val_size': args.val_size, **stop}
     # ---- warm-up, and the model is the same from run to run
     VAEP().fit_batch(games, actions, tree_params=dict(n_estimators=2))
     fb = ops.features(ab, known, 3, bool_bits=True)
     lb = ops.labels(ab)
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    rows = val_rows = None
+    if args.val_size > 0:  # fit_batch's split, from the same seed
+        np.random.seed(SPLIT_SEED)
+        idx = np.random.permutation(n)
+        cut = math.floor(n * (1 - args.val_size))
+        rows = torch.from_numpy(np.sort(idx[:cut])).to(ab.device)
+        val_rows = torch.from_numpy(np.sort(idx[cut + 1:])).to(ab.device)
+        res['eval_rows'] = int(val_rows.numel())
     t0 = time.perf_counter()
-    cuts = boost.make_cuts(fb)
+    cuts = boost.make_cuts(fb, rows)
     torch.cuda.synchronize()
     res['make_cuts_ms'] = round((time.perf_counter() - t0) * 1e3, 2)
     e0.record()
@@ -71,10 +98,10 @@ def main() -> None:
     res['bytes_per_row_per_level'] = {'bitmaps': n_bool / 8, 'bins': f_num, 'gradients_and_node': 9}
     jsons = {}
     for col in ('scores', 'concedes'):
-        clf = boost.DeviceGBTClassifier()
+        clf = boost.DeviceGBTClassifier(**stop)
         clf._events = []
         t0 = time.perf_counter()
-        clf.fit_binned(data, getattr(lb, col))
+        clf.fit_binned(data, getattr(lb, col), rows, val_rows)
         torch.cuda.synchronize()
         wall = (time.perf_counter() - t0) * 1e3
         per = {f: [a.elapsed_time(b) for fam, a, b in clf._events if fam == f] for f in FAMILIES}
@@ -89,6 +116,14 @@ def main() -> None:
         # LDS integer atomics a level issues for the numeric bins (two per feature and row), per second
         entry['lds_atomics_per_s'] = {
             'hist_bins': round(2 * f_num * n / (statistics.median(per['hist_bins']) * 1e-3), 0)}
+        if val_rows is not None:  # what the evaluation adds to a round, against a round's training
+            ran = max(clf.n_rounds_run_, 1)
+            entry['rounds_run'] = clf.n_rounds_run_
+            entry['best_iteration'] = clf.best_iteration
+            entry['best_score'] = clf.best_score
+            entry['table_reads_during_fit'] = clf.n_polls_
+            entry['eval_ms_per_round'] = round(sum(sum(per[f]) for f in EVAL_FAMILIES) / ran, 4)
+            entry['train_ms_per_round'] = round(sum(sum(per[f]) for f in FAMILIES if f not in EVAL_FAMILIES) / ran, 4)
         clf._events = None
         jsons[col] = json.dumps(clf.to_xgboost_json())
         entry['split_nodes'] = int((clf.trees_['feature'] >= 0).sum())
@@ -99,12 +134,17 @@ def main() -> None:
     for _ in range(args.reps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        m = VAEP().fit_batch(games, actions)
+        np.random.seed(SPLIT_SEED)
+        m = VAEP().fit_batch(games, actions, val_size=args.val_size, **stop)
         torch.cuda.synchronize()
         walls.append(round((time.perf_counter() - t0) * 1e3, 1))
     res['fit_batch_wall_ms'] = walls
     res['fit_batch_wall_ms_median'] = statistics.median(walls)
     res['run_to_run_equal'] = all(json.dumps(m._VAEP__models[c].to_xgboost_json()) == jsons[c] for c in jsons)
+    if args.val_size > 0:
+        res['held_out_scores'] = {c: {k: v[k] for k in ('log_loss', 'log_loss_baseline', 'auroc', 'n', 'n_pos')}
+                                  for c, v in m.device_eval_.items()}
+        res['trees_kept'] = {c: len(m._VAEP__models[c].trees_) for c in jsons}
     res['train_scores'] = {c: {k: v[k] for k in ('log_loss', 'log_loss_baseline', 'auroc')}
                            for c, v in m.score_batch(games, actions).items()}
     line = json.dumps(res)

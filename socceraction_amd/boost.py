@@ -11,8 +11,15 @@ The arithmetic contract (DESIGN.md §3 "Boosted-tree training"; ``tests/boost_re
 restates it in numpy): float32 cuts, ``bin(x) = #{i : cut_i <= x32}`` with NaN -> 255, gradients
 quantised to int32 at scale 2^30, int64 histograms, float64 gains, ties to the lowest feature then
 the lowest cut.  Every sum is an integer sum: the model is the same bit for bit from run to run
-and for any row order.  No early stopping, subsampling, sample weights, categorical splits or
-learned default directions (missing values always go right).
+and for any row order.
+
+Held-out evaluation and early stopping (contract items 9-12; ``tests/boost_stop_reference.py``):
+rows given as ``eval_rows`` / ``eval_set`` are pushed through every finished tree by
+``sa_boost_apply`` and scored by the integer sums of ``sa_metric_sums`` (log loss) or the integer
+pair count of ``sa_auc_count`` (AUROC).  Rounds are compared by those integers
+(:func:`stop_decision`: xgboost's rule, zero tolerance), so the early-stopped model is as
+reproducible as the full one.  No subsampling, sample weights, categorical splits or learned
+default directions (missing values always go right).
 """
 from __future__ import annotations
 
@@ -453,6 +460,115 @@ def best_splits(hist, totals, cuts: Sequence[np.ndarray], reg_lambda: float = 1.
     return tree.cpu().numpy().view(NODE_DTYPE).reshape(-1)[node0:node0 + 3 * n_nodes]
 
 
+def _row_list(rows, n: int, dev):
+    """Row indices (int64, on ``dev``) of an index list or a bool mask over the ``n`` rows."""
+    import torch
+    rows = torch.as_tensor(rows, device=dev)
+    if rows.dtype == torch.bool:
+        return torch.nonzero(rows[:n]).reshape(-1)
+    return rows.reshape(-1).to(torch.int64).contiguous()
+
+
+def _apply(data: BinnedData, tree, max_depth: int, rows, n_rows: int, margin, p, launch=None) -> None:
+    """One ``sa_boost_apply`` launch: ``tree`` (device node table) over ``rows`` (device int64
+    list or None) into the compact ``margin`` / ``p``."""
+    nb = len(data.bit_feat)
+    run = launch or (lambda family, fn, *a: _native.check(fn(*a)))
+    run('apply', _native.lib().sa_boost_apply, tree.data_ptr(), int(max_depth), data.dev['fmap'].data_ptr(),
+        data.bits.data_ptr() if nb else None, data.bits.shape[1] * 8 if nb else 0,
+        data.bins.data_ptr() if len(data.num_feat) else None, data.ld,
+        None if rows is None else rows.data_ptr(), int(n_rows), data.n, margin.data_ptr(),
+        None if p is None else p.data_ptr(), _stream())
+
+
+def apply_tree(data: BinnedData, table, margin, rows=None, max_depth: int = DEFAULTS['max_depth']):
+    """``sa_boost_apply``: one tree -- ``table``, ``2^(max_depth+1) - 1`` records of
+    :data:`NODE_DTYPE` in heap order (host array) -- applied to the listed rows of ``data``
+    (indices; default every row).  ``margin``: one float32 per list entry.  Returns the new
+    ``(margin, p)`` device columns; the input is not changed."""
+    import torch
+    D = int(max_depth)
+    if not 1 <= D <= MAX_DEPTH:
+        raise ValueError(f'max_depth must be in 1..{MAX_DEPTH}')
+    tab = np.ascontiguousarray(np.asarray(table, NODE_DTYPE).reshape(-1))
+    if len(tab) != 2 ** (D + 1) - 1:
+        raise ValueError(f'a depth-{D} table has {2 ** (D + 1) - 1} records')
+    dev = data.device
+    if rows is not None:
+        rows = _row_list(rows, data.n, dev)
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= data.n):
+            raise ValueError('rows must be inside the table')
+    k = data.n if rows is None else int(rows.numel())
+    m = torch.as_tensor(margin, device=dev).to(torch.float32).reshape(-1).clone()
+    if m.numel() != k:
+        raise ValueError('one margin per list entry')
+    m = _pad(m, max(k, 1), torch.float32)
+    p = torch.zeros(max(k, 1), dtype=torch.float32, device=dev)
+    tree = torch.from_numpy(tab.view(np.uint8).copy()).to(dev)
+    _apply(data, tree, D, rows, k, m, p)
+    return m[:k], p[:k]
+
+
+# ----------------------------------------------------------------------------- early stopping (host)
+EVAL_METRICS = ('auc', 'logloss')
+
+
+def check_stop_params(early_stopping_rounds=None, eval_metric: str = 'auc'):
+    """``(early_stopping_rounds or None, eval_metric)`` validated: an int >= 1, 'auc' or 'logloss'."""
+    if eval_metric not in EVAL_METRICS:
+        raise ValueError(f'eval_metric must be one of {EVAL_METRICS}, not {eval_metric!r}')
+    if early_stopping_rounds is not None:
+        if isinstance(early_stopping_rounds, bool) or int(early_stopping_rounds) != early_stopping_rounds \
+                or int(early_stopping_rounds) < 1:
+            raise ValueError('early_stopping_rounds must be an integer >= 1')
+        early_stopping_rounds = int(early_stopping_rounds)
+    return early_stopping_rounds, eval_metric
+
+
+def stop_decision(series: Sequence[int], rounds: Optional[int], maximize: bool):
+    """xgboost's early-stopping rule with zero tolerance on the integer metric of every round:
+    round 0 sets the best score, a later round that is STRICTLY better becomes the best and
+    resets a counter, any other round increments it, and training stops after the round at which
+    the counter reaches ``rounds`` (None: never).  Returns ``(best_iteration, rounds_run)``:
+    the first round holding the best score among the rounds run, and how many rounds are run."""
+    best = count = 0
+    for t in range(1, len(series)):
+        if (series[t] > series[best]) if maximize else (series[t] < series[best]):
+            best, count = t, 0
+            continue
+        count += 1
+        if rounds is not None and count >= rounds:
+            return best, t + 1
+    return best, len(series)
+
+
+def stop_look(series: Sequence[int], rounds: int, maximize: bool):
+    """One look of the host at the rounds finished so far (the last one is the round the look was
+    scheduled after): ``(fired, next_look)`` -- whether the rule has fired, i.e. the rounds since
+    the best have reached ``rounds``, and otherwise the round after which it could next fire,
+    ``best + rounds``.  Looking after round ``rounds`` first and then after every ``next_look``
+    meets the stopping round exactly: the rule fires at ``best + rounds`` for the final best, and
+    every earlier look's ``next_look`` is at most that."""
+    best, stop = stop_decision(series, rounds, maximize)
+    return stop - 1 - best >= rounds, best + rounds
+
+
+def metric_integer(row: Sequence[int], eval_metric: str) -> int:
+    """The integer a round is compared by, from its ten words in the ``ops.BinaryMetrics``
+    layout: ``U2`` for 'auc', the log-loss limb sums ``l0 + (l1 << 32) + (l2 << 64)`` for 'logloss'."""
+    if eval_metric == 'auc':
+        return int(row[9])
+    return int(row[5]) + (int(row[6]) << 32) + (int(row[7]) << 64)
+
+
+def metric_score(value: int, eval_metric: str, n_eval: int, n_pos: int) -> float:
+    """The float score of :func:`metric_integer`'s integer: ``U2 / (2 n_pos n_neg)``, or the
+    fixed-point log-loss total over ``n_eval``."""
+    if eval_metric == 'auc':
+        return int(value) / (2 * int(n_pos) * (int(n_eval) - int(n_pos)))
+    return (int(value) / (1 << (95 - _native.SA_METRIC_LOGLOSS_EXP))) / int(n_eval)
+
+
 # ----------------------------------------------------------------------------- the classifier
 def check_params(params: Dict[str, Any]) -> Dict[str, Any]:
     unknown = set(params) - set(DEFAULTS)
@@ -478,10 +594,21 @@ class DeviceGBTClassifier:
     ``record=True`` keeps every round's probabilities and the margin after it (``record_['p']``,
     ``record_['margin']``, ``[n_estimators, n]`` on the device) for tests on small tables.
     After a fit: ``trees_`` (the node tables), ``cuts_``, ``feature_names_in_``, and on the device
-    the training rows' final ``margin_`` and probabilities ``p_``."""
+    the training rows' final ``margin_`` and probabilities ``p_``.
 
-    def __init__(self, record: bool = False, **params) -> None:
+    Held-out evaluation: with evaluation rows (``eval_rows`` of :meth:`fit_binned` /
+    :meth:`fit_blocks`, ``eval_set`` of :meth:`fit`) every finished tree is applied to them and
+    the round is scored by ``eval_metric`` ('auc' or 'logloss') as an integer.  After the fit:
+    ``evals_result_ = {'validation_0': {metric: [float per round run]}}``, ``eval_sums_`` (the
+    integers behind it), ``best_iteration``, ``best_score``, ``n_rounds_run_`` and, with
+    ``record=True``, ``record_['eval_p'] [rounds, n_eval]``.  ``early_stopping_rounds`` (an int
+    >= 1, needs evaluation rows) stops training by :func:`stop_decision`; ``trees_`` then holds
+    trees ``0..best_iteration`` and ``margin_`` / ``p_`` are those trees replayed over all rows."""
+
+    def __init__(self, record: bool = False, early_stopping_rounds: Optional[int] = None,
+                 eval_metric: str = 'auc', **params) -> None:
         p = check_params(params)
+        self.early_stopping_rounds, self.eval_metric = check_stop_params(early_stopping_rounds, eval_metric)
         for k, v in p.items():
             setattr(self, k, v)
         self.record = bool(record)
@@ -502,11 +629,95 @@ class DeviceGBTClassifier:
         e1.record()
         self._events.append((family, e0, e1))
 
-    def fit_binned(self, data: BinnedData, y_dev, rows=None) -> 'DeviceGBTClassifier':
+    def _timed(self, family, work):
+        """``work()`` (device work that is not one of the library's entry points) under the
+        same per-family event timing as :meth:`_launch`."""
+        if self._events is None:
+            return work()
+        import torch
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = work()
+        e1.record()
+        self._events.append((family, e0, e1))
+        return out
+
+    def _eval_setup(self, data: BinnedData, y, eval_rows, T: int):
+        """The evaluation state of a fit: the row list, its compact labels and margins, the
+        zeroed ``[T, 10]`` metric table, and -- the fit's ONE host read before the first round --
+        the list's bounds and its positives (which class is the minority for the AUROC)."""
+        import torch
+        dev, n = data.device, data.n
+        idx = _row_list(eval_rows, n, dev)
+        k = int(idx.numel())
+        if k == 0:
+            raise ValueError('binary scores need at least one row')
+        if k >= 2 ** 30:
+            raise ValueError('binary scores take fewer than 2**30 rows')
+        inside = idx.clamp(0, max(n - 1, 0))
+        lo, hi, n_pos = torch.stack([idx.min(), idx.max(), (y[inside] != 0).sum()]).cpu().tolist()
+        if lo < 0 or hi >= n:
+            raise ValueError('eval_rows must be inside the table')
+        if n_pos == 0 or n_pos == k:
+            raise ValueError('Only one class present in y. The AUROC is not defined in that case.')
+        minority = int(n_pos <= k - n_pos)
+        ev = {'idx': idx, 'n': k, 'n_pos': int(n_pos), 'minority': minority,
+              'm': int(n_pos) if minority else k - int(n_pos), 'y': y[idx].contiguous(),
+              'margin': torch.full((k,), float(base_margin(self.base_score)), dtype=torch.float32, device=dev),
+              'p': torch.empty(k, dtype=torch.float32, device=dev),
+              'table': torch.zeros((max(T, 1), 10), dtype=torch.int64, device=dev),
+              'P': torch.empty((T, k), dtype=torch.float32, device=dev) if self.record else None}
+        if self.eval_metric == 'auc':
+            ev['keys'] = torch.empty(ev['m'], dtype=torch.int32, device=dev)
+            ev['cursor'] = torch.zeros(max(T, 1), dtype=torch.int64, device=dev)
+        return ev
+
+    def _eval_round(self, data: BinnedData, ev, tree, t: int, st) -> None:
+        """Round t's tree applied to the evaluation rows and the round's integer sums written to
+        row t of the metric table: the counts and log-loss limbs always, ``U2`` for 'auc'."""
+        import torch
+        lib, run = _native.lib(), self._launch
+        k, y = ev['n'], ev['y']
+        p = ev['P'][t] if ev['P'] is not None else ev['p']
+        _apply(data, tree, int(self.max_depth), ev['idx'], k, ev['margin'], p, run)
+        row = ev['table'][t]
+        run('metric', lib.sa_metric_sums, y.data_ptr(), p.data_ptr(), 1, k, row[0:2].data_ptr(), row[2:8].data_ptr(),
+            row[8:9].data_ptr(), st)
+        if self.eval_metric != 'auc':
+            return
+        m, mino = ev['m'], ev['minority']
+        run('metric', lib.sa_auc_keys, y.data_ptr(), p.data_ptr(), 1, k, mino, ev['keys'].data_ptr(), m,
+            ev['cursor'][t:t + 1].data_ptr(), st)
+        keys = self._timed('sort', lambda: torch.sort(ev['keys']).values)  # top bit clear: signed order
+        run('metric', lib.sa_auc_count, y.data_ptr(), p.data_ptr(), 1, k, keys.data_ptr(), m, mino,
+            row[9:10].data_ptr(), st)
+
+    def _eval_series(self, ev, rounds: int) -> List[int]:
+        """One host read of the metric table's first ``rounds`` rows: the integer series."""
+        if rounds <= 0:
+            return []
+        from .ops import BinaryMetrics
+        h = ev['table'][:rounds].cpu().tolist()
+        err = 0
+        for r in h:
+            err |= r[8] & 0xFFFFFFFF
+        BinaryMetrics.raise_errors(err)
+        return [metric_integer(r, self.eval_metric) for r in h]
+
+    def fit_binned(self, data: BinnedData, y_dev, rows=None, eval_rows=None) -> 'DeviceGBTClassifier':
         """Fit on binned data and a device label column (uint8 / bool, at least n rows).  The
         whole fit is enqueued on the current stream -- fixed launch sequences per level and per
-        round, no host synchronisation -- and the node tables of all trees are read back once."""
+        round, no host synchronisation -- and the node tables of all trees are read back once.
+
+        ``eval_rows`` (indices or a bool mask; any rows, independent of ``rows``): every round's
+        tree is applied to them and scored, still stream-ordered.  With ``early_stopping_rounds``
+        the host reads the finished rows of the metric table only when the rule could first
+        fire -- after round ``early_stopping_rounds``, then after round ``best + patience`` as
+        known at the previous look -- and launches no round after the stopping round."""
         import torch
+        esr = self.early_stopping_rounds
+        if esr is not None and eval_rows is None:
+            raise ValueError('early_stopping_rounds needs evaluation rows (eval_rows / eval_set)')
         lib, d, dev = _native.lib(), data.dev, data.device
         n, ld, F = data.n, data.ld, data.n_features
         T, D = int(self.n_estimators), int(self.max_depth)
@@ -541,6 +752,9 @@ class DeviceGBTClassifier:
         bstride = data.bits.shape[1] * 8 if nb else 0
         mptr = None if mask is None else mask.data_ptr()
         run = self._launch
+        ev = None if eval_rows is None else self._eval_setup(data, y, eval_rows, T)  # before any training launch
+        maximize = self.eval_metric == 'auc'
+        look, R, self.n_polls_ = esr, T, 0
         for t in range(T):
             tree = trees[t]
             pt = P[t] if P is not None else p
@@ -564,38 +778,105 @@ class DeviceGBTClassifier:
                 node.data_ptr(), margin.data_ptr(), st)
             if Mrec is not None:
                 Mrec[t].copy_(margin)
-        run('grad', lib.sa_boost_grad, margin.data_ptr(), None, None, n, None, None, p.data_ptr(), None, st)
-        self.trees_ = trees.cpu().numpy().view(NODE_DTYPE).reshape(max(T, 1), M)[:T].copy()  # the one read-back
+            if ev is None:
+                continue
+            self._eval_round(data, ev, tree, t, st)
+            if esr is not None and t == look and t + 1 < T:  # the rule could first fire here
+                self.n_polls_ += 1
+                fired, look = stop_look(self._eval_series(ev, t + 1), esr, maximize)
+                if fired:
+                    R = t + 1
+                    break
+        keep = R
+        for k in ('evals_result_', 'eval_sums_', 'best_iteration', 'best_score'):
+            self.__dict__.pop(k, None)
+        if ev is not None:
+            series = self._eval_series(ev, R)
+            best, stop = stop_decision(series, esr, maximize)
+            assert stop == R, (stop, R)  # every round launched was needed
+            self.eval_sums_ = series
+            scores = [metric_score(v, self.eval_metric, ev['n'], ev['n_pos']) for v in series]
+            self.evals_result_ = {'validation_0': {self.eval_metric: scores}}
+            if series:
+                self.best_iteration, self.best_score = best, scores[best]
+                if esr is not None:
+                    keep = best + 1
+        self.n_rounds_run_ = R
+        if esr is not None and keep:
+            # margin_ / p_ belong to the kept trees: replay them over every row from the base
+            # margin (the predictor's walk and its float32 additions, in tree order)
+            margin.fill_(float(base_margin(self.base_score)))
+            for t in range(keep):
+                _apply(data, trees[t], D, None, n, margin, p if t == keep - 1 else None, run)
+        else:
+            run('grad', lib.sa_boost_grad, margin.data_ptr(), None, None, n, None, None, p.data_ptr(), None, st)
+        self.trees_ = trees[:keep].cpu().numpy().view(NODE_DTYPE).reshape(keep, M).copy()  # the one read-back
         self.cuts_ = data.cuts
         self.feature_names_in_ = np.array(data.names, dtype=object)
         self.n_features_in_ = F
         self.classes_ = np.array([0, 1])
         self.margin_, self.p_ = margin[:n], p[:n]
-        self.record_ = {'p': P[:, :n], 'margin': Mrec[:, :n]} if P is not None else None
+        self.record_ = {'p': P[:R, :n], 'margin': Mrec[:R, :n]} if P is not None else None
+        if P is not None and ev is not None:
+            self.record_['eval_p'] = ev['P'][:R]
         self._ensemble = None
         return self
 
-    def fit_blocks(self, blocks, y_dev, rows=None, cuts=None) -> 'DeviceGBTClassifier':
+    def fit_blocks(self, blocks, y_dev, rows=None, cuts=None, eval_rows=None) -> 'DeviceGBTClassifier':
         """Fit on device feature blocks (``ops.features(..., bool_bits=True)``) and a device label
         column.  ``rows``: the training rows (indices or a bool mask), default all; ``cuts``:
-        explicit cut lists, default :func:`make_cuts` on the training rows."""
+        explicit cut lists, default :func:`make_cuts` on the training rows; ``eval_rows``: the
+        evaluation rows (indices or a bool mask), default none."""
+        if self.early_stopping_rounds is not None and eval_rows is None:
+            raise ValueError('early_stopping_rounds needs evaluation rows (eval_rows / eval_set)')
         if rows is not None:
             import torch
             rows = torch.as_tensor(rows, device=blocks.device)
             if rows.dtype == torch.bool:
                 rows = torch.nonzero(rows[:blocks.n]).reshape(-1)
-        return self.fit_binned(bin_blocks(blocks, cuts, rows), y_dev, rows)
+        return self.fit_binned(bin_blocks(blocks, cuts, rows), y_dev, rows, eval_rows)
 
-    def fit(self, X, y, cuts=None) -> 'DeviceGBTClassifier':
-        """Fit on a host frame or 2-D array: uploaded, binned and trained by the same kernels."""
+    def fit(self, X, y, cuts=None, eval_set=None) -> 'DeviceGBTClassifier':
+        """Fit on a host frame or 2-D array: uploaded, binned and trained by the same kernels.
+        ``eval_set=[(X_val, y_val)]``: exactly one pair with the same columns; the two frames
+        are uploaded as one table whose first ``len(X)`` rows train and whose other rows are the
+        evaluation rows (the cuts come from the training rows only)."""
+        if self.early_stopping_rounds is not None and eval_set is None:
+            raise ValueError('early_stopping_rounds needs evaluation rows (eval_rows / eval_set)')
+        yh = np.asarray(y).astype(bool).astype(np.uint8).ravel()
+        n_train = len(yh)
+        rows = eval_rows = None
+        if eval_set is not None:
+            if len(eval_set) != 1 or len(eval_set[0]) != 2:
+                raise ValueError('eval_set takes exactly one (X_val, y_val) pair')
+            names, cols = _host_columns(X)
+            vnames, vcols = _host_columns(eval_set[0][0])
+            if vnames != names or [_kind(c) for c in vcols] != [_kind(c) for c in cols]:
+                raise ValueError('the evaluation frame must have the training frame\'s columns')
+            if cols and len(cols[0]) != n_train:
+                raise ValueError('X and y have different lengths')
+            yv = np.asarray(eval_set[0][1]).astype(bool).astype(np.uint8).ravel()
+            if vcols and len(vcols[0]) != len(yv):
+                raise ValueError('X_val and y_val have different lengths')
+            import pandas as pd
+            X = pd.DataFrame({c: np.concatenate([a, b]) for c, a, b in zip(names, cols, vcols)}, columns=names)
+            yh = np.concatenate([yh, yv])
+            rows = np.arange(n_train, dtype=np.int64)
+            eval_rows = np.arange(n_train, len(yh), dtype=np.int64)
         import torch
-        data = bin_host(X, cuts)
-        yh = np.ascontiguousarray(np.asarray(y).astype(bool).astype(np.uint8).ravel())
+        data = bin_host(X, cuts, rows)
+        yh = np.ascontiguousarray(yh)
         if len(yh) != data.n:
             raise ValueError('X and y have different lengths')
         yd = torch.zeros(data.ld, dtype=torch.uint8, device=data.device)
         yd[:data.n] = torch.from_numpy(yh).to(data.device)
-        return self.fit_binned(data, yd)
+        self.fit_binned(data, yd, rows, eval_rows)
+        if eval_set is not None:  # the fitted columns are the training frame's
+            self.margin_, self.p_ = self.margin_[:n_train], self.p_[:n_train]
+            if self.record_ is not None:
+                for k in ('p', 'margin'):
+                    self.record_[k] = self.record_[k][:, :n_train]
+        return self
 
     # ------------------------------------------------------------------ use
     def _fitted(self) -> None:
@@ -604,8 +885,14 @@ class DeviceGBTClassifier:
             raise NotFittedError('this DeviceGBTClassifier is not fitted yet')
 
     def to_xgboost_json(self) -> dict:
+        """The kept trees as an xgboost-1.6-shaped model; under early stopping the learner
+        ``attributes`` carry ``best_iteration`` and ``best_score`` as strings, as xgboost's do."""
         self._fitted()
-        return trees_to_xgboost_json(self.trees_, list(self.feature_names_in_), float(self.base_score))
+        model = trees_to_xgboost_json(self.trees_, list(self.feature_names_in_), float(self.base_score))
+        if self.early_stopping_rounds is not None and hasattr(self, 'best_iteration'):
+            model['learner']['attributes'] = {'best_iteration': str(int(self.best_iteration)),
+                                              'best_score': repr(float(self.best_score))}
+        return model
 
     def predict_proba(self, X) -> np.ndarray:
         """Host ``[n, 2]`` float32 probabilities of a host frame (columns matched by name) or
@@ -660,4 +947,5 @@ class DeviceGBTClassifier:
 
 __all__ = ['DeviceGBTClassifier', 'BinnedData', 'NODE_DTYPE', 'make_cuts', 'cuts_from_sample', 'sample_rows',
            'cast32', 'bin_values', 'bin_blocks', 'bin_host', 'gradients', 'histograms', 'best_splits',
-           'trees_to_xgboost_json', 'predict_tables', 'base_margin', 'check_params']
+           'trees_to_xgboost_json', 'predict_tables', 'base_margin', 'check_params', 'apply_tree',
+           'stop_decision', 'stop_look', 'check_stop_params', 'metric_integer', 'metric_score', 'EVAL_METRICS']

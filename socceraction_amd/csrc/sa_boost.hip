@@ -452,6 +452,62 @@ __global__ __launch_bounds__(256) void boost_advance_kernel(const sa_boost_node*
   node[j] = (uint8_t)(2 * raw + 1 + (right ? 1 : 0));
 }
 
+// ---------------------------------------------------------------------------------------- apply
+// One finished tree applied to a list of rows (the held-out rows of a round; every row when the
+// kept trees are replayed): one thread per list entry.  The workgroup stages what the walk reads
+// of the round's node table -- at most 127 records of 48 bytes -- in LDS once, as 12 bytes per
+// node: the split feature's place (fmap resolved; -1 = leaf), its cut and the node's value.  The
+// walk is the predictor's: bit set / bin > cut goes right, so the missing bin 255 goes right; at
+// most max_depth steps, so the node index stays below 2^(max_depth+1) - 1.  The bitmap and bin
+// reads are gathers by row.  A list entry whose row is outside [0, n) is left untouched.
+constexpr int AP_THREADS = 256;
+constexpr int AP_NODES = (2 << SA_BOOST_MAX_DEPTH) - 1;
+
+__global__ __launch_bounds__(AP_THREADS) void boost_apply_kernel(const sa_boost_node* __restrict__ tree, int max_depth,
+                                                                  const int32_t* __restrict__ fmap,
+                                                                  const u64* __restrict__ bits, int64_t wstride,
+                                                                  const uint8_t* __restrict__ bins, int64_t ld,
+                                                                  const int64_t* __restrict__ rows, int64_t n_rows,
+                                                                  int64_t n, float* __restrict__ margin,
+                                                                  float* __restrict__ p) {
+  __shared__ int32_t s_slot[AP_NODES];
+  __shared__ int32_t s_cut[AP_NODES];
+  __shared__ float s_val[AP_NODES];
+  const int n_nodes = (2 << max_depth) - 1;
+  for (int k = threadIdx.x; k < n_nodes; k += AP_THREADS) {
+    const int f = tree[k].feature;
+    int32_t slot = -1;
+    if (f >= 0) {
+      slot = fmap[f];
+      // a split on a kind of feature whose data was not passed cannot be walked: the walk ends here
+      if (slot < 0 || ((slot >> 24) == 0 ? bits == nullptr : bins == nullptr)) slot = -1;
+    }
+    s_slot[k] = slot;
+    s_cut[k] = tree[k].cut;
+    s_val[k] = tree[k].value;
+  }
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * AP_THREADS + threadIdx.x;
+  if (i >= n_rows) return;
+  const int64_t j = rows ? rows[i] : i;
+  if (j < 0 || j >= n) return;
+  int node = 0;
+  for (int d = 0; d < max_depth; ++d) {
+    const int32_t slot = s_slot[node];
+    if (slot < 0) break;
+    const int64_t row = slot & 0xFFFFFF;
+    bool right;
+    if ((slot >> 24) == 0)
+      right = (bits[row * wstride + (j >> 6)] >> (j & 63)) & 1;
+    else
+      right = (int)bins[row * ld + j] > s_cut[node];
+    node = 2 * node + 1 + (right ? 1 : 0);
+  }
+  const float m = margin[i] + s_val[node];
+  margin[i] = m;
+  if (p) p[i] = 1.0f / (1.0f + expf(-m));
+}
+
 // level-local node range [node0, node0 + n_nodes): one whole level of the heap, at most 32 nodes
 bool level_ok(int node0, int n_nodes) {
   return n_nodes >= 1 && n_nodes <= SA_BOOST_MAX_LEVEL_NODES && (n_nodes & (n_nodes - 1)) == 0 &&
@@ -581,4 +637,20 @@ extern "C" int sa_boost_advance(const sa_boost_node* tree, int32_t node0, int32_
     hipLaunchKernelGGL((boost_advance_kernel<false>), grid, block, 0, (hipStream_t)stream, tree, node0, n_nodes, fmap,
                        (const u64*)bits, bits_stride / 8, bins, ld, n, node, margin);
   return check_launch("boost_advance_kernel");
+}
+
+extern "C" int sa_boost_apply(const sa_boost_node* tree, int32_t max_depth, const int32_t* fmap, const uint64_t* bits,
+                              int64_t bits_stride, const uint8_t* bins, int64_t ld, const int64_t* rows,
+                              int64_t n_rows, int64_t n, float* margin, float* p, void* stream) {
+  if (n < 0 || n_rows < 0 || max_depth < 1 || max_depth > SA_BOOST_MAX_DEPTH || ld < n)
+    return fail(SA_EINVAL, "sa_boost_apply: bad sizes");
+  if (!tree || !fmap || !margin) return fail(SA_EINVAL, "sa_boost_apply: null pointer");
+  if (bits && (bits_stride % 8 || bits_stride < 8 * ((n + 63) / 64) || ((uintptr_t)bits & 7u)))
+    return fail(SA_EINVAL, "sa_boost_apply: bad bitmaps");
+  if (n_rows > (int64_t)0x7FFFFFFF * AP_THREADS) return fail(SA_EINVAL, "sa_boost_apply: too many rows");
+  if (n_rows == 0) return SA_OK;
+  hipLaunchKernelGGL(boost_apply_kernel, dim3((unsigned)((n_rows + AP_THREADS - 1) / AP_THREADS)), dim3(AP_THREADS), 0,
+                     (hipStream_t)stream, tree, (int)max_depth, fmap, (const u64*)bits, bits_stride / 8, bins, ld, rows,
+                     n_rows, n, margin, p);
+  return check_launch("boost_apply_kernel");
 }

@@ -210,7 +210,7 @@ class VAEP:
             missing_cols = ' and '.join(set(cols).difference(X.columns))
             raise ValueError(f'{missing_cols} are not available in the features dataframe')
         if learner == 'device':
-            return self._fit_device(X[cols], y, train_idx, val_idx, val_size, tree_params)
+            return self._fit_device(X[cols], y, train_idx, val_idx, val_size, tree_params, fit_params)
         X_train, y_train = X.iloc[train_idx][cols], y.iloc[train_idx]
         X_val, y_val = X.iloc[val_idx][cols], y.iloc[val_idx]
         for col in list(y.columns):
@@ -229,22 +229,42 @@ class VAEP:
         return self
 
     # ---------------------------------------------------------------- learning (device)
-    def _fit_device(self, X, y, train_idx, val_idx, val_size, tree_params) -> 'VAEP':
+    @staticmethod
+    def _device_stop_params(early_stopping_rounds, eval_metric, has_val: bool) -> Dict[str, Any]:
+        """The device learner's early-stopping parameters, validated before any device call."""
+        from .. import boost
+        esr, metric = boost.check_stop_params(early_stopping_rounds, eval_metric)
+        if esr is not None and not has_val:
+            raise ValueError('early_stopping_rounds needs held-out rows: val_size must be positive')
+        return dict(early_stopping_rounds=esr, eval_metric=metric)
+
+    def _fit_device(self, X, y, train_idx, val_idx, val_size, tree_params, fit_params=None) -> 'VAEP':
         """``fit(..., learner='device')``: one :class:`socceraction_amd.boost.DeviceGBTClassifier`
         per label column on the reference's split of the rows.  The frame is uploaded and binned
-        once (cuts from the training rows); no early stopping: the held-out rows are scored once
-        after training (``self.device_eval_[col]``, :func:`socceraction_amd.metrics.binary_scores`)."""
+        once (cuts from the training rows).  ``fit_params`` is read for ``early_stopping_rounds``
+        and ``eval_metric`` only: with ``early_stopping_rounds`` the held-out rows are the
+        evaluation rows of every round and the best round's model is kept (the reference's
+        default ``fit``); without, all trees are trained.  Either way the held-out rows are scored
+        once with the kept trees (``self.device_eval_[col]``,
+        :func:`socceraction_amd.metrics.binary_scores`)."""
         from .. import boost, metrics
         import torch
         params = boost.check_params(dict(tree_params or {}))  # before any device call
+        fp = dict(fit_params or {})
+        stop = self._device_stop_params(fp.get('early_stopping_rounds'), fp.get('eval_metric', 'auc'),
+                                        val_size > 0 and len(val_idx) > 0)
         train_idx = np.sort(np.asarray(train_idx, np.int64))
         data = boost.bin_host(X, rows=train_idx)
         rows = torch.from_numpy(train_idx).to(data.device)
+        eval_rows = None
+        if stop['early_stopping_rounds'] is not None:
+            eval_rows = torch.from_numpy(np.sort(np.asarray(val_idx, np.int64))).to(data.device)
         self.device_eval_: Dict[str, Dict[str, float]] = {}
         for col in list(y.columns):
             yh = np.zeros(data.ld, np.uint8)
             yh[:data.n] = y[col].to_numpy().astype(bool)
-            clf = boost.DeviceGBTClassifier(**params).fit_binned(data, torch.from_numpy(yh).to(data.device), rows)
+            clf = boost.DeviceGBTClassifier(**params, **stop).fit_binned(
+                data, torch.from_numpy(yh).to(data.device), rows, eval_rows)
             self.__models[col] = clf
             if val_size > 0 and len(val_idx):
                 p = clf.predict_proba(X.iloc[val_idx])[:, 1]
@@ -253,18 +273,22 @@ class VAEP:
 
     def fit_batch(self, games: pd.DataFrame, actions: pd.DataFrame, learner: str = 'device',
                   val_size: float = 0.0, nr_actions: int = 10,
-                  tree_params: Optional[Dict[str, Any]] = None) -> 'VAEP':
+                  tree_params: Optional[Dict[str, Any]] = None,
+                  early_stopping_rounds: Optional[int] = None, eval_metric: str = 'auc') -> 'VAEP':
         """Fit both learners on many games (contiguous per game) without the feature frame: one
         ``ActionBatch``, the features as bitmaps plus numeric blocks and the labels all on the
         device; only the cut sample and the finished trees cross the link.  ``val_size``: the
         share of rows (the reference's random split) held out and scored once after training
-        into ``self.device_eval_``.  Built-in transformers only."""
+        into ``self.device_eval_``.  ``early_stopping_rounds`` (needs ``val_size > 0``): the
+        held-out rows are evaluated after every round by ``eval_metric`` ('auc' or 'logloss')
+        and the best round's model is kept.  Built-in transformers only."""
         from .. import boost, metrics
         from ..trees import TreeEnsemble
         import torch
         if learner != 'device':
             raise ValueError(f'A {learner} learner is not supported by fit_batch')
         params = boost.check_params(dict(tree_params or {}))  # before any device call
+        stop = self._device_stop_params(early_stopping_rounds, eval_metric, val_size > 0)
         known, unknown = self._split_xfns()
         if unknown:
             raise ValueError('fit_batch needs built-in feature transformers')
@@ -282,7 +306,8 @@ class VAEP:
         self.device_eval_ = {}
         for col in ('scores', 'concedes'):
             ycol = getattr(lb, col)
-            clf = boost.DeviceGBTClassifier(**params).fit_binned(data, ycol, rows)
+            clf = boost.DeviceGBTClassifier(**params, **stop).fit_binned(
+                data, ycol, rows, val_rows if stop['early_stopping_rounds'] is not None else None)
             self.__models[col] = clf
             if val_rows is not None and val_rows.numel():
                 p = TreeEnsemble.from_model(clf).predict_blocks(fb)
