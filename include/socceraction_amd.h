@@ -831,8 +831,29 @@ int sa_auc_count(const uint8_t* y, const void* p, int32_t f32, int64_t n, const 
  *   the trainer's.  bits or bins may be NULL when the table has no feature of that kind; an
  *   entry whose row is outside [0, n) is never dereferenced and keeps its margin and p.  One
  *   thread per entry, 256 per workgroup; the records' walk fields are staged in LDS once per
- *   workgroup (12 bytes per node), the bitmap and bin reads are gathers by row. */
+ *   workgroup (12 bytes per node), the bitmap and bin reads are gathers by row.
+ *
+ * Sample weights, sampling and the L1 penalty (contract items 13-17).  The existing entries keep
+ * their results; the _ex entries with neutral arguments (weight = row_keys = feature_mask = NULL,
+ * scale_pos_weight = 1, shift = 0, thr = 2^32, reg_alpha = 0) compute the same.
+ * sa_boost_grad_ex: we = weight[j] * (y[j] ? scale_pos_weight : 1.0f) (weight == NULL: 1.0f), g =
+ *   (p - y) * we, h = (p * (1 - p)) * we, gq = (int32)rint(g * 2^(30 - shift)), hq likewise, every
+ *   product rounded on its own.  The caller guarantees 0 <= we <= 2^shift, shift in 0 ..
+ *   SA_BOOST_MAX_SHIFT.  Row j is in the round's sample iff (draw >> 32) < thr, thr in 0 .. 2^32
+ *   (2^32: every row, no hash), draw = fm(fm(fm(seed ^ SA_BOOST_SALT_ROWS) + round) + key), fm =
+ *   splitmix64's finaliser on wrapping uint64, key = row_keys[j] (NULL: j).  A row outside the
+ *   sample gets gq = hq = 0; its node is set like any other row's.
+ * sa_boost_hist_bins_ex: list entry r is row num_rows[r] (NULL: r) of the n_bin_rows-row bin
+ *   matrix and feature number num_feat[r]: a round's column sample reads only its own rows.
+ * sa_boost_split_ex: sa_boost_split with T(G) = G > a ? G - a : (G < -a ? G + a : 0), a =
+ *   reg_alpha, in place of G, GL and GR in the gain and the leaf value; every integer sum scaled
+ *   by 2^(shift - 30) (so min_child_weight compares weighted hessians); and feature_mask
+ *   [n_features] (NULL: all): a feature whose byte is 0 is no split candidate (best_cut = -1).
+ * sa_boost_row_keys: keys[j] = fm(game_id[j]) + action_id[j], wrapping. */
 #define SA_BOOST_MAX_DEPTH 6
+#define SA_BOOST_MAX_SHIFT 20
+#define SA_BOOST_SALT_ROWS 0x726F77ull
+#define SA_BOOST_SALT_COLS 0x636F6Cull
 #define SA_BOOST_MAX_CUTS 254
 #define SA_BOOST_MISSING_BIN 255
 #define SA_BOOST_NO_NODE 255
@@ -876,6 +897,21 @@ int sa_boost_apply(const sa_boost_node* tree, int32_t max_depth, const int32_t* 
                    const int64_t* rows /* NULL: rows 0..n_rows-1 */, int64_t n_rows, int64_t n,
                    float* margin /* [n_rows], updated in place */, float* p /* [n_rows] or NULL */,
                    void* stream);
+int sa_boost_grad_ex(const float* margin, const uint8_t* y, const uint8_t* row_mask, int64_t n,
+                     const float* weight, float scale_pos_weight, int32_t shift,
+                     const int64_t* row_keys, uint64_t seed, int64_t round, uint64_t thr, int32_t* gq,
+                     int32_t* hq, float* p, uint8_t* node, void* stream);
+int sa_boost_hist_bins_ex(const uint8_t* bins, int64_t ld, const int32_t* num_feat,
+                          const int32_t* num_rows, int32_t n_bin_rows, int32_t n_num, const int32_t* gq,
+                          const int32_t* hq, const uint8_t* node, int64_t n, int32_t node0,
+                          int32_t n_nodes, int32_t n_features, int64_t* hist, void* stream);
+int sa_boost_split_ex(const int64_t* hist, const int32_t* cut_start, const float* cuts,
+                      int32_t n_features, int32_t node0, int32_t n_nodes, int32_t leaf_only,
+                      double reg_lambda, double min_child_weight, double gamma, double learning_rate,
+                      double reg_alpha, int32_t shift, const uint8_t* feature_mask, double* best_gain,
+                      int32_t* best_cut, sa_boost_node* tree, void* stream);
+int sa_boost_row_keys(const int64_t* game_id, const int64_t* action_id, int64_t n, int64_t* keys,
+                      void* stream);
 
 /* ---- runtime ------------------------------------------------------------------ */
 int sa_abi_version(void);

@@ -18,8 +18,22 @@ of the minority keys); with ``--early-stopping-rounds`` training also stops by t
 record carries ``n_rounds_run_``, ``best_iteration``, the host's looks at the metric table and the
 held-out scores per learner.
 
+``--subsample``, ``--colsample-bytree``, ``--reg-alpha``, ``--scale-pos-weight``, ``--random-state``
+and ``--max-weight W`` (a synthetic weight column uniform in [0, W); W > 1 gives a quantisation
+shift e > 0) put the learner's tuning parameters into every fit of the run.
+
+``--sampling-record`` instead writes the record of those parameters' cost
+(``profiles/boost_fit_sampling.json``): for the default parameters, ``colsample_bytree=0.5``,
+``subsample=0.5`` and weights with e > 0 in turn, the median and the spread of `--reps`
+``fit_batch`` calls and the per-family event sums of one instrumented fit per learner, each as a
+ratio to the default's; ``--parent-json FILE`` (this script's ``--out`` file from the parent
+commit, run on the same device in the same session) puts the parent's default figures beside
+the first.
+
     python scripts/boost_time.py [--games 1000] [--reps 3] [--val-size 0.25]
         [--early-stopping-rounds 10] [--eval-metric auc|logloss] [--sklearn] [--out FILE]
+        [--subsample S] [--colsample-bytree C] [--reg-alpha A] [--scale-pos-weight P]
+        [--random-state R] [--max-weight W] [--sampling-record [--parent-json FILE]]
 """
 from __future__ import annotations
 
@@ -46,6 +60,63 @@ EVAL_FAMILIES = ('apply', 'metric', 'sort')
 SPLIT_SEED = 0
 
 
+def sampling_record(args, games, actions, data, lb) -> dict:
+    """The four configurations of ``--sampling-record`` on one batch, one after the other."""
+    n = data.n
+    w = (np.random.default_rng(0).random(n) * args.max_weight).astype(np.float32)
+    keys = boost.row_keys(actions['game_id'].to_numpy(), actions['action_id'].to_numpy(), data.device)
+    configs = [('default', {}, None), ('colsample_bytree_0.5', dict(colsample_bytree=0.5), None),
+               ('subsample_0.5', dict(subsample=0.5), None), (f'weights_below_{args.max_weight:g}', {}, w)]
+    out = {}
+    for name, tp, weight in configs:
+        fams, shift, splits = {}, None, 0
+        for col in ('scores', 'concedes'):  # one instrumented fit per learner
+            clf = boost.make_classifier(tp)
+            clf._events = []
+            clf.fit_binned(data, getattr(lb, col), None, None, weight, keys)
+            torch.cuda.synchronize()
+            for fam, a, b in clf._events:
+                fams[fam] = fams.get(fam, 0.0) + a.elapsed_time(b)
+            shift, splits = clf.quant_shift_, splits + int(((clf.trees_['feature'] >= 0)
+                                                            & (clf.trees_['exists'] != 0)).sum())
+        walls, models = [], []
+        for _ in range(args.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            m = VAEP().fit_batch(games, actions, tree_params=tp, sample_weight=weight)
+            torch.cuda.synchronize()
+            walls.append(round((time.perf_counter() - t0) * 1e3, 1))
+            models.append(json.dumps(m._VAEP__models['scores'].to_xgboost_json()))
+        out[name] = {'tree_params': tp, 'weights': weight is not None, 'quant_shift': shift,
+                     'fit_batch_wall_ms': walls, 'fit_batch_wall_ms_median': statistics.median(walls),
+                     'fit_batch_wall_ms_spread': round(max(walls) - min(walls), 1),
+                     'family_sum_ms_both_learners': {f: round(v, 2) for f, v in fams.items()},
+                     'kernel_sum_ms_both_learners': round(sum(fams.values()), 2), 'split_nodes': splits,
+                     'run_to_run_equal': len(set(models)) == 1}
+        print(name, json.dumps(out[name]), flush=True)
+    base = out['default']
+    for name, entry in out.items():
+        entry['wall_ratio_to_default'] = round(entry['fit_batch_wall_ms_median'] / base['fit_batch_wall_ms_median'], 4)
+        entry['kernel_ratio_to_default'] = round(entry['kernel_sum_ms_both_learners']
+                                                 / base['kernel_sum_ms_both_learners'], 4)
+        entry['hist_ratio_to_default'] = round(
+            sum(entry['family_sum_ms_both_learners'][f] for f in ('hist_bits', 'hist_bins'))
+            / sum(base['family_sum_ms_both_learners'][f] for f in ('hist_bits', 'hist_bins')), 4)
+    if args.parent_json:
+        with open(args.parent_json) as f:
+            parent = json.load(f)
+        pw = parent['fit_batch_wall_ms']
+        out['parent_commit_default'] = {
+            'fit_batch_wall_ms': pw, 'fit_batch_wall_ms_median': statistics.median(pw),
+            'fit_batch_wall_ms_spread': round(max(pw) - min(pw), 1), 'device': parent.get('device'),
+            'rows': parent.get('rows'),
+            'family_sum_ms_both_learners': {f: round(parent['scores']['sum_ms'][f] + parent['concedes']['sum_ms'][f], 2)
+                                            for f in ('grad', 'hist_bits', 'hist_bins', 'split', 'advance')}}
+        out['default_minus_parent_wall_ms'] = round(base['fit_batch_wall_ms_median']
+                                                    - out['parent_commit_default']['fit_batch_wall_ms_median'], 1)
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument('--games', type=int, default=1000)
@@ -55,7 +126,20 @@ def main() -> None:
     ap.add_argument('--eval-metric', default='auc', choices=boost.EVAL_METRICS)
     ap.add_argument('--sklearn', action='store_true')
     ap.add_argument('--out', default='')
+    ap.add_argument('--subsample', type=float, default=1.0)
+    ap.add_argument('--colsample-bytree', type=float, default=1.0)
+    ap.add_argument('--reg-alpha', type=float, default=0.0)
+    ap.add_argument('--scale-pos-weight', type=float, default=1.0)
+    ap.add_argument('--random-state', type=int, default=0)
+    ap.add_argument('--max-weight', type=float, default=0.0)
+    ap.add_argument('--sampling-record', action='store_true')
+    ap.add_argument('--parent-json', default='')
     args = ap.parse_args()
+    tp = {k: v for k, v in dict(subsample=args.subsample, colsample_bytree=args.colsample_bytree,
+                                reg_alpha=args.reg_alpha, scale_pos_weight=args.scale_pos_weight,
+                                random_state=args.random_state).items() if v != boost.ALL_DEFAULTS[k]}
+    if args.sampling_record and not args.max_weight > 0:
+        args.max_weight = 5.0
     stop = dict(early_stopping_rounds=args.early_stopping_rounds, eval_metric=args.eval_metric)
     if args.early_stopping_rounds is not None and not args.val_size > 0:
         ap.error('--early-stopping-rounds needs --val-size')
@@ -67,7 +151,8 @@ def main() -> None:
     ab = B.ActionBatch.from_frame(actions, home_team_id=home_of, segments='game')
     n = ab.n
     res = {'device': torch.cuda.get_device_name(0), 'games': args.games, 'rows': n, 'reps': args.reps,
-           'params': dict(boost.DEFAULTS), 'hbm_bytes_per_s_for_floors': HBM_BYTES_PER_S,
+           'params': {**boost.ALL_DEFAULTS, **tp}, 'max_weight': args.max_weight,
+           'hbm_bytes_per_s_for_floors': HBM_BYTES_PER_S,
            'val_size': args.val_size, **stop}
     # ---- warm-up, and the model is the same from run to run
     VAEP().fit_batch(games, actions, tree_params=dict(n_estimators=2))
@@ -96,12 +181,25 @@ def main() -> None:
     res['bin_GBs'] = round(n * (8 * f_num + f_num) / e0.elapsed_time(e1) * 1e-6, 1)
     bytes_level = {'hist_bits': n * (n_bool / 8 + 9), 'hist_bins': n * (f_num + 9)}
     res['bytes_per_row_per_level'] = {'bitmaps': n_bool / 8, 'bins': f_num, 'gradients_and_node': 9}
+    if args.sampling_record:
+        res['configurations'] = sampling_record(args, games, actions, data, lb)
+        line = json.dumps(res)
+        if args.out:
+            with open(args.out, 'w') as f:
+                f.write(json.dumps(res, indent=1) + '\n')
+        print(line)
+        return
+    weight = None
+    if args.max_weight > 0:
+        weight = (np.random.default_rng(0).random(n) * args.max_weight).astype(np.float32)
+    keys = boost.row_keys(actions['game_id'].to_numpy(), actions['action_id'].to_numpy(), ab.device) \
+        if args.subsample != 1.0 else None
     jsons = {}
     for col in ('scores', 'concedes'):
-        clf = boost.DeviceGBTClassifier(**stop)
+        clf = boost.make_classifier(tp, **stop)
         clf._events = []
         t0 = time.perf_counter()
-        clf.fit_binned(data, getattr(lb, col), rows, val_rows)
+        clf.fit_binned(data, getattr(lb, col), rows, val_rows, weight, keys)
         torch.cuda.synchronize()
         wall = (time.perf_counter() - t0) * 1e3
         per = {f: [a.elapsed_time(b) for fam, a, b in clf._events if fam == f] for f in FAMILIES}
@@ -135,7 +233,7 @@ def main() -> None:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         np.random.seed(SPLIT_SEED)
-        m = VAEP().fit_batch(games, actions, val_size=args.val_size, **stop)
+        m = VAEP().fit_batch(games, actions, val_size=args.val_size, tree_params=tp, sample_weight=weight, **stop)
         torch.cuda.synchronize()
         walls.append(round((time.perf_counter() - t0) * 1e3, 1))
     res['fit_batch_wall_ms'] = walls

@@ -43,6 +43,7 @@ SA_AUC_LDS_SAMPLE = 1024  # sorted minority keys sa_auc_count keeps in LDS
 # boosted-tree training (sa_boost.hip; mirrors include/socceraction_amd.h)
 SA_BOOST_MAX_DEPTH, SA_BOOST_MAX_CUTS, SA_BOOST_MISSING_BIN, SA_BOOST_NO_NODE = 6, 254, 255, 255
 SA_BOOST_MAX_LEVEL_NODES, SA_BOOST_FEATURE_GROUP = 32, 4
+SA_BOOST_MAX_SHIFT, SA_BOOST_SALT_ROWS, SA_BOOST_SALT_COLS = 20, 0x726F77, 0x636F6C
 SA_BOOST_BIN_TILE, SA_BOOST_BITS_TILE, SA_BOOST_BINS_TILE = 1024, 2048, 1024
 SA_OK, SA_EINVAL, SA_EHIP, SA_EDATA, SA_ENOMEM = 0, -1, -2, -3, -4
 
@@ -278,6 +279,15 @@ _SIGNATURES = {
                                         ctypes.c_int64, ctypes.c_int64, _p, _p, _p]),
     'sa_boost_apply': (ctypes.c_int, [_p, ctypes.c_int32, _p, _p, ctypes.c_int64, _p, ctypes.c_int64, _p,
                                       ctypes.c_int64, ctypes.c_int64, _p, _p, _p]),
+    'sa_boost_grad_ex': (ctypes.c_int, [_p, _p, _p, ctypes.c_int64, _p, ctypes.c_float, ctypes.c_int32, _p,
+                                        ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint64, _p, _p, _p, _p, _p]),
+    'sa_boost_hist_bins_ex': (ctypes.c_int, [_p, ctypes.c_int64, _p, _p, ctypes.c_int32, ctypes.c_int32, _p, _p, _p,
+                                             ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                             _p, _p]),
+    'sa_boost_split_ex': (ctypes.c_int, [_p, _p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_int32, _p, _p, _p, _p, _p]),
+    'sa_boost_row_keys': (ctypes.c_int, [_p, _p, ctypes.c_int64, _p, _p]),
     'sa_device_alloc': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
     'sa_device_free': (ctypes.c_int, [_p]),
     'sa_copy2d_async': (ctypes.c_int, [_p, ctypes.c_int64, _p, ctypes.c_int64, ctypes.c_int64,

@@ -18,12 +18,20 @@ rows given as ``eval_rows`` / ``eval_set`` are pushed through every finished tre
 ``sa_boost_apply`` and scored by the integer sums of ``sa_metric_sums`` (log loss) or the integer
 pair count of ``sa_auc_count`` (AUROC).  Rounds are compared by those integers
 (:func:`stop_decision`: xgboost's rule, zero tolerance), so the early-stopped model is as
-reproducible as the full one.  No subsampling, sample weights, categorical splits or learned
-default directions (missing values always go right).
+reproducible as the full one.
+
+Sample weights, ``scale_pos_weight``, the L1 penalty and row / column subsampling (contract items
+13-17; ``tests/boost_sample_reference.py``): weights are folded in before the quantisation with an
+exact power-of-two rescale, a round's samples come from a counter hash of ``(random_state, round,
+row key or feature)``, so a tuned model is as reproducible as a plain one.  The tuning parameters
+are :class:`TunedGBTClassifier`'s; :class:`DeviceGBTClassifier` keeps its seven.  No weighted
+evaluation, bylevel / bynode column sampling, categorical splits or learned default directions
+(missing values always go right).
 """
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional, Sequence
 
@@ -42,6 +50,10 @@ SAMPLE_ROWS = 65536
 GRAD_SCALE = 2 ** 30
 DEFAULTS = dict(n_estimators=100, max_depth=3, learning_rate=0.3, reg_lambda=1.0, min_child_weight=1.0,
                 gamma=0.0, base_score=0.5)
+# the tuning parameters of contract items 13-17 (TunedGBTClassifier, VAEP's tree_params), neutral
+TUNING_DEFAULTS = dict(subsample=1.0, colsample_bytree=1.0, reg_alpha=0.0, scale_pos_weight=1.0, random_state=0)
+ALL_DEFAULTS = {**DEFAULTS, **TUNING_DEFAULTS}
+THR_ALL = 1 << 32  # the row threshold that takes every row
 
 
 # ----------------------------------------------------------------------------- cuts (host)
@@ -368,8 +380,13 @@ def _stream():
     return stream_handle()
 
 
-def gradients(margin, y, row_mask=None):
-    """``sa_boost_grad`` on device columns: ``(gq, hq, p)`` -- int32, int32, float32."""
+def gradients(margin, y, row_mask=None, *, weight=None, scale_pos_weight: float = 1.0, shift: int = 0,
+              row_keys=None, seed: int = 0, round: int = 0, thr: Optional[int] = None):
+    """``sa_boost_grad`` on device columns: ``(gq, hq, p)`` -- int32, int32, float32.  With any
+    keyword argument ``sa_boost_grad_ex``: ``weight`` (float32 device column), ``scale_pos_weight``,
+    the quantisation ``shift`` e (the caller keeps every effective weight ``<= 2^e``), and the
+    round's row sample -- ``row_keys`` (int64 device column, default the row index), ``seed``,
+    ``round`` and the raw threshold ``thr`` in ``0 .. 2^32`` (default ``2^32``: every row)."""
     import torch
     n = margin.numel()
     margin = margin.to(torch.float32).contiguous()
@@ -377,10 +394,39 @@ def gradients(margin, y, row_mask=None):
     gq = torch.empty(max(n, 1), dtype=torch.int32, device=margin.device)
     hq = torch.empty_like(gq)
     p = torch.empty(max(n, 1), dtype=torch.float32, device=margin.device)
-    _native.check(_native.lib().sa_boost_grad(margin.data_ptr(), y.contiguous().data_ptr(),
-                                              None if row_mask is None else row_mask.data_ptr(), n,
-                                              gq.data_ptr(), hq.data_ptr(), p.data_ptr(), None, _stream()))
+    mptr = None if row_mask is None else row_mask.data_ptr()
+    if weight is None and scale_pos_weight == 1.0 and shift == 0 and row_keys is None and thr is None:
+        _native.check(_native.lib().sa_boost_grad(margin.data_ptr(), y.contiguous().data_ptr(), mptr, n,
+                                                  gq.data_ptr(), hq.data_ptr(), p.data_ptr(), None, _stream()))
+        return gq[:n], hq[:n], p[:n]
+    if weight is not None:
+        weight = weight.to(torch.float32).contiguous()
+        if weight.numel() < n:
+            raise ValueError('one weight per row')
+    if row_keys is not None:
+        row_keys = row_keys.to(torch.int64).contiguous()
+        if row_keys.numel() < n:
+            raise ValueError('one key per row')
+    _native.check(_native.lib().sa_boost_grad_ex(
+        margin.data_ptr(), y.contiguous().data_ptr(), mptr, n, None if weight is None else weight.data_ptr(),
+        float(scale_pos_weight), int(shift), None if row_keys is None else row_keys.data_ptr(), int(seed), int(round),
+        THR_ALL if thr is None else int(thr), gq.data_ptr(), hq.data_ptr(), p.data_ptr(), None, _stream()))
     return gq[:n], hq[:n], p[:n]
+
+
+def row_keys(game_id, action_id, device=None):
+    """``sa_boost_row_keys``: the int64 device column ``fm(game_id) + action_id`` (wrapping) that
+    names an action whatever its position (contract item 16), from two host integer columns."""
+    import torch
+    g = np.ascontiguousarray(np.asarray(game_id).ravel().astype(np.int64))
+    a = np.ascontiguousarray(np.asarray(action_id).ravel().astype(np.int64))
+    if len(g) != len(a):
+        raise ValueError('game_id and action_id have different lengths')
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    gd, ad = torch.from_numpy(g).to(dev), torch.from_numpy(a).to(dev)
+    out = torch.empty(max(len(g), 1), dtype=torch.int64, device=dev)
+    _native.check(_native.lib().sa_boost_row_keys(gd.data_ptr(), ad.data_ptr(), len(g), out.data_ptr(), _stream()))
+    return out[:len(g)]
 
 
 def _level(n_nodes: int) -> int:
@@ -397,10 +443,23 @@ def _pad(t, ld, dtype, fill=0):
 
 
 def _hist_level(data: BinnedData, gq, hq, node, node0: int, n_nodes: int, hist, tree, add_totals: bool,
-                launch=None) -> None:
-    """Both histogram kernels of one level into the zeroed ``hist``."""
+                launch=None, cols=None) -> None:
+    """Both histogram kernels of one level into the zeroed ``hist``.  ``cols``: a round's column
+    sample (:func:`_column_lists`): the kernels visit its features only, and the bitmap kernel is
+    launched even for none of them (it carries the level-0 node totals)."""
     lib, d, F = _native.lib(), data.dev, data.n_features
     run = launch or (lambda family, fn, *a: _native.check(fn(*a)))
+    if cols is not None:
+        nb, nn = cols['nb'], cols['nn']
+        run('hist_bits', lib.sa_boost_hist_bits, data.bits.data_ptr() if nb else None,
+            data.bits.shape[1] * 8 if nb else 0, cols['bit_rows'] if nb else None, cols['bit_feat'] if nb else None,
+            nb, gq.data_ptr(), hq.data_ptr(), node.data_ptr(), data.n, node0, n_nodes, F, hist.data_ptr(),
+            tree.data_ptr(), int(add_totals), _stream())
+        if nn:
+            run('hist_bins', lib.sa_boost_hist_bins_ex, data.bins.data_ptr(), data.ld, cols['num_feat'],
+                cols['num_rows'], len(data.num_feat), nn, gq.data_ptr(), hq.data_ptr(), node.data_ptr(), data.n,
+                node0, n_nodes, F, hist.data_ptr(), _stream())
+        return
     nb = len(data.bit_feat)
     run('hist_bits', lib.sa_boost_hist_bits, data.bits.data_ptr() if nb else None,
         data.bits.shape[1] * 8 if nb else 0, d['bit_rows'].data_ptr() if nb else None,
@@ -410,6 +469,37 @@ def _hist_level(data: BinnedData, gq, hq, node, node0: int, n_nodes: int, hist, 
     if nn:
         run('hist_bins', lib.sa_boost_hist_bins, data.bins.data_ptr(), data.ld, d['num_feat'].data_ptr(), nn,
             gq.data_ptr(), hq.data_ptr(), node.data_ptr(), data.n, node0, n_nodes, F, hist.data_ptr(), _stream())
+
+
+def _column_lists(data: BinnedData, seed: int, T: int, colsample_bytree: float):
+    """Every round's column sample as the compacted lists the histogram kernels take, built on
+the host and uploaded once: ``(rounds, mask, lists)`` -- per round the device addresses of its
+    slices (``bit_rows``, ``bit_feat``, ``nb``; ``num_feat``, ``num_rows``, ``nn``) and the
+    ``[T, F]`` uint8 feature mask of the split search (and the uploaded lists, to be kept alive
+    while the addresses are in use).  ``rounds[t]['features']`` is the sample."""
+    import torch
+    F = data.n_features
+    mask = np.zeros((max(T, 1), F), np.uint8)
+    parts = {'bit_rows': [], 'bit_feat': [], 'num_feat': [], 'num_rows': []}
+    rounds = []
+    for t in range(T):
+        S = column_sample(seed, t, F, colsample_bytree)
+        mask[t, S] = 1
+        bsel = np.flatnonzero(mask[t, data.bit_feat] != 0) if len(data.bit_feat) else np.zeros(0, np.int64)
+        nsel = np.flatnonzero(mask[t, data.num_feat] != 0) if len(data.num_feat) else np.zeros(0, np.int64)
+        parts['bit_rows'].append(data.bit_rows[bsel])
+        parts['bit_feat'].append(data.bit_feat[bsel])
+        parts['num_feat'].append(data.num_feat[nsel])
+        parts['num_rows'].append(nsel)
+        rounds.append({'features': S, 'nb': len(bsel), 'nn': len(nsel)})
+    dev = {k: torch.from_numpy(np.concatenate(v + [np.zeros(1, np.int32)]).astype(np.int32)).to(data.device)
+           for k, v in parts.items()}
+    ob = on = 0
+    for r in rounds:
+        r.update(bit_rows=dev['bit_rows'].data_ptr() + 4 * ob, bit_feat=dev['bit_feat'].data_ptr() + 4 * ob,
+                 num_feat=dev['num_feat'].data_ptr() + 4 * on, num_rows=dev['num_rows'].data_ptr() + 4 * on)
+        ob, on = ob + r['nb'], on + r['nn']
+    return rounds, torch.from_numpy(mask).to(data.device), dev
 
 
 def histograms(data: BinnedData, gq, hq, node, n_nodes: int, return_totals: bool = False):
@@ -432,10 +522,13 @@ def histograms(data: BinnedData, gq, hq, node, n_nodes: int, return_totals: bool
 
 
 def best_splits(hist, totals, cuts: Sequence[np.ndarray], reg_lambda: float = 1.0, min_child_weight: float = 1.0,
-                gamma: float = 0.0, learning_rate: float = 0.3) -> np.ndarray:
+                gamma: float = 0.0, learning_rate: float = 0.3, *, reg_alpha: float = 0.0, shift: int = 0,
+                feature_mask=None) -> np.ndarray:
     """``sa_boost_split`` on a level's histograms ``[n_nodes, F, 256, 2]`` and node totals
     ``[n_nodes, 2]``: the level's node records (:data:`NODE_DTYPE`) and, after them, their
-    children's -- ``[3 * n_nodes]`` rows: the level, then the children level in heap order."""
+    children's -- ``[3 * n_nodes]`` rows: the level, then the children level in heap order.
+    With ``reg_alpha``, the quantisation ``shift`` or a ``feature_mask`` (``[F]``, 0 = the feature
+    is no candidate) ``sa_boost_split_ex``."""
     import torch
     n_nodes, F = hist.shape[0], hist.shape[1]
     node0 = _level(n_nodes)
@@ -453,10 +546,22 @@ def best_splits(hist, totals, cuts: Sequence[np.ndarray], reg_lambda: float = 1.
     cs, cf = torch.from_numpy(cut_start).to(dev), torch.from_numpy(flat).to(dev)
     bg = torch.empty(n_nodes * F, dtype=torch.float64, device=dev)
     bc = torch.empty(n_nodes * F, dtype=torch.int32, device=dev)
-    _native.check(_native.lib().sa_boost_split(
-        hist.contiguous().data_ptr(), cs.data_ptr(), cf.data_ptr(), F, node0, n_nodes, 0, float(reg_lambda),
-        float(min_child_weight), float(gamma), float(learning_rate), bg.data_ptr(), bc.data_ptr(),
-        tree.data_ptr(), _stream()))
+    if reg_alpha == 0.0 and shift == 0 and feature_mask is None:
+        _native.check(_native.lib().sa_boost_split(
+            hist.contiguous().data_ptr(), cs.data_ptr(), cf.data_ptr(), F, node0, n_nodes, 0, float(reg_lambda),
+            float(min_child_weight), float(gamma), float(learning_rate), bg.data_ptr(), bc.data_ptr(),
+            tree.data_ptr(), _stream()))
+    else:
+        fm = None
+        if feature_mask is not None:
+            fm = np.ascontiguousarray(np.asarray(feature_mask).astype(bool).astype(np.uint8).ravel())
+            if len(fm) != F:
+                raise ValueError('one mask byte per feature')
+            fm = torch.from_numpy(fm).to(dev)
+        _native.check(_native.lib().sa_boost_split_ex(
+            hist.contiguous().data_ptr(), cs.data_ptr(), cf.data_ptr(), F, node0, n_nodes, 0, float(reg_lambda),
+            float(min_child_weight), float(gamma), float(learning_rate), float(reg_alpha), int(shift),
+            None if fm is None else fm.data_ptr(), bg.data_ptr(), bc.data_ptr(), tree.data_ptr(), _stream()))
     return tree.cpu().numpy().view(NODE_DTYPE).reshape(-1)[node0:node0 + 3 * n_nodes]
 
 
@@ -569,12 +674,123 @@ def metric_score(value: int, eval_metric: str, n_eval: int, n_pos: int) -> float
     return (int(value) / (1 << (95 - _native.SA_METRIC_LOGLOSS_EXP))) / int(n_eval)
 
 
+# ----------------------------------------------------------------------------- weights and sampling (host)
+_M64 = (1 << 64) - 1
+
+
+def fmix64(z: int) -> int:
+    """splitmix64's finaliser on a wrapping uint64 (contract item 16)."""
+    z &= _M64
+    z ^= z >> 30
+    z = (z * 0xBF58476D1CE4E5B9) & _M64
+    z ^= z >> 27
+    z = (z * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def draw(salt: int, seed: int, t: int, key: int) -> int:
+    """The 64-bit draw of ``key`` in round ``t``: ``fm(fm(fm(seed ^ salt) + t) + key)``."""
+    return fmix64(fmix64(fmix64(int(seed) ^ int(salt)) + int(t)) + int(key))
+
+
+def row_threshold(subsample: float) -> int:
+    """``floor(subsample * 2^32)``: a row is in a round's sample iff ``(draw >> 32) < thr``."""
+    return int(math.floor(float(subsample) * 4294967296.0))
+
+
+def column_sample(seed: int, t: int, n_features: int, colsample_bytree: float) -> np.ndarray:
+    """Round ``t``'s features (ascending): the ``k = max(1, floor(colsample_bytree * F))`` with
+    the smallest ``(draw(SALT_COLS, t, f), f)`` (contract item 17)."""
+    F = int(n_features)
+    k = max(1, int(math.floor(float(colsample_bytree) * F)))
+    order = sorted(range(F), key=lambda f: (draw(_native.SA_BOOST_SALT_COLS, seed, t, f), f))
+    return np.array(sorted(order[:k]), np.int32)
+
+
+def weight_shift(mx: float) -> int:
+    """The smallest integer ``e >= 0`` with ``mx <= 2^e`` (contract item 13)."""
+    m, ex = math.frexp(float(mx))  # mx = m * 2^ex, 0.5 <= m < 1
+    return max(0, ex - 1 if m == 0.5 else ex)
+
+
+def _check_weight_range(mx: float, mn: float, finite: bool) -> int:
+    if not finite or not mn >= 0:
+        raise ValueError('sample weights must be finite and not negative')
+    if not 0 < mx <= 2.0 ** _native.SA_BOOST_MAX_SHIFT:
+        raise ValueError(f'the largest effective training weight must be in (0, 2^{_native.SA_BOOST_MAX_SHIFT}]')
+    return weight_shift(mx)
+
+
+def check_weights(sample_weight, n: int, y=None, scale_pos_weight: float = 1.0, rows=None):
+    """A host weight column validated without the device: ``(float32 column, e or None)``.  One
+    entry per row, finite, not negative, and the training rows' (``rows``: host indices or bool
+    mask, default all) largest effective weight ``w * (y ? scale_pos_weight : 1)`` in
+    ``(0, 2^20]``.  Without host labels ``y`` only what holds for any labels is checked and the
+    shift is left to the device (None)."""
+    w64 = np.asarray(sample_weight, np.float64).ravel()
+    if len(w64) != int(n):
+        raise ValueError(f'sample_weight has {len(w64)} entries for {int(n)} rows')
+    with np.errstate(over='ignore'):
+        w = w64.astype(np.float32)
+    sel = w if rows is None else w[np.asarray(rows)]
+    if not len(sel):
+        raise ValueError('no training rows')
+    s = np.float32(float(scale_pos_weight))
+    if y is not None:
+        yy = np.asarray(y).astype(bool).ravel()
+        yy = yy if rows is None else yy[np.asarray(rows)]
+        we = (sel * np.where(yy, s, np.float32(1.0))).astype(np.float32)
+        return w, _check_weight_range(float(we.max()), float(we.min()), bool(np.isfinite(we).all()))
+    # whatever the labels are, the largest effective weight is at least max(w) * min(s, 1)
+    lo = float(np.float32(sel.max() * min(s, np.float32(1.0)))) if np.isfinite(sel).all() else math.nan
+    _check_weight_range(lo, float(sel.min()), bool(np.isfinite(sel).all()))
+    return w, None
+
+
+IMPORTANCE_TYPES = ('gain', 'total_gain', 'weight', 'cover', 'total_cover')
+
+
+def importances(trees: np.ndarray, n_features: int, importance_type: str = 'gain', quant_shift: int = 0) -> np.ndarray:
+    """xgboost's feature importances of node tables, normalised to sum 1 as its scikit-learn
+    wrapper does (all zero when no tree splits): over the split nodes of a feature, their number
+    ('weight'), the sum ('total_gain') or mean ('gain') of their stored gain, the sum
+    ('total_cover') or mean ('cover') of their hessian sums ``H * 2^(quant_shift - 30)``."""
+    if importance_type not in IMPORTANCE_TYPES:
+        raise ValueError(f'importance_type must be one of {IMPORTANCE_TYPES}, not {importance_type!r}')
+    nodes = np.asarray(trees).reshape(-1)
+    nodes = nodes[(nodes['exists'] != 0) & (nodes['feature'] >= 0)]
+    f = nodes['feature'].astype(np.int64)
+    count = np.bincount(f, minlength=n_features).astype(np.float64)
+    if importance_type == 'weight':
+        score = count
+    else:
+        v = nodes['gain'] if 'gain' in importance_type else nodes['H'].astype(np.float64) * 2.0 ** (quant_shift - 30)
+        score = np.bincount(f, weights=v, minlength=n_features)
+        if not importance_type.startswith('total_'):
+            score = np.divide(score, count, out=np.zeros(n_features), where=count > 0)
+    total = score.sum()
+    return (score / total if total > 0 else np.zeros(n_features)).astype(np.float32)
+
+
 # ----------------------------------------------------------------------------- the classifier
-def check_params(params: Dict[str, Any]) -> Dict[str, Any]:
-    unknown = set(params) - set(DEFAULTS)
+def check_params(params: Dict[str, Any], known: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+    """``params`` over the defaults ``known`` (default :data:`ALL_DEFAULTS`), validated; a key
+    outside ``known`` is a ``ValueError``."""
+    known = ALL_DEFAULTS if known is None else known
+    unknown = set(params) - set(known)
     if unknown:
-        raise ValueError(f'unknown parameters {sorted(unknown)} (known: {sorted(DEFAULTS)})')
-    p = {**DEFAULTS, **params}
+        raise ValueError(f'unknown parameters {sorted(unknown)} (known: {sorted(known)})')
+    p = {**ALL_DEFAULTS, **params}
+    for k in ('subsample', 'colsample_bytree'):
+        if not 0.0 < float(p[k]) <= 1.0:
+            raise ValueError(f'{k} must be inside (0, 1]')
+    if not 0.0 <= float(p['reg_alpha']) < math.inf:
+        raise ValueError('reg_alpha must be finite and not negative')
+    if not 0.0 < float(np.float32(float(p['scale_pos_weight']))) < math.inf:
+        raise ValueError('scale_pos_weight must be positive')
+    rs = p['random_state']
+    if isinstance(rs, (bool, float, np.floating)) or not isinstance(rs, (int, np.integer)) or not 0 <= int(rs) < 2 ** 63:
+        raise ValueError('random_state must be an integer in [0, 2^63)')
     if int(p['max_depth']) != p['max_depth'] or not 1 <= int(p['max_depth']) <= MAX_DEPTH:
         raise ValueError(f'max_depth must be in 1..{MAX_DEPTH}')
     if int(p['n_estimators']) < 0:
@@ -583,18 +799,37 @@ def check_params(params: Dict[str, Any]) -> Dict[str, Any]:
         raise ValueError('reg_lambda and min_child_weight must not be negative')
     if not 0.0 < float(p['base_score']) < 1.0:
         raise ValueError('base_score must be inside (0, 1)')
-    return p
+    return {k: p[k] for k in known}
+
+
+def is_tuned(params: Dict[str, Any]) -> bool:
+    """Whether ``params`` hold a tuning parameter away from its neutral value."""
+    return any(k in params and params[k] != v for k, v in TUNING_DEFAULTS.items())
+
+
+def make_classifier(params: Dict[str, Any], **kw) -> 'DeviceGBTClassifier':
+    """The classifier of validated parameters: a :class:`DeviceGBTClassifier` when every tuning
+    parameter is neutral or absent (the plain learner, as it was), else a
+    :class:`TunedGBTClassifier`."""
+    if is_tuned(params):
+        return TunedGBTClassifier(**params, **kw)
+    return DeviceGBTClassifier(**{k: v for k, v in params.items() if k in DEFAULTS}, **kw)
 
 
 class DeviceGBTClassifier:
     """Binary logistic gradient boosting trained by ``csrc/sa_boost.hip`` (scikit-learn shaped).
 
     Parameters (xgboost's names and defaults): ``n_estimators=100, max_depth=3 (1..6),
-    learning_rate=0.3, reg_lambda=1.0, min_child_weight=1.0, gamma=0.0, base_score=0.5``.
+    learning_rate=0.3, reg_lambda=1.0, min_child_weight=1.0, gamma=0.0, base_score=0.5``; any
+    other key is a ``ValueError``.  The tuning parameters of contract items 13-17 belong to the
+    subclass :class:`TunedGBTClassifier`; ``sample_weight`` is an argument of the fit methods of both.
     ``record=True`` keeps every round's probabilities and the margin after it (``record_['p']``,
     ``record_['margin']``, ``[n_estimators, n]`` on the device) for tests on small tables.
     After a fit: ``trees_`` (the node tables), ``cuts_``, ``feature_names_in_``, and on the device
-    the training rows' final ``margin_`` and probabilities ``p_``.
+    the training rows' final ``margin_`` and probabilities ``p_``; ``quant_shift_`` (the e of a
+    weighted fit: the node tables' ``G`` / ``H`` are in units of ``2^(e - 30)``), ``column_samples_``
+    (every kept round's features under ``colsample_bytree``) and ``feature_importances_``
+    (``importance_type`` 'gain', 'total_gain', 'weight', 'cover' or 'total_cover', normalised to sum 1).
 
     Held-out evaluation: with evaluation rows (``eval_rows`` of :meth:`fit_binned` /
     :meth:`fit_blocks`, ``eval_set`` of :meth:`fit`) every finished tree is applied to them and
@@ -605,17 +840,22 @@ class DeviceGBTClassifier:
     >= 1, needs evaluation rows) stops training by :func:`stop_decision`; ``trees_`` then holds
     trees ``0..best_iteration`` and ``margin_`` / ``p_`` are those trees replayed over all rows."""
 
+    PARAMS = DEFAULTS
+
     def __init__(self, record: bool = False, early_stopping_rounds: Optional[int] = None,
-                 eval_metric: str = 'auc', **params) -> None:
-        p = check_params(params)
+                 eval_metric: str = 'auc', importance_type: str = 'gain', **params) -> None:
+        p = check_params(params, self.PARAMS)
+        if importance_type not in IMPORTANCE_TYPES:
+            raise ValueError(f'importance_type must be one of {IMPORTANCE_TYPES}, not {importance_type!r}')
+        self.importance_type = importance_type
         self.early_stopping_rounds, self.eval_metric = check_stop_params(early_stopping_rounds, eval_metric)
-        for k, v in p.items():
+        for k, v in {**TUNING_DEFAULTS, **p}.items():
             setattr(self, k, v)
         self.record = bool(record)
         self._events = None
 
     def get_params(self, deep: bool = True) -> Dict[str, Any]:
-        return {k: getattr(self, k) for k in DEFAULTS}
+        return {k: getattr(self, k) for k in self.PARAMS}
 
     # ------------------------------------------------------------------ fitting
     def _launch(self, family, fn, *args) -> None:
@@ -704,7 +944,25 @@ class DeviceGBTClassifier:
         BinaryMetrics.raise_errors(err)
         return [metric_integer(r, self.eval_metric) for r in h]
 
-    def fit_binned(self, data: BinnedData, y_dev, rows=None, eval_rows=None) -> 'DeviceGBTClassifier':
+    def _weight_shift(self, wd, y, mask, n: int) -> int:
+        """The quantisation shift e of a weighted fit (contract item 13) -- the fit's one host read
+        for it, before the first round: the training rows' effective weights, formed on the device
+        by the gradient kernel's own float32 product, reduced to their maximum, minimum and
+        finiteness."""
+        import torch
+        one = torch.ones((), dtype=torch.float32, device=y.device)
+        we = torch.where(y[:n] != 0, one * float(np.float32(float(self.scale_pos_weight))), one)
+        if wd is not None:
+            we = wd[:n] * we
+        if mask is not None:
+            we = we[mask[:n] != 0]
+        if not we.numel():
+            raise ValueError('no training rows')
+        mx, mn, fin = torch.stack([we.max(), we.min(), torch.isfinite(we).all().to(torch.float32)]).cpu().tolist()
+        return _check_weight_range(mx, mn, bool(fin))
+
+    def fit_binned(self, data: BinnedData, y_dev, rows=None, eval_rows=None, sample_weight=None,
+                   row_keys=None) -> 'DeviceGBTClassifier':
         """Fit on binned data and a device label column (uint8 / bool, at least n rows).  The
         whole fit is enqueued on the current stream -- fixed launch sequences per level and per
         round, no host synchronisation -- and the node tables of all trees are read back once.
@@ -713,7 +971,16 @@ class DeviceGBTClassifier:
         tree is applied to them and scored, still stream-ordered.  With ``early_stopping_rounds``
         the host reads the finished rows of the metric table only when the rule could first
         fire -- after round ``early_stopping_rounds``, then after round ``best + patience`` as
-        known at the previous look -- and launches no round after the stopping round."""
+        known at the previous look -- and launches no round after the stopping round.
+
+        ``sample_weight`` (one float32 per row, device or host; the training rows' are used),
+        ``scale_pos_weight``, ``reg_alpha``, ``subsample`` and ``colsample_bytree`` (contract items
+        13-17) keep the fit bit-identical from run to run: a round's row sample is a counter hash
+        of ``(random_state, round, row key)``.  ``row_keys`` (int64, device or host) names the
+        rows; with it a sampled fit is also the same for any row order.  The default key is the
+        row index, which gives run-to-run identity only: permuting the rows then changes the
+        sample.  With every one of these at its neutral value the launches are the unweighted
+        fit's and nothing is read from the device before the first round."""
         import torch
         esr = self.early_stopping_rounds
         if esr is not None and eval_rows is None:
@@ -734,6 +1001,35 @@ class DeviceGBTClassifier:
                 mask[:n] = rows[:n].to(torch.uint8)
             else:
                 mask[rows.to(torch.int64)] = 1
+        alpha, spw, seed = float(self.reg_alpha), float(self.scale_pos_weight), int(self.random_state)
+        thr, colsample = row_threshold(self.subsample), float(self.colsample_bytree)
+        plain = sample_weight is None and spw == 1.0 and thr == THR_ALL and colsample == 1.0 and alpha == 0.0
+        e, wd, keys, rounds, fmask = 0, None, None, None, None
+        if not plain:
+            if sample_weight is not None:
+                if isinstance(sample_weight, torch.Tensor) and sample_weight.device == dev:
+                    if sample_weight.numel() < n:
+                        raise ValueError(f'sample_weight has {sample_weight.numel()} entries for {n} rows')
+                    wd = sample_weight.reshape(-1).to(torch.float32).contiguous()
+                else:
+                    host = sample_weight.numpy() if isinstance(sample_weight, torch.Tensor) else sample_weight
+                    if rows is None:
+                        host, _ = check_weights(host, n)
+                    elif len(np.asarray(host).ravel()) != n:
+                        raise ValueError(f'sample_weight has {len(np.asarray(host).ravel())} entries for {n} rows')
+                    with np.errstate(over='ignore'):
+                        host = np.ascontiguousarray(np.asarray(host, np.float64).ravel().astype(np.float32))
+                    wd = torch.from_numpy(host).to(dev)
+            if wd is not None or spw != 1.0:
+                e = self._weight_shift(wd, y, mask, n)
+            if row_keys is not None and thr != THR_ALL:
+                keys = torch.as_tensor(row_keys).reshape(-1).to(dev).to(torch.int64).contiguous()
+                if keys.numel() < n:
+                    raise ValueError(f'row_keys has {keys.numel()} entries for {n} rows')
+            if colsample != 1.0:
+                rounds, fmask, _lists = _column_lists(data, seed, T, colsample)
+        wptr = None if wd is None else wd.data_ptr()
+        kptr = None if keys is None else keys.data_ptr()
         margin = torch.full((ld,), float(base_margin(self.base_score)), dtype=torch.float32, device=dev)
         gq = torch.zeros(ld, dtype=torch.int32, device=dev)
         hq = torch.zeros(ld, dtype=torch.int32, device=dev)
@@ -758,22 +1054,39 @@ class DeviceGBTClassifier:
         for t in range(T):
             tree = trees[t]
             pt = P[t] if P is not None else p
-            run('grad', lib.sa_boost_grad, margin.data_ptr(), y.data_ptr(), mptr, n, gq.data_ptr(), hq.data_ptr(),
-                pt.data_ptr(), node.data_ptr(), st)
+            if plain:
+                run('grad', lib.sa_boost_grad, margin.data_ptr(), y.data_ptr(), mptr, n, gq.data_ptr(),
+                    hq.data_ptr(), pt.data_ptr(), node.data_ptr(), st)
+            else:
+                run('grad', lib.sa_boost_grad_ex, margin.data_ptr(), y.data_ptr(), mptr, n, wptr, spw, e, kptr, seed,
+                    t, thr, gq.data_ptr(), hq.data_ptr(), pt.data_ptr(), node.data_ptr(), st)
+            cols = None if rounds is None else rounds[t]
+            fptr = None if fmask is None else fmask[t].data_ptr()
             for level in range(D):
                 nn = 2 ** level
                 node0 = nn - 1
                 h = hist[:nn]
                 h.zero_()
-                _hist_level(data, gq, hq, node, node0, nn, h, tree, level == 0, run)
-                run('split', lib.sa_boost_split, h.data_ptr(), d['cut_start'].data_ptr(), d['cuts'].data_ptr(), F,
-                    node0, nn, 0, float(self.reg_lambda), float(self.min_child_weight), float(self.gamma),
-                    float(self.learning_rate), bg.data_ptr(), bc.data_ptr(), tree.data_ptr(), st)
+                _hist_level(data, gq, hq, node, node0, nn, h, tree, level == 0, run, cols)
+                if plain:
+                    run('split', lib.sa_boost_split, h.data_ptr(), d['cut_start'].data_ptr(), d['cuts'].data_ptr(),
+                        F, node0, nn, 0, float(self.reg_lambda), float(self.min_child_weight), float(self.gamma),
+                        float(self.learning_rate), bg.data_ptr(), bc.data_ptr(), tree.data_ptr(), st)
+                else:
+                    run('split', lib.sa_boost_split_ex, h.data_ptr(), d['cut_start'].data_ptr(),
+                        d['cuts'].data_ptr(), F, node0, nn, 0, float(self.reg_lambda), float(self.min_child_weight),
+                        float(self.gamma), float(self.learning_rate), alpha, e, fptr, bg.data_ptr(), bc.data_ptr(),
+                        tree.data_ptr(), st)
                 run('advance', lib.sa_boost_advance, tree.data_ptr(), node0, nn, d['fmap'].data_ptr(), bits_ptr,
                     bstride, data.bins.data_ptr(), ld, n, node.data_ptr(), None, st)
-            run('split', lib.sa_boost_split, None, None, None, F, 2 ** D - 1, 2 ** D, 1, float(self.reg_lambda),
-                float(self.min_child_weight), float(self.gamma), float(self.learning_rate), None, None,
-                tree.data_ptr(), st)
+            if plain:
+                run('split', lib.sa_boost_split, None, None, None, F, 2 ** D - 1, 2 ** D, 1, float(self.reg_lambda),
+                    float(self.min_child_weight), float(self.gamma), float(self.learning_rate), None, None,
+                    tree.data_ptr(), st)
+            else:
+                run('split', lib.sa_boost_split_ex, None, None, None, F, 2 ** D - 1, 2 ** D, 1,
+                    float(self.reg_lambda), float(self.min_child_weight), float(self.gamma),
+                    float(self.learning_rate), alpha, e, None, None, None, tree.data_ptr(), st)
             run('advance', lib.sa_boost_advance, tree.data_ptr(), 0, 1, None, None, 0, None, ld, n,
                 node.data_ptr(), margin.data_ptr(), st)
             if Mrec is not None:
@@ -812,6 +1125,8 @@ class DeviceGBTClassifier:
             run('grad', lib.sa_boost_grad, margin.data_ptr(), None, None, n, None, None, p.data_ptr(), None, st)
         self.trees_ = trees[:keep].cpu().numpy().view(NODE_DTYPE).reshape(keep, M).copy()  # the one read-back
         self.cuts_ = data.cuts
+        self.quant_shift_ = e
+        self.column_samples_ = None if rounds is None else [r['features'] for r in rounds[:keep]]
         self.feature_names_in_ = np.array(data.names, dtype=object)
         self.n_features_in_ = F
         self.classes_ = np.array([0, 1])
@@ -822,11 +1137,13 @@ class DeviceGBTClassifier:
         self._ensemble = None
         return self
 
-    def fit_blocks(self, blocks, y_dev, rows=None, cuts=None, eval_rows=None) -> 'DeviceGBTClassifier':
+    def fit_blocks(self, blocks, y_dev, rows=None, cuts=None, eval_rows=None, sample_weight=None,
+                   row_keys=None) -> 'DeviceGBTClassifier':
         """Fit on device feature blocks (``ops.features(..., bool_bits=True)``) and a device label
         column.  ``rows``: the training rows (indices or a bool mask), default all; ``cuts``:
         explicit cut lists, default :func:`make_cuts` on the training rows; ``eval_rows``: the
-        evaluation rows (indices or a bool mask), default none."""
+        evaluation rows (indices or a bool mask), default none; ``sample_weight`` / ``row_keys``: as
+        in :meth:`fit_binned`."""
         if self.early_stopping_rounds is not None and eval_rows is None:
             raise ValueError('early_stopping_rounds needs evaluation rows (eval_rows / eval_set)')
         if rows is not None:
@@ -834,17 +1151,26 @@ class DeviceGBTClassifier:
             rows = torch.as_tensor(rows, device=blocks.device)
             if rows.dtype == torch.bool:
                 rows = torch.nonzero(rows[:blocks.n]).reshape(-1)
-        return self.fit_binned(bin_blocks(blocks, cuts, rows), y_dev, rows, eval_rows)
+        return self.fit_binned(bin_blocks(blocks, cuts, rows), y_dev, rows, eval_rows, sample_weight, row_keys)
 
-    def fit(self, X, y, cuts=None, eval_set=None) -> 'DeviceGBTClassifier':
+    def fit(self, X, y, cuts=None, eval_set=None, sample_weight=None, row_keys=None) -> 'DeviceGBTClassifier':
         """Fit on a host frame or 2-D array: uploaded, binned and trained by the same kernels.
         ``eval_set=[(X_val, y_val)]``: exactly one pair with the same columns; the two frames
         are uploaded as one table whose first ``len(X)`` rows train and whose other rows are the
-        evaluation rows (the cuts come from the training rows only)."""
+        evaluation rows (the cuts come from the training rows only).  ``sample_weight`` /
+        ``row_keys``: one entry per row of ``X`` (host), validated before anything is uploaded."""
         if self.early_stopping_rounds is not None and eval_set is None:
             raise ValueError('early_stopping_rounds needs evaluation rows (eval_rows / eval_set)')
         yh = np.asarray(y).astype(bool).astype(np.uint8).ravel()
         n_train = len(yh)
+        if sample_weight is not None:
+            sample_weight, _ = check_weights(sample_weight, n_train, yh, self.scale_pos_weight)
+        if row_keys is not None:
+            row_keys = np.asarray(row_keys).ravel()
+            if len(row_keys) != n_train or row_keys.dtype.kind not in 'iu':
+                raise ValueError('row_keys takes one integer per row')
+            row_keys = row_keys.astype(np.uint64).view(np.int64) if row_keys.dtype == np.uint64 else \
+                row_keys.astype(np.int64)
         rows = eval_rows = None
         if eval_set is not None:
             if len(eval_set) != 1 or len(eval_set[0]) != 2:
@@ -863,6 +1189,10 @@ class DeviceGBTClassifier:
             yh = np.concatenate([yh, yv])
             rows = np.arange(n_train, dtype=np.int64)
             eval_rows = np.arange(n_train, len(yh), dtype=np.int64)
+            if sample_weight is not None:  # the evaluation rows are scored unweighted
+                sample_weight = np.concatenate([sample_weight, np.zeros(len(yv), np.float32)])
+            if row_keys is not None:
+                row_keys = np.concatenate([row_keys, np.zeros(len(yv), np.int64)])
         import torch
         data = bin_host(X, cuts, rows)
         yh = np.ascontiguousarray(yh)
@@ -870,7 +1200,9 @@ class DeviceGBTClassifier:
             raise ValueError('X and y have different lengths')
         yd = torch.zeros(data.ld, dtype=torch.uint8, device=data.device)
         yd[:data.n] = torch.from_numpy(yh).to(data.device)
-        self.fit_binned(data, yd, rows, eval_rows)
+        if sample_weight is not None:
+            sample_weight = torch.from_numpy(np.ascontiguousarray(sample_weight, np.float32)).to(data.device)
+        self.fit_binned(data, yd, rows, eval_rows, sample_weight, row_keys)
         if eval_set is not None:  # the fitted columns are the training frame's
             self.margin_, self.p_ = self.margin_[:n_train], self.p_[:n_train]
             if self.record_ is not None:
@@ -883,6 +1215,16 @@ class DeviceGBTClassifier:
         if not hasattr(self, 'trees_'):
             from sklearn.exceptions import NotFittedError
             raise NotFittedError('this DeviceGBTClassifier is not fitted yet')
+
+    def feature_importances(self, importance_type: Optional[str] = None) -> np.ndarray:
+        """:func:`importances` of the kept trees (default: ``self.importance_type``)."""
+        self._fitted()
+        return importances(self.trees_, int(self.n_features_in_), importance_type or self.importance_type,
+                           int(getattr(self, 'quant_shift_', 0)))
+
+    @property
+    def feature_importances_(self) -> np.ndarray:
+        return self.feature_importances()
 
     def to_xgboost_json(self) -> dict:
         """The kept trees as an xgboost-1.6-shaped model; under early stopping the learner
@@ -945,7 +1287,21 @@ class DeviceGBTClassifier:
         return (self.predict_proba(X)[:, 1] > 0.5).astype(np.int64)
 
 
+class TunedGBTClassifier(DeviceGBTClassifier):
+    """:class:`DeviceGBTClassifier` with the tuning parameters of contract items 13-17 beside its
+    own: ``subsample=1.0, colsample_bytree=1.0, reg_alpha=0.0, scale_pos_weight=1.0,
+    random_state=0`` (xgboost's names and neutral defaults; ``colsample_bylevel`` /
+    ``colsample_bynode`` are not built).  It is a class of its own because the plain classifier's
+    parameter set is fixed: there ``subsample`` stays an unknown parameter.  With every tuning
+    parameter neutral it trains what the plain classifier trains, launch for launch."""
+
+    PARAMS = ALL_DEFAULTS
+
+
 __all__ = ['DeviceGBTClassifier', 'BinnedData', 'NODE_DTYPE', 'make_cuts', 'cuts_from_sample', 'sample_rows',
            'cast32', 'bin_values', 'bin_blocks', 'bin_host', 'gradients', 'histograms', 'best_splits',
            'trees_to_xgboost_json', 'predict_tables', 'base_margin', 'check_params', 'apply_tree',
-           'stop_decision', 'stop_look', 'check_stop_params', 'metric_integer', 'metric_score', 'EVAL_METRICS']
+           'stop_decision', 'stop_look', 'check_stop_params', 'metric_integer', 'metric_score', 'EVAL_METRICS',
+           'fmix64', 'draw', 'row_threshold', 'column_sample', 'weight_shift', 'check_weights', 'importances',
+           'IMPORTANCE_TYPES', 'THR_ALL', 'row_keys',
+           'TunedGBTClassifier', 'TUNING_DEFAULTS', 'ALL_DEFAULTS', 'is_tuned', 'make_classifier']

@@ -119,6 +119,61 @@ __global__ __launch_bounds__(256) void boost_grad_kernel(const float* __restrict
   if (node) node[j] = (!mask || mask[j]) ? 0 : NO_NODE;
 }
 
+// Contract items 13, 14 and 16: the effective weight we = w * (y ? s : 1) folded in before the
+// quantisation at scale 2^(30 - e) (|g| <= we <= 2^e keeps |gq| <= 2^30), and the round's row sample
+// from a counter hash of (seed, round, row key): a row outside it gets gq = hq = 0 -- the histogram
+// kernels skip zero adds -- and still walks the tree.  Each product is its own statement.
+__device__ __host__ __forceinline__ u64 fmix64(u64 z) {  // splitmix64's finaliser
+  z ^= z >> 30;
+  z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27;
+  z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return z;
+}
+
+__global__ __launch_bounds__(256) void boost_grad_ex_kernel(
+    const float* __restrict__ margin, const uint8_t* __restrict__ y, const uint8_t* __restrict__ mask, int64_t n,
+    const float* __restrict__ weight, float spw, float scale, const int64_t* __restrict__ keys, u64 round_base, u64 thr,
+    int32_t* __restrict__ gq, int32_t* __restrict__ hq, float* __restrict__ p_out, uint8_t* __restrict__ node) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const float m = margin[j];
+  const float p = 1.0f / (1.0f + expf(-m));
+  if (p_out) p_out[j] = p;
+  if (gq) {
+    const bool pos = y[j] != 0;
+    const u64 key = keys ? (u64)keys[j] : (u64)j;
+    const bool in = thr > 0xFFFFFFFFull || (fmix64(round_base + key) >> 32) < thr;
+    int32_t gi = 0, hi = 0;
+    if (in) {
+      const float w = weight ? weight[j] : 1.0f;
+      const float we = w * (pos ? spw : 1.0f);
+      const float yy = pos ? 1.0f : 0.0f;
+      const float d = p - yy;
+      const float g = d * we;
+      const float q = p * (1.0f - p);
+      const float h = q * we;
+      const float gs = g * scale;
+      const float hs = h * scale;
+      gi = (int32_t)rintf(gs);
+      hi = (int32_t)rintf(hs);
+    }
+    gq[j] = gi;
+    hq[j] = hi;
+  }
+  if (node) node[j] = (!mask || mask[j]) ? 0 : NO_NODE;
+}
+
+// fit_batch's row keys: fm(game_id) + action_id, wrapping (contract item 16)
+__global__ __launch_bounds__(256) void boost_row_keys_kernel(const int64_t* __restrict__ game_id,
+                                                              const int64_t* __restrict__ action_id, int64_t n,
+                                                              int64_t* __restrict__ keys) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  keys[j] = (int64_t)(fmix64((u64)game_id[j]) + (u64)action_id[j]);
+}
+
 // ---------------------------------------------------------------------------------------- bitmaps
 // One workgroup per tile of HB_TILE rows: the rows' gq, hq and level-local node are staged in LDS
 // once; then work item (column c, word w) -- adjacent threads take adjacent words of one column:
@@ -223,8 +278,11 @@ __global__ __launch_bounds__(256) void boost_bits_fill_kernel(const int32_t* __r
 // Workgroup (x, y): feature group y (fg features), row steps x, x + gridDim.x, ...; an int64
 // histogram [fg][n_nodes][256][2] in LDS, filled with LDS integer atomics from coalesced 4-B
 // reads of 4 rows' bins, flushed once at the end with 64-bit global atomics (zero entries skipped).
+// ROWS: list entry r is row num_rows[r] of the bin matrix (a round's column sample) instead of row r.
+template <bool ROWS>
 __global__ __launch_bounds__(HN_THREADS) void boost_hist_bins_kernel(
-    const uint8_t* __restrict__ bins, int64_t ld, const int32_t* __restrict__ num_feat, int n_num,
+    const uint8_t* __restrict__ bins, int64_t ld, const int32_t* __restrict__ num_feat,
+    const int32_t* __restrict__ num_rows, int n_bin_rows, int n_num,
     const int32_t* __restrict__ gq, const int32_t* __restrict__ hq, const uint8_t* __restrict__ node, int64_t n,
     int node0, int n_nodes, int F, int fg, int64_t* __restrict__ hist) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hn_lds[];
@@ -255,7 +313,12 @@ __global__ __launch_bounds__(HN_THREADS) void boost_hist_bins_kernel(
     }
     if (!any) continue;
     for (int fi = 0; fi < nf; ++fi) {
-      const uint32_t b4 = *reinterpret_cast<const uint32_t*>(bins + (int64_t)(r0 + fi) * ld + j0);
+      int row = r0 + fi;
+      if (ROWS) {
+        row = num_rows[r0 + fi];
+        if (row < 0 || row >= n_bin_rows) continue;  // never read outside the matrix
+      }
+      const uint32_t b4 = *reinterpret_cast<const uint32_t*>(bins + (int64_t)row * ld + j0);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         if (k[q] < 0) continue;
@@ -278,9 +341,13 @@ __global__ __launch_bounds__(HN_THREADS) void boost_hist_bins_kernel(
 }
 
 // ---------------------------------------------------------------------------------------- splits
+// contract item 15: T(G) = G > a ? G - a : (G < -a ? G + a : 0); with a == 0, T(G) == G exactly
+__device__ __forceinline__ double l1_shrink(double G, double a) { return G > a ? G - a : (G < -a ? G + a : 0.0); }
+
 __device__ __forceinline__ double split_gain(double GL, double HL, double GR, double HR, double G, double H,
-                                             double lambda) {
-  return ((GL * GL) / (HL + lambda) + (GR * GR) / (HR + lambda)) - (G * G) / (H + lambda);
+                                             double lambda, double alpha) {
+  const double TL = l1_shrink(GL, alpha), TR = l1_shrink(GR, alpha), TG = l1_shrink(G, alpha);
+  return ((TL * TL) / (HL + lambda) + (TR * TR) / (HR + lambda)) - (TG * TG) / (H + lambda);
 }
 
 // a candidate (gain, index) beats another on a larger gain, then on the lower index
@@ -290,10 +357,12 @@ __device__ __forceinline__ bool better(double ga, int ia, double gb, int ib) {
 
 // One workgroup per (node, feature): the inclusive scan over the feature's bins, the float64 gain
 // of every cut and the best cut (largest gain, then the lowest cut) -> best_gain / best_cut
-// (-inf / -1 when no cut is valid).
+// (-inf / -1 when no cut is valid, and for a feature outside the round's column sample: fmask[f]
+// == 0).  `s` = 2^(e - 30) turns the integer sums into weighted sums (contract item 14).
 __global__ __launch_bounds__(BINS) void boost_scan_kernel(const int64_t* __restrict__ hist,
                                                            const int32_t* __restrict__ cut_start, int F, int node0,
-                                                           double lambda, double mcw,
+                                                           double lambda, double mcw, double alpha, double s,
+                                                           const uint8_t* __restrict__ fmask,
                                                            const sa_boost_node* __restrict__ tree,
                                                            double* __restrict__ best_gain,
                                                            int32_t* __restrict__ best_cut) {
@@ -302,7 +371,7 @@ __global__ __launch_bounds__(BINS) void boost_scan_kernel(const int64_t* __restr
   __shared__ int ri[BINS];
   const int k = blockIdx.y, f = blockIdx.x, i = threadIdx.x;
   const sa_boost_node nd = tree[node0 + k];
-  if (!nd.exists && node0 != 0) {  // (the root always exists)
+  if ((!nd.exists && node0 != 0) || (fmask && !fmask[f])) {  // (the root always exists)
     if (i == 0) {
       best_gain[(int64_t)k * F + f] = -INFINITY;
       best_cut[(int64_t)k * F + f] = -1;
@@ -326,12 +395,11 @@ __global__ __launch_bounds__(BINS) void boost_scan_kernel(const int64_t* __restr
   int idx = -1;
   if (i < m) {
     const int64_t gl = sg[cur][i], hl = sh[cur][i];
-    const double s = 9.313225746154785e-10;  // 2^-30
     const double G = (double)nd.G * s, H = (double)nd.H * s;
     const double GL = (double)gl * s, HL = (double)hl * s;
     const double GR = (double)(nd.G - gl) * s, HR = (double)(nd.H - hl) * s;
     if (HL >= mcw && HR >= mcw) {
-      const double v = split_gain(GL, HL, GR, HR, G, H, lambda);
+      const double v = split_gain(GL, HL, GR, HR, G, H, lambda, alpha);
       if (!isnan(v)) {
         gain = v;
         idx = i;
@@ -360,6 +428,7 @@ __global__ __launch_bounds__(256) void boost_decide_kernel(const int64_t* __rest
                                                             const int32_t* __restrict__ cut_start,
                                                             const float* __restrict__ cuts, int F, int node0,
                                                             int leaf_only, double lambda, double gamma, double eta,
+                                                            double alpha, double s,
                                                             const double* __restrict__ best_gain,
                                                             const int32_t* __restrict__ best_cut,
                                                             sa_boost_node* __restrict__ tree) {
@@ -389,9 +458,8 @@ __global__ __launch_bounds__(256) void boost_decide_kernel(const int64_t* __rest
     __syncthreads();
   }
   if (tid != 0) return;
-  const double s = 9.313225746154785e-10;  // 2^-30
   const double G = (double)nd->G * s, H = (double)nd->H * s;
-  nd->value = (float)(eta * (-(G / (H + lambda))));
+  nd->value = (float)(eta * (-(l1_shrink(G, alpha) / (H + lambda))));
   nd->exists = 1;
   nd->feature = -1;
   nd->cut = -1;
@@ -545,6 +613,32 @@ extern "C" int sa_boost_grad(const float* margin, const uint8_t* y, const uint8_
   return check_launch("boost_grad_kernel");
 }
 
+extern "C" int sa_boost_grad_ex(const float* margin, const uint8_t* y, const uint8_t* row_mask, int64_t n,
+                                const float* weight, float scale_pos_weight, int32_t shift, const int64_t* row_keys,
+                                uint64_t seed, int64_t round, uint64_t thr, int32_t* gq, int32_t* hq, float* p,
+                                uint8_t* node, void* stream) {
+  if (n < 0 || !margin || (gq && (!hq || !y)) || (!gq && hq))
+    return fail(SA_EINVAL, "sa_boost_grad_ex: bad arguments");
+  if (shift < 0 || shift > SA_BOOST_MAX_SHIFT || !(scale_pos_weight > 0.0f) || std::isinf(scale_pos_weight) ||
+      round < 0 || thr > (1ull << 32))
+    return fail(SA_EINVAL, "sa_boost_grad_ex: bad parameters");
+  if (n == 0) return SA_OK;
+  const u64 round_base = fmix64(fmix64((u64)seed ^ SA_BOOST_SALT_ROWS) + (u64)round);
+  hipLaunchKernelGGL(boost_grad_ex_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, margin,
+                     y, row_mask, n, weight, scale_pos_weight, std::ldexp(1.0f, 30 - shift), row_keys, round_base,
+                     (u64)thr, gq, hq, p, node);
+  return check_launch("boost_grad_ex_kernel");
+}
+
+extern "C" int sa_boost_row_keys(const int64_t* game_id, const int64_t* action_id, int64_t n, int64_t* keys,
+                                 void* stream) {
+  if (n < 0 || (n > 0 && (!game_id || !action_id || !keys))) return fail(SA_EINVAL, "sa_boost_row_keys: bad arguments");
+  if (n == 0) return SA_OK;
+  hipLaunchKernelGGL(boost_row_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     game_id, action_id, n, keys);
+  return check_launch("boost_row_keys_kernel");
+}
+
 extern "C" int sa_boost_hist_bits(const uint64_t* bits, int64_t bits_stride, const int32_t* bit_rows,
                                   const int32_t* bit_feat, int32_t n_bool, const int32_t* gq, const int32_t* hq,
                                   const uint8_t* node, int64_t n, int32_t node0, int32_t n_nodes, int32_t n_features,
@@ -571,10 +665,12 @@ extern "C" int sa_boost_hist_bits(const uint64_t* bits, int64_t bits_stride, con
   return check_launch("boost_bits_fill_kernel");
 }
 
-extern "C" int sa_boost_hist_bins(const uint8_t* bins, int64_t ld, const int32_t* num_feat, int32_t n_num,
-                                  const int32_t* gq, const int32_t* hq, const uint8_t* node, int64_t n, int32_t node0,
-                                  int32_t n_nodes, int32_t n_features, int64_t* hist, void* stream) {
-  if (n < 0 || n_num < 0 || n_features < 1 || ld < n || ld % 4 != 0 || !level_ok(node0, n_nodes))
+namespace {
+int hist_bins(const uint8_t* bins, int64_t ld, const int32_t* num_feat, const int32_t* num_rows, int32_t n_bin_rows,
+              int32_t n_num, const int32_t* gq, const int32_t* hq, const uint8_t* node, int64_t n, int32_t node0,
+              int32_t n_nodes, int32_t n_features, int64_t* hist, void* stream) {
+  if (n < 0 || n_num < 0 || n_features < 1 || ld < n || ld % 4 != 0 || !level_ok(node0, n_nodes) ||
+      (num_rows && n_bin_rows < 1))
     return fail(SA_EINVAL, "sa_boost_hist_bins: bad sizes");
   if (!gq || !hq || !node || !hist || ((uintptr_t)node & 3u))
     return fail(SA_EINVAL, "sa_boost_hist_bins: null or misaligned pointer");
@@ -589,16 +685,39 @@ extern "C" int sa_boost_hist_bins(const uint8_t* bins, int64_t ld, const int32_t
   int64_t gx = (int64_t)device_cus(current_device()) * 4 / groups;
   if (gx < 8) gx = 8;
   if (gx > steps) gx = steps;
-  hipLaunchKernelGGL(boost_hist_bins_kernel, dim3((unsigned)gx, (unsigned)groups), dim3(HN_THREADS), lds,
-                     (hipStream_t)stream, bins, ld, num_feat, n_num, gq, hq, node, n, node0, n_nodes, n_features, fg,
-                     hist);
+  if (num_rows)
+    hipLaunchKernelGGL((boost_hist_bins_kernel<true>), dim3((unsigned)gx, (unsigned)groups), dim3(HN_THREADS), lds,
+                       (hipStream_t)stream, bins, ld, num_feat, num_rows, n_bin_rows, n_num, gq, hq, node, n, node0,
+                       n_nodes, n_features, fg, hist);
+  else
+    hipLaunchKernelGGL((boost_hist_bins_kernel<false>), dim3((unsigned)gx, (unsigned)groups), dim3(HN_THREADS), lds,
+                       (hipStream_t)stream, bins, ld, num_feat, num_rows, n_bin_rows, n_num, gq, hq, node, n, node0,
+                       n_nodes, n_features, fg, hist);
   return check_launch("boost_hist_bins_kernel");
 }
+}  // namespace
 
-extern "C" int sa_boost_split(const int64_t* hist, const int32_t* cut_start, const float* cuts, int32_t n_features,
-                              int32_t node0, int32_t n_nodes, int32_t leaf_only, double reg_lambda,
-                              double min_child_weight, double gamma, double learning_rate, double* best_gain,
-                              int32_t* best_cut, sa_boost_node* tree, void* stream) {
+extern "C" int sa_boost_hist_bins(const uint8_t* bins, int64_t ld, const int32_t* num_feat, int32_t n_num,
+                                  const int32_t* gq, const int32_t* hq, const uint8_t* node, int64_t n, int32_t node0,
+                                  int32_t n_nodes, int32_t n_features, int64_t* hist, void* stream) {
+  return hist_bins(bins, ld, num_feat, nullptr, 0, n_num, gq, hq, node, n, node0, n_nodes, n_features, hist, stream);
+}
+
+extern "C" int sa_boost_hist_bins_ex(const uint8_t* bins, int64_t ld, const int32_t* num_feat, const int32_t* num_rows,
+                                     int32_t n_bin_rows, int32_t n_num, const int32_t* gq, const int32_t* hq,
+                                     const uint8_t* node, int64_t n, int32_t node0, int32_t n_nodes,
+                                     int32_t n_features, int64_t* hist, void* stream) {
+  return hist_bins(bins, ld, num_feat, num_rows, n_bin_rows, n_num, gq, hq, node, n, node0, n_nodes, n_features, hist,
+                   stream);
+}
+
+extern "C" int sa_boost_split_ex(const int64_t* hist, const int32_t* cut_start, const float* cuts, int32_t n_features,
+                                 int32_t node0, int32_t n_nodes, int32_t leaf_only, double reg_lambda,
+                                 double min_child_weight, double gamma, double learning_rate, double reg_alpha,
+                                 int32_t shift, const uint8_t* feature_mask, double* best_gain, int32_t* best_cut,
+                                 sa_boost_node* tree, void* stream) {
+  if (!(reg_alpha >= 0.0) || std::isinf(reg_alpha) || shift < 0 || shift > SA_BOOST_MAX_SHIFT)
+    return fail(SA_EINVAL, "sa_boost_split: bad parameters");
   if (n_features < 1 || n_nodes < 1 || n_nodes > 2 * SA_BOOST_MAX_LEVEL_NODES || (n_nodes & (n_nodes - 1)) ||
       node0 != n_nodes - 1)
     return fail(SA_EINVAL, "sa_boost_split: bad sizes");
@@ -608,14 +727,24 @@ extern "C" int sa_boost_split(const int64_t* hist, const int32_t* cut_start, con
   if (!(reg_lambda >= 0.0) || !(min_child_weight >= 0.0) || std::isnan(gamma) || std::isnan(learning_rate))
     return fail(SA_EINVAL, "sa_boost_split: bad parameters");
   hipStream_t st = (hipStream_t)stream;
+  const double s = std::ldexp(1.0, shift - 30);  // an exact power of two: 2^-30 with no weights
   if (!leaf_only) {
     hipLaunchKernelGGL(boost_scan_kernel, dim3((unsigned)n_features, (unsigned)n_nodes), dim3(BINS), 0, st, hist,
-                       cut_start, n_features, node0, reg_lambda, min_child_weight, tree, best_gain, best_cut);
+                       cut_start, n_features, node0, reg_lambda, min_child_weight, reg_alpha, s, feature_mask, tree,
+                       best_gain, best_cut);
     if (int rc = check_launch("boost_scan_kernel")) return rc;
   }
   hipLaunchKernelGGL(boost_decide_kernel, dim3((unsigned)n_nodes), dim3(256), 0, st, hist, cut_start, cuts, n_features,
-                     node0, leaf_only, reg_lambda, gamma, learning_rate, best_gain, best_cut, tree);
+                     node0, leaf_only, reg_lambda, gamma, learning_rate, reg_alpha, s, best_gain, best_cut, tree);
   return check_launch("boost_decide_kernel");
+}
+
+extern "C" int sa_boost_split(const int64_t* hist, const int32_t* cut_start, const float* cuts, int32_t n_features,
+                              int32_t node0, int32_t n_nodes, int32_t leaf_only, double reg_lambda,
+                              double min_child_weight, double gamma, double learning_rate, double* best_gain,
+                              int32_t* best_cut, sa_boost_node* tree, void* stream) {
+  return sa_boost_split_ex(hist, cut_start, cuts, n_features, node0, n_nodes, leaf_only, reg_lambda, min_child_weight,
+                           gamma, learning_rate, 0.0, 0, nullptr, best_gain, best_cut, tree, stream);
 }
 
 extern "C" int sa_boost_advance(const sa_boost_node* tree, int32_t node0, int32_t n_nodes, const int32_t* fmap,

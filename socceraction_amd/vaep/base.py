@@ -241,8 +241,12 @@ class VAEP:
     def _fit_device(self, X, y, train_idx, val_idx, val_size, tree_params, fit_params=None) -> 'VAEP':
         """``fit(..., learner='device')``: one :class:`socceraction_amd.boost.DeviceGBTClassifier`
         per label column on the reference's split of the rows.  The frame is uploaded and binned
-        once (cuts from the training rows).  ``fit_params`` is read for ``early_stopping_rounds``
-        and ``eval_metric`` only: with ``early_stopping_rounds`` the held-out rows are the
+        once (cuts from the training rows).  ``tree_params`` takes the learner's parameters,
+        ``subsample``, ``colsample_bytree``, ``reg_alpha``, ``scale_pos_weight`` and ``random_state``
+        among them.  ``fit_params`` is read for ``sample_weight`` (row-aligned with ``X``; the
+        training rows' weights are used), ``row_keys`` (one integer per row of ``X``, naming the
+        rows for ``subsample``; default the row index), ``early_stopping_rounds`` and
+        ``eval_metric``: with ``early_stopping_rounds`` the held-out rows are the
         evaluation rows of every round and the best round's model is kept (the reference's
         default ``fit``); without, all trees are trained.  Either way the held-out rows are scored
         once with the kept trees (``self.device_eval_[col]``,
@@ -254,8 +258,22 @@ class VAEP:
         stop = self._device_stop_params(fp.get('early_stopping_rounds'), fp.get('eval_metric', 'auc'),
                                         val_size > 0 and len(val_idx) > 0)
         train_idx = np.sort(np.asarray(train_idx, np.int64))
+        weight, keys = fp.get('sample_weight'), fp.get('row_keys')
+        if weight is not None:  # every label's effective weights, before any device call
+            for col in list(y.columns):
+                weight, _ = boost.check_weights(weight, len(X), y[col].to_numpy(), params['scale_pos_weight'],
+                                                train_idx)
+        if keys is not None:
+            keys = np.asarray(keys).ravel()
+            if len(keys) != len(X) or keys.dtype.kind not in 'iu':
+                raise ValueError('row_keys takes one integer per row')
+            keys = keys.astype(np.uint64).view(np.int64) if keys.dtype == np.uint64 else keys.astype(np.int64)
         data = boost.bin_host(X, rows=train_idx)
         rows = torch.from_numpy(train_idx).to(data.device)
+        if weight is not None:
+            weight = torch.from_numpy(np.ascontiguousarray(weight)).to(data.device)
+        if keys is not None:
+            keys = torch.from_numpy(np.ascontiguousarray(keys)).to(data.device)
         eval_rows = None
         if stop['early_stopping_rounds'] is not None:
             eval_rows = torch.from_numpy(np.sort(np.asarray(val_idx, np.int64))).to(data.device)
@@ -263,8 +281,8 @@ class VAEP:
         for col in list(y.columns):
             yh = np.zeros(data.ld, np.uint8)
             yh[:data.n] = y[col].to_numpy().astype(bool)
-            clf = boost.DeviceGBTClassifier(**params, **stop).fit_binned(
-                data, torch.from_numpy(yh).to(data.device), rows, eval_rows)
+            clf = boost.make_classifier(params, **stop).fit_binned(
+                data, torch.from_numpy(yh).to(data.device), rows, eval_rows, weight, keys)
             self.__models[col] = clf
             if val_size > 0 and len(val_idx):
                 p = clf.predict_proba(X.iloc[val_idx])[:, 1]
@@ -274,14 +292,19 @@ class VAEP:
     def fit_batch(self, games: pd.DataFrame, actions: pd.DataFrame, learner: str = 'device',
                   val_size: float = 0.0, nr_actions: int = 10,
                   tree_params: Optional[Dict[str, Any]] = None,
-                  early_stopping_rounds: Optional[int] = None, eval_metric: str = 'auc') -> 'VAEP':
+                  early_stopping_rounds: Optional[int] = None, eval_metric: str = 'auc',
+                  sample_weight=None) -> 'VAEP':
         """Fit both learners on many games (contiguous per game) without the feature frame: one
         ``ActionBatch``, the features as bitmaps plus numeric blocks and the labels all on the
         device; only the cut sample and the finished trees cross the link.  ``val_size``: the
         share of rows (the reference's random split) held out and scored once after training
         into ``self.device_eval_``.  ``early_stopping_rounds`` (needs ``val_size > 0``): the
         held-out rows are evaluated after every round by ``eval_metric`` ('auc' or 'logloss')
-        and the best round's model is kept.  Built-in transformers only."""
+        and the best round's model is kept.  ``sample_weight``: one weight per row of ``actions``
+        (every entry finite and not negative).  With ``subsample`` in ``tree_params`` a round's
+        row sample is keyed by ``fm(game_id) + action_id``, built on the device, so it belongs to
+        the action, not to its position: the model is the same for any game order or batch
+        split (as long as the cuts agree).  Built-in transformers only."""
         from .. import boost, metrics
         from ..trees import TreeEnsemble
         import torch
@@ -289,6 +312,11 @@ class VAEP:
             raise ValueError(f'A {learner} learner is not supported by fit_batch')
         params = boost.check_params(dict(tree_params or {}))  # before any device call
         stop = self._device_stop_params(early_stopping_rounds, eval_metric, val_size > 0)
+        if sample_weight is not None:
+            sample_weight, _ = boost.check_weights(sample_weight, len(actions), None, params['scale_pos_weight'])
+        sampled = boost.row_threshold(params['subsample']) != boost.THR_ALL
+        if sampled and not {'game_id', 'action_id'} <= set(actions.columns):
+            raise ValueError('subsample needs the game_id and action_id columns (they key the row sample)')
         known, unknown = self._split_xfns()
         if unknown:
             raise ValueError('fit_batch needs built-in feature transformers')
@@ -303,11 +331,16 @@ class VAEP:
             rows = torch.from_numpy(np.sort(idx[:cut])).to(ab.device)
             val_rows = torch.from_numpy(np.sort(idx[cut + 1:])).to(ab.device)
         data = boost.bin_blocks(fb, rows=rows)
+        keys = boost.row_keys(actions['game_id'].to_numpy(), actions['action_id'].to_numpy(), ab.device) \
+            if sampled else None
+        if sample_weight is not None:
+            sample_weight = torch.from_numpy(np.ascontiguousarray(sample_weight)).to(ab.device)
         self.device_eval_ = {}
         for col in ('scores', 'concedes'):
             ycol = getattr(lb, col)
-            clf = boost.DeviceGBTClassifier(**params, **stop).fit_binned(
-                data, ycol, rows, val_rows if stop['early_stopping_rounds'] is not None else None)
+            clf = boost.make_classifier(params, **stop).fit_binned(
+                data, ycol, rows, val_rows if stop['early_stopping_rounds'] is not None else None,
+                sample_weight, keys)
             self.__models[col] = clf
             if val_rows is not None and val_rows.numel():
                 p = TreeEnsemble.from_model(clf).predict_blocks(fb)
