@@ -32,7 +32,8 @@ from __future__ import annotations
 
 import ctypes
 import math
-from dataclasses import dataclass
+from collections import namedtuple
+from dataclasses import dataclass, make_dataclass
 from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
@@ -285,6 +286,21 @@ def _ld(n: int) -> int:
     return max(16, (n + 15) // 16 * 16)
 
 
+def _flat_cuts(cuts: Sequence[np.ndarray]):
+    """``(cut_start [F + 1] int32, every feature's cuts in one float32 array)`` as the kernels take them."""
+    cut_start = np.zeros(len(cuts) + 1, np.int32)
+    cut_start[1:] = np.cumsum([len(c) for c in cuts])
+    return cut_start, np.concatenate(list(cuts) + [np.zeros(1, np.float32)]).astype(np.float32)
+
+
+def _padded_block(cols, n: int, ld: int, dtype) -> np.ndarray:
+    """Host columns as one zero-padded ``[1, C, ld]`` block of ``dtype``."""
+    h = np.zeros((1, len(cols), ld), dtype)
+    for r, c in enumerate(cols):
+        h[0, r, :n] = c
+    return h
+
+
 def _bin(names, kinds_cols, bits, f_blk, i_blk, f32: bool, n: int, cuts) -> BinnedData:
     """kinds_cols[f] = (kind, column in its block / bitmap row)."""
     import torch
@@ -294,9 +310,7 @@ def _bin(names, kinds_cols, bits, f_blk, i_blk, f32: bool, n: int, cuts) -> Binn
     F = len(names)
     cuts = check_cuts(cuts, F)
     ld = _ld(n)
-    cut_start = np.zeros(F + 1, np.int32)
-    cut_start[1:] = np.cumsum([len(c) for c in cuts])
-    flat = np.concatenate(cuts + [np.zeros(1, np.float32)]).astype(np.float32)
+    cut_start, flat = _flat_cuts(cuts)
     bool_f = [f for f, (k, _) in enumerate(kinds_cols) if k == 'b']
     num_f = [f for f, (k, _) in enumerate(kinds_cols) if k != 'b']
     for f in bool_f:
@@ -364,12 +378,7 @@ def bin_host(X, cuts: Optional[Sequence[np.ndarray]] = None, rows=None, device=N
     for r, c in enumerate(per['b']):
         pk = np.packbits(c.astype(bool), bitorder='little')
         hb[r, :len(pk)] = pk
-    hf = np.zeros((1, len(per['f']), ld), np.float64)
-    for r, c in enumerate(per['f']):
-        hf[0, r, :n] = c
-    hi = np.zeros((1, len(per['i']), ld), np.int64)
-    for r, c in enumerate(per['i']):
-        hi[0, r, :n] = c
+    hf, hi = _padded_block(per['f'], n, ld, np.float64), _padded_block(per['i'], n, ld, np.int64)
     return _bin(names, kc, torch.from_numpy(hb.view(np.int64)).to(dev), torch.from_numpy(hf).to(dev),
                 torch.from_numpy(hi).to(dev), False, n, cuts)
 
@@ -378,6 +387,95 @@ def bin_host(X, cuts: Optional[Sequence[np.ndarray]] = None, rows=None, device=N
 def _stream():
     from .batch import stream_handle
     return stream_handle()
+
+
+def _run(family, fn, *args) -> None:
+    """A launch outside a fit (``DeviceGBTClassifier._launch`` without events)."""
+    _native.check(fn(*args))
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+# What a fit (or one launch) has beyond the plain learner's (contract items 13-16): the float32 device
+# weight column (None: every weight 1), scale_pos_weight, the quantisation shift e (the scale is
+# 2^(30 - e)), the int64 device key column (None: a row's key is its index), the seed, the row sample's
+# raw threshold, the L1 penalty.  Where a Tuning is expected, None means plain: the entry points without `_ex`.
+Tuning = namedtuple('Tuning', 'weight scale_pos_weight shift keys seed thr reg_alpha',
+                    defaults=(None, 1.0, 0, None, 0, THR_ALL, 0.0))
+
+
+class ColumnSamples:
+    """Every round's column sample (contract item 17) as the compacted int32 device lists the
+    histogram kernels take, built on the host, uploaded once and sliced once: ``rounds[t]`` holds
+    round t's views ``(bit_rows, bit_feat, n_bool, num_feat, num_rows, n_num)`` of them.
+    ``mask [T, F]`` (uint8, on the device) is the split search's; ``features[t]`` is the sample."""
+
+    def __init__(self, data: BinnedData, seed: int, T: int, colsample_bytree: float) -> None:
+        import torch
+        F = data.n_features
+        mask = np.zeros((max(T, 1), F), np.uint8)
+        lists = [], [], [], []  # bit_rows, bit_feat, num_feat, num_rows
+        self.features, bit_off, num_off = [], [0], [0]
+        for t in range(T):
+            self.features.append(column_sample(seed, t, F, colsample_bytree))
+            mask[t, self.features[t]] = 1
+            bsel, nsel = np.flatnonzero(mask[t, data.bit_feat]), np.flatnonzero(mask[t, data.num_feat])
+            for part, v in zip(lists, (data.bit_rows[bsel], data.bit_feat[bsel], data.num_feat[nsel], nsel)):
+                part.append(v)
+            bit_off.append(bit_off[t] + len(bsel))
+            num_off.append(num_off[t] + len(nsel))
+        br, bf, nf, nr = (  # (a spare entry: no list is empty)
+            torch.from_numpy(np.concatenate(v + [np.zeros(1, np.int32)]).astype(np.int32)).to(data.device)
+            for v in lists)
+        self.rounds = [(br[bit_off[t]:], bf[bit_off[t]:], bit_off[t + 1] - bit_off[t], nf[num_off[t]:],
+                        nr[num_off[t]:], num_off[t + 1] - num_off[t]) for t in range(T)]
+        self.mask = torch.from_numpy(mask).to(data.device)
+
+
+def _grad(run, st, margin, y, mask, n: int, gq, hq, p, node, tu: Optional[Tuning] = None, t: int = 0) -> None:
+    """Round ``t``'s gradient launch: ``sa_boost_grad``, with a :class:`Tuning` ``sa_boost_grad_ex``."""
+    lib, out = _native.lib(), (_ptr(gq), _ptr(hq), _ptr(p), _ptr(node), st)
+    if tu is None:
+        run('grad', lib.sa_boost_grad, margin.data_ptr(), _ptr(y), _ptr(mask), n, *out)
+    else:
+        run('grad', lib.sa_boost_grad_ex, margin.data_ptr(), _ptr(y), _ptr(mask), n, _ptr(tu.weight),
+            tu.scale_pos_weight, tu.shift, _ptr(tu.keys), tu.seed, t, tu.thr, *out)
+
+
+def _hist(run, st, data: BinnedData, gq, hq, node, n_nodes: int, hist, tree, add_totals: bool, cols=None) -> None:
+    """Both histogram kernels of the level of ``n_nodes`` nodes into the zeroed ``hist``.  This pair
+    is chosen by the column sample, not by the :class:`Tuning`: with ``cols`` (a round of
+    :class:`ColumnSamples`) the kernels visit its features only (``sa_boost_hist_bins_ex``), and the
+    bitmap kernel is launched even for none of them (it carries the level-0 node totals)."""
+    lib, d = _native.lib(), data.dev
+    bit_rows, bit_feat, nb, num_feat, num_rows, nn = cols or (
+        d['bit_rows'], d['bit_feat'], len(data.bit_feat), d['num_feat'], None, len(data.num_feat))
+    level = (gq.data_ptr(), hq.data_ptr(), node.data_ptr(), data.n, n_nodes - 1, n_nodes, data.n_features,
+             hist.data_ptr())
+    run('hist_bits', lib.sa_boost_hist_bits, data.bits.data_ptr() if nb else None,
+        data.bits.shape[1] * 8 if nb else 0, bit_rows.data_ptr() if nb else None, bit_feat.data_ptr() if nb else None,
+        nb, *level, tree.data_ptr(), int(add_totals), st)
+    if nn and cols is None:
+        run('hist_bins', lib.sa_boost_hist_bins, data.bins.data_ptr(), data.ld, num_feat.data_ptr(), nn, *level, st)
+    elif nn:
+        run('hist_bins', lib.sa_boost_hist_bins_ex, data.bins.data_ptr(), data.ld, num_feat.data_ptr(),
+            num_rows.data_ptr(), len(data.num_feat), nn, *level, st)
+
+
+def _split(run, st, hist, cut_start, cuts, F: int, n_nodes: int, params, bg, bc, tree, tu: Optional[Tuning] = None,
+           fmask=None, leaf_only: bool = False) -> None:
+    """The split search of the level of ``n_nodes`` nodes (``leaf_only``: its leaf values only);
+    ``params = (reg_lambda, min_child_weight, gamma, learning_rate)``.  With a :class:`Tuning`
+    ``sa_boost_split_ex``: its L1 penalty and shift, and the ``[F]`` uint8 device mask ``fmask``."""
+    lib = _native.lib()
+    head = (_ptr(hist), _ptr(cut_start), _ptr(cuts), F, n_nodes - 1, n_nodes, int(leaf_only), *params)
+    tail = (_ptr(bg), _ptr(bc), tree.data_ptr(), st)
+    if tu is None:
+        run('split', lib.sa_boost_split, *head, *tail)
+    else:
+        run('split', lib.sa_boost_split_ex, *head, tu.reg_alpha, tu.shift, _ptr(fmask), *tail)
 
 
 def gradients(margin, y, row_mask=None, *, weight=None, scale_pos_weight: float = 1.0, shift: int = 0,
@@ -394,23 +492,19 @@ def gradients(margin, y, row_mask=None, *, weight=None, scale_pos_weight: float 
     gq = torch.empty(max(n, 1), dtype=torch.int32, device=margin.device)
     hq = torch.empty_like(gq)
     p = torch.empty(max(n, 1), dtype=torch.float32, device=margin.device)
-    mptr = None if row_mask is None else row_mask.data_ptr()
-    if weight is None and scale_pos_weight == 1.0 and shift == 0 and row_keys is None and thr is None:
-        _native.check(_native.lib().sa_boost_grad(margin.data_ptr(), y.contiguous().data_ptr(), mptr, n,
-                                                  gq.data_ptr(), hq.data_ptr(), p.data_ptr(), None, _stream()))
-        return gq[:n], hq[:n], p[:n]
-    if weight is not None:
-        weight = weight.to(torch.float32).contiguous()
-        if weight.numel() < n:
-            raise ValueError('one weight per row')
-    if row_keys is not None:
-        row_keys = row_keys.to(torch.int64).contiguous()
-        if row_keys.numel() < n:
-            raise ValueError('one key per row')
-    _native.check(_native.lib().sa_boost_grad_ex(
-        margin.data_ptr(), y.contiguous().data_ptr(), mptr, n, None if weight is None else weight.data_ptr(),
-        float(scale_pos_weight), int(shift), None if row_keys is None else row_keys.data_ptr(), int(seed), int(round),
-        THR_ALL if thr is None else int(thr), gq.data_ptr(), hq.data_ptr(), p.data_ptr(), None, _stream()))
+    tu = None
+    if not (weight is None and scale_pos_weight == 1.0 and shift == 0 and row_keys is None and thr is None):
+        if weight is not None:
+            weight = weight.to(torch.float32).contiguous()
+            if weight.numel() < n:
+                raise ValueError('one weight per row')
+        if row_keys is not None:
+            row_keys = row_keys.to(torch.int64).contiguous()
+            if row_keys.numel() < n:
+                raise ValueError('one key per row')
+        tu = Tuning(weight, float(scale_pos_weight), int(shift), row_keys, int(seed),
+                    THR_ALL if thr is None else int(thr))
+    _grad(_run, _stream(), margin, y.contiguous(), row_mask, n, gq, hq, p, None, tu=tu, t=int(round))
     return gq[:n], hq[:n], p[:n]
 
 
@@ -442,66 +536,6 @@ def _pad(t, ld, dtype, fill=0):
     return out
 
 
-def _hist_level(data: BinnedData, gq, hq, node, node0: int, n_nodes: int, hist, tree, add_totals: bool,
-                launch=None, cols=None) -> None:
-    """Both histogram kernels of one level into the zeroed ``hist``.  ``cols``: a round's column
-    sample (:func:`_column_lists`): the kernels visit its features only, and the bitmap kernel is
-    launched even for none of them (it carries the level-0 node totals)."""
-    lib, d, F = _native.lib(), data.dev, data.n_features
-    run = launch or (lambda family, fn, *a: _native.check(fn(*a)))
-    if cols is not None:
-        nb, nn = cols['nb'], cols['nn']
-        run('hist_bits', lib.sa_boost_hist_bits, data.bits.data_ptr() if nb else None,
-            data.bits.shape[1] * 8 if nb else 0, cols['bit_rows'] if nb else None, cols['bit_feat'] if nb else None,
-            nb, gq.data_ptr(), hq.data_ptr(), node.data_ptr(), data.n, node0, n_nodes, F, hist.data_ptr(),
-            tree.data_ptr(), int(add_totals), _stream())
-        if nn:
-            run('hist_bins', lib.sa_boost_hist_bins_ex, data.bins.data_ptr(), data.ld, cols['num_feat'],
-                cols['num_rows'], len(data.num_feat), nn, gq.data_ptr(), hq.data_ptr(), node.data_ptr(), data.n,
-                node0, n_nodes, F, hist.data_ptr(), _stream())
-        return
-    nb = len(data.bit_feat)
-    run('hist_bits', lib.sa_boost_hist_bits, data.bits.data_ptr() if nb else None,
-        data.bits.shape[1] * 8 if nb else 0, d['bit_rows'].data_ptr() if nb else None,
-        d['bit_feat'].data_ptr() if nb else None, nb, gq.data_ptr(), hq.data_ptr(), node.data_ptr(), data.n,
-        node0, n_nodes, F, hist.data_ptr(), tree.data_ptr(), int(add_totals), _stream())
-    nn = len(data.num_feat)
-    if nn:
-        run('hist_bins', lib.sa_boost_hist_bins, data.bins.data_ptr(), data.ld, d['num_feat'].data_ptr(), nn,
-            gq.data_ptr(), hq.data_ptr(), node.data_ptr(), data.n, node0, n_nodes, F, hist.data_ptr(), _stream())
-
-
-def _column_lists(data: BinnedData, seed: int, T: int, colsample_bytree: float):
-    """Every round's column sample as the compacted lists the histogram kernels take, built on
-the host and uploaded once: ``(rounds, mask, lists)`` -- per round the device addresses of its
-    slices (``bit_rows``, ``bit_feat``, ``nb``; ``num_feat``, ``num_rows``, ``nn``) and the
-    ``[T, F]`` uint8 feature mask of the split search (and the uploaded lists, to be kept alive
-    while the addresses are in use).  ``rounds[t]['features']`` is the sample."""
-    import torch
-    F = data.n_features
-    mask = np.zeros((max(T, 1), F), np.uint8)
-    parts = {'bit_rows': [], 'bit_feat': [], 'num_feat': [], 'num_rows': []}
-    rounds = []
-    for t in range(T):
-        S = column_sample(seed, t, F, colsample_bytree)
-        mask[t, S] = 1
-        bsel = np.flatnonzero(mask[t, data.bit_feat] != 0) if len(data.bit_feat) else np.zeros(0, np.int64)
-        nsel = np.flatnonzero(mask[t, data.num_feat] != 0) if len(data.num_feat) else np.zeros(0, np.int64)
-        parts['bit_rows'].append(data.bit_rows[bsel])
-        parts['bit_feat'].append(data.bit_feat[bsel])
-        parts['num_feat'].append(data.num_feat[nsel])
-        parts['num_rows'].append(nsel)
-        rounds.append({'features': S, 'nb': len(bsel), 'nn': len(nsel)})
-    dev = {k: torch.from_numpy(np.concatenate(v + [np.zeros(1, np.int32)]).astype(np.int32)).to(data.device)
-           for k, v in parts.items()}
-    ob = on = 0
-    for r in rounds:
-        r.update(bit_rows=dev['bit_rows'].data_ptr() + 4 * ob, bit_feat=dev['bit_feat'].data_ptr() + 4 * ob,
-                 num_feat=dev['num_feat'].data_ptr() + 4 * on, num_rows=dev['num_rows'].data_ptr() + 4 * on)
-        ob, on = ob + r['nb'], on + r['nn']
-    return rounds, torch.from_numpy(mask).to(data.device), dev
-
-
 def histograms(data: BinnedData, gq, hq, node, n_nodes: int, return_totals: bool = False):
     """The dense ``[n_nodes, F, 256, 2]`` int64 histogram of one level: ``node`` holds every row's
     level-local node (0 .. n_nodes-1; ``NO_NODE`` = the row takes no part)."""
@@ -514,7 +548,7 @@ def histograms(data: BinnedData, gq, hq, node, n_nodes: int, return_totals: bool
     gq, hq = _pad(gq, data.ld, torch.int32), _pad(hq, data.ld, torch.int32)
     hist = torch.zeros((n_nodes, data.n_features, 256, 2), dtype=torch.int64, device=dev)
     tree = torch.zeros((4 * n_nodes, NODE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-    _hist_level(data, gq, hq, heap, node0, n_nodes, hist, tree, True)
+    _hist(_run, _stream(), data, gq, hq, heap, n_nodes, hist, tree, True)
     if not return_totals:
         return hist
     tab = tree.cpu().numpy().view(NODE_DTYPE).reshape(-1)[node0:node0 + n_nodes]
@@ -534,9 +568,7 @@ def best_splits(hist, totals, cuts: Sequence[np.ndarray], reg_lambda: float = 1.
     node0 = _level(n_nodes)
     cuts = check_cuts(cuts, F)
     dev = hist.device
-    cut_start = np.zeros(F + 1, np.int32)
-    cut_start[1:] = np.cumsum([len(c) for c in cuts])
-    flat = np.concatenate(list(cuts) + [np.zeros(1, np.float32)]).astype(np.float32)
+    cut_start, flat = _flat_cuts(cuts)
     tab = np.zeros(4 * n_nodes, NODE_DTYPE)
     tot = np.asarray(totals, np.int64).reshape(n_nodes, 2)
     tab['G'][node0:node0 + n_nodes] = tot[:, 0]
@@ -546,22 +578,16 @@ def best_splits(hist, totals, cuts: Sequence[np.ndarray], reg_lambda: float = 1.
     cs, cf = torch.from_numpy(cut_start).to(dev), torch.from_numpy(flat).to(dev)
     bg = torch.empty(n_nodes * F, dtype=torch.float64, device=dev)
     bc = torch.empty(n_nodes * F, dtype=torch.int32, device=dev)
-    if reg_alpha == 0.0 and shift == 0 and feature_mask is None:
-        _native.check(_native.lib().sa_boost_split(
-            hist.contiguous().data_ptr(), cs.data_ptr(), cf.data_ptr(), F, node0, n_nodes, 0, float(reg_lambda),
-            float(min_child_weight), float(gamma), float(learning_rate), bg.data_ptr(), bc.data_ptr(),
-            tree.data_ptr(), _stream()))
-    else:
-        fm = None
+    tu = fm = None
+    if not (reg_alpha == 0.0 and shift == 0 and feature_mask is None):
+        tu = Tuning(reg_alpha=float(reg_alpha), shift=int(shift))
         if feature_mask is not None:
             fm = np.ascontiguousarray(np.asarray(feature_mask).astype(bool).astype(np.uint8).ravel())
             if len(fm) != F:
                 raise ValueError('one mask byte per feature')
             fm = torch.from_numpy(fm).to(dev)
-        _native.check(_native.lib().sa_boost_split_ex(
-            hist.contiguous().data_ptr(), cs.data_ptr(), cf.data_ptr(), F, node0, n_nodes, 0, float(reg_lambda),
-            float(min_child_weight), float(gamma), float(learning_rate), float(reg_alpha), int(shift),
-            None if fm is None else fm.data_ptr(), bg.data_ptr(), bc.data_ptr(), tree.data_ptr(), _stream()))
+    params = (float(reg_lambda), float(min_child_weight), float(gamma), float(learning_rate))
+    _split(_run, _stream(), hist.contiguous(), cs, cf, F, n_nodes, params, bg, bc, tree, tu=tu, fmask=fm)
     return tree.cpu().numpy().view(NODE_DTYPE).reshape(-1)[node0:node0 + 3 * n_nodes]
 
 
@@ -578,7 +604,7 @@ def _apply(data: BinnedData, tree, max_depth: int, rows, n_rows: int, margin, p,
     """One ``sa_boost_apply`` launch: ``tree`` (device node table) over ``rows`` (device int64
     list or None) into the compact ``margin`` / ``p``."""
     nb = len(data.bit_feat)
-    run = launch or (lambda family, fn, *a: _native.check(fn(*a)))
+    run = launch or _run
     run('apply', _native.lib().sa_boost_apply, tree.data_ptr(), int(max_depth), data.dev['fmap'].data_ptr(),
         data.bits.data_ptr() if nb else None, data.bits.shape[1] * 8 if nb else 0,
         data.bins.data_ptr() if len(data.num_feat) else None, data.ld,
@@ -747,6 +773,23 @@ def check_weights(sample_weight, n: int, y=None, scale_pos_weight: float = 1.0, 
     return w, None
 
 
+def weights_to_device(w, dev):
+    """A host weight column as a float32 device column, rounded through float64 as :func:`check_weights` does."""
+    import torch
+    w = np.asarray(w).ravel()
+    with np.errstate(over='ignore'):  # a weight beyond float32's range becomes inf, which the range check refuses
+        w = w if w.dtype == np.float32 else w.astype(np.float64).astype(np.float32)
+    return torch.from_numpy(np.ascontiguousarray(w)).to(dev)
+
+
+def check_row_keys(row_keys, n: int) -> np.ndarray:
+    """Host row keys validated: one integer per row, as int64 (a uint64 key is its bit pattern)."""
+    keys = np.asarray(row_keys).ravel()
+    if len(keys) != int(n) or keys.dtype.kind not in 'iu':
+        raise ValueError('row_keys takes one integer per row')
+    return keys.astype(np.uint64).view(np.int64) if keys.dtype == np.uint64 else keys.astype(np.int64)
+
+
 IMPORTANCE_TYPES = ('gain', 'total_gain', 'weight', 'cover', 'total_cover')
 
 
@@ -816,6 +859,13 @@ def make_classifier(params: Dict[str, Any], **kw) -> 'DeviceGBTClassifier':
     return DeviceGBTClassifier(**{k: v for k, v in params.items() if k in DEFAULTS}, **kw)
 
 
+# The evaluation state of a fit (DeviceGBTClassifier._eval_setup fills it) and the state of one
+# fit_binned between its parts (._prepare fills it: `tu` / `columns` None: plain; `ev` None: no evaluation rows)
+_Eval = make_dataclass('_Eval', 'idx n n_pos minority m y margin p table P keys cursor'.split())
+_Fit = make_dataclass('_Fit', 'data y mask tu columns T D stream params margin gq hq node p P Mrec trees hist bg bc ev'
+                      .split())
+
+
 class DeviceGBTClassifier:
     """Binary logistic gradient boosting trained by ``csrc/sa_boost.hip`` (scikit-learn shaped).
 
@@ -845,8 +895,7 @@ class DeviceGBTClassifier:
     def __init__(self, record: bool = False, early_stopping_rounds: Optional[int] = None,
                  eval_metric: str = 'auc', importance_type: str = 'gain', **params) -> None:
         p = check_params(params, self.PARAMS)
-        if importance_type not in IMPORTANCE_TYPES:
-            raise ValueError(f'importance_type must be one of {IMPORTANCE_TYPES}, not {importance_type!r}')
+        importances(np.zeros(0, NODE_DTYPE), 1, importance_type)  # (its check of the name)
         self.importance_type = importance_type
         self.early_stopping_rounds, self.eval_metric = check_stop_params(early_stopping_rounds, eval_metric)
         for k, v in {**TUNING_DEFAULTS, **p}.items():
@@ -858,20 +907,19 @@ class DeviceGBTClassifier:
         return {k: getattr(self, k) for k in self.PARAMS}
 
     # ------------------------------------------------------------------ fitting
+    def _check_eval_rows(self, eval_rows) -> Optional[int]:
+        if self.early_stopping_rounds is not None and eval_rows is None:
+            raise ValueError('early_stopping_rounds needs evaluation rows (eval_rows / eval_set)')
+        return self.early_stopping_rounds
+
     def _launch(self, family, fn, *args) -> None:
         if self._events is None:
-            _native.check(fn(*args))
-            return
-        import torch
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _native.check(fn(*args))
-        e1.record()
-        self._events.append((family, e0, e1))
+            return _native.check(fn(*args))
+        self._timed(family, lambda: _native.check(fn(*args)))
 
     def _timed(self, family, work):
-        """``work()`` (device work that is not one of the library's entry points) under the
-        same per-family event timing as :meth:`_launch`."""
+        """``work()`` -- a launch of the library's, or other device work -- and, when ``_events``
+        is a list, its ``(family, start event, end event)`` entry."""
         if self._events is None:
             return work()
         import torch
@@ -882,7 +930,7 @@ class DeviceGBTClassifier:
         self._events.append((family, e0, e1))
         return out
 
-    def _eval_setup(self, data: BinnedData, y, eval_rows, T: int):
+    def _eval_setup(self, data: BinnedData, y, eval_rows, T: int) -> '_Eval':
         """The evaluation state of a fit: the row list, its compact labels and margins, the
         zeroed ``[T, 10]`` metric table, and -- the fit's ONE host read before the first round --
         the list's bounds and its positives (which class is the minority for the AUROC)."""
@@ -900,44 +948,42 @@ class DeviceGBTClassifier:
             raise ValueError('eval_rows must be inside the table')
         if n_pos == 0 or n_pos == k:
             raise ValueError('Only one class present in y. The AUROC is not defined in that case.')
-        minority = int(n_pos <= k - n_pos)
-        ev = {'idx': idx, 'n': k, 'n_pos': int(n_pos), 'minority': minority,
-              'm': int(n_pos) if minority else k - int(n_pos), 'y': y[idx].contiguous(),
-              'margin': torch.full((k,), float(base_margin(self.base_score)), dtype=torch.float32, device=dev),
-              'p': torch.empty(k, dtype=torch.float32, device=dev),
-              'table': torch.zeros((max(T, 1), 10), dtype=torch.int64, device=dev),
-              'P': torch.empty((T, k), dtype=torch.float32, device=dev) if self.record else None}
-        if self.eval_metric == 'auc':
-            ev['keys'] = torch.empty(ev['m'], dtype=torch.int32, device=dev)
-            ev['cursor'] = torch.zeros(max(T, 1), dtype=torch.int64, device=dev)
-        return ev
+        minority, auc = int(n_pos <= k - n_pos), self.eval_metric == 'auc'
+        m = int(n_pos) if minority else k - int(n_pos)
+        return _Eval(idx=idx, n=k, n_pos=int(n_pos), minority=minority, m=m, y=y[idx].contiguous(),
+                     margin=torch.full((k,), float(base_margin(self.base_score)), dtype=torch.float32, device=dev),
+                     p=torch.empty(k, dtype=torch.float32, device=dev),
+                     table=torch.zeros((max(T, 1), 10), dtype=torch.int64, device=dev),
+                     P=torch.empty((T, k), dtype=torch.float32, device=dev) if self.record else None,
+                     keys=torch.empty(m, dtype=torch.int32, device=dev) if auc else None,
+                     cursor=torch.zeros(max(T, 1), dtype=torch.int64, device=dev) if auc else None)
 
-    def _eval_round(self, data: BinnedData, ev, tree, t: int, st) -> None:
+    def _eval_round(self, data: BinnedData, ev: '_Eval', tree, t: int, st) -> None:
         """Round t's tree applied to the evaluation rows and the round's integer sums written to
         row t of the metric table: the counts and log-loss limbs always, ``U2`` for 'auc'."""
         import torch
         lib, run = _native.lib(), self._launch
-        k, y = ev['n'], ev['y']
-        p = ev['P'][t] if ev['P'] is not None else ev['p']
-        _apply(data, tree, int(self.max_depth), ev['idx'], k, ev['margin'], p, run)
-        row = ev['table'][t]
+        k, y = ev.n, ev.y
+        p = ev.P[t] if ev.P is not None else ev.p
+        _apply(data, tree, int(self.max_depth), ev.idx, k, ev.margin, p, run)
+        row = ev.table[t]
         run('metric', lib.sa_metric_sums, y.data_ptr(), p.data_ptr(), 1, k, row[0:2].data_ptr(), row[2:8].data_ptr(),
             row[8:9].data_ptr(), st)
         if self.eval_metric != 'auc':
             return
-        m, mino = ev['m'], ev['minority']
-        run('metric', lib.sa_auc_keys, y.data_ptr(), p.data_ptr(), 1, k, mino, ev['keys'].data_ptr(), m,
-            ev['cursor'][t:t + 1].data_ptr(), st)
-        keys = self._timed('sort', lambda: torch.sort(ev['keys']).values)  # top bit clear: signed order
+        m, mino = ev.m, ev.minority
+        run('metric', lib.sa_auc_keys, y.data_ptr(), p.data_ptr(), 1, k, mino, ev.keys.data_ptr(), m,
+            ev.cursor[t:t + 1].data_ptr(), st)
+        keys = self._timed('sort', lambda: torch.sort(ev.keys).values)  # top bit clear: signed order
         run('metric', lib.sa_auc_count, y.data_ptr(), p.data_ptr(), 1, k, keys.data_ptr(), m, mino,
             row[9:10].data_ptr(), st)
 
-    def _eval_series(self, ev, rounds: int) -> List[int]:
+    def _eval_series(self, ev: '_Eval', rounds: int) -> List[int]:
         """One host read of the metric table's first ``rounds`` rows: the integer series."""
         if rounds <= 0:
             return []
         from .ops import BinaryMetrics
-        h = ev['table'][:rounds].cpu().tolist()
+        h = ev.table[:rounds].cpu().tolist()
         err = 0
         for r in h:
             err |= r[8] & 0xFFFFFFFF
@@ -961,6 +1007,107 @@ class DeviceGBTClassifier:
         mx, mn, fin = torch.stack([we.max(), we.min(), torch.isfinite(we).all().to(torch.float32)]).cpu().tolist()
         return _check_weight_range(mx, mn, bool(fin))
 
+    def _prepare(self, data: BinnedData, y_dev, rows, eval_rows, sample_weight, row_keys) -> '_Fit':
+        """A fit's state before round 0, in this order: labels, row mask, weights and their shift
+        (a weighted fit's one host read), row keys, column samples, buffers, evaluation state (one
+        host read).  Every validation error is raised here, before the first training launch."""
+        import torch
+        dev, n, ld, F = data.device, data.n, data.ld, data.n_features
+        T, D = int(self.n_estimators), int(self.max_depth)
+        y = y_dev.view(torch.uint8) if y_dev.dtype == torch.bool else y_dev
+        if y.dtype != torch.uint8 or y.numel() < n or y.device != dev:
+            raise ValueError('y_dev must be a uint8 / bool device column of at least n rows')
+        y = y.contiguous()
+        mask = None
+        if rows is not None:
+            rows = torch.as_tensor(rows, device=dev)
+            mask = torch.zeros(ld, dtype=torch.uint8, device=dev)
+            if rows.dtype == torch.bool:
+                mask[:n] = rows[:n].to(torch.uint8)
+            else:
+                mask[rows.to(torch.int64)] = 1
+        alpha, spw, seed = float(self.reg_alpha), float(self.scale_pos_weight), int(self.random_state)
+        thr, colsample = row_threshold(self.subsample), float(self.colsample_bytree)
+        tu = columns = None
+        if not (sample_weight is None and spw == 1.0 and thr == THR_ALL and colsample == 1.0 and alpha == 0.0):
+            e, wd, keys = 0, None, None
+            if isinstance(sample_weight, torch.Tensor) and sample_weight.device == dev:
+                if sample_weight.numel() < n:
+                    raise ValueError(f'sample_weight has {sample_weight.numel()} entries for {n} rows')
+                wd = sample_weight.reshape(-1).to(torch.float32).contiguous()
+            elif sample_weight is not None:
+                host = sample_weight.numpy() if isinstance(sample_weight, torch.Tensor) else sample_weight
+                if rows is None:
+                    host, _ = check_weights(host, n)
+                elif len(np.asarray(host).ravel()) != n:
+                    raise ValueError(f'sample_weight has {len(np.asarray(host).ravel())} entries for {n} rows')
+                wd = weights_to_device(host, dev)
+            if wd is not None or spw != 1.0:
+                e = self._weight_shift(wd, y, mask, n)
+            if row_keys is not None and thr != THR_ALL:
+                keys = torch.as_tensor(row_keys).reshape(-1).to(dev).to(torch.int64).contiguous()
+                if keys.numel() < n:
+                    raise ValueError(f'row_keys has {keys.numel()} entries for {n} rows')
+            if colsample != 1.0:
+                columns = ColumnSamples(data, seed, T, colsample)
+            tu = Tuning(wd, spw, e, keys, seed, thr, alpha)
+        params = (float(self.reg_lambda), float(self.min_child_weight), float(self.gamma), float(self.learning_rate))
+        top = 2 ** (D - 1)  # nodes of the deepest level that splits
+        rec = lambda: torch.empty((T, ld), dtype=torch.float32, device=dev) if self.record else None  # noqa: E731
+        return _Fit(
+            data=data, y=y, mask=mask, tu=tu, columns=columns, T=T, D=D, stream=_stream(), params=params,
+            margin=torch.full((ld,), float(base_margin(self.base_score)), dtype=torch.float32, device=dev),
+            gq=torch.zeros(ld, dtype=torch.int32, device=dev), hq=torch.zeros(ld, dtype=torch.int32, device=dev),
+            node=torch.full((ld,), NO_NODE, dtype=torch.uint8, device=dev),
+            p=torch.empty(ld, dtype=torch.float32, device=dev), P=rec(), Mrec=rec(),
+            trees=torch.zeros((max(T, 1), 2 ** (D + 1) - 1, NODE_DTYPE.itemsize), dtype=torch.uint8, device=dev),
+            hist=torch.empty((top, F, 256, 2), dtype=torch.int64, device=dev),
+            bg=torch.empty(top * F, dtype=torch.float64, device=dev),
+            bc=torch.empty(top * F, dtype=torch.int32, device=dev),
+            ev=None if eval_rows is None else self._eval_setup(data, y, eval_rows, T))  # before any training launch
+
+    def _finish(self, f: '_Fit', R: int) -> 'DeviceGBTClassifier':
+        """After ``R`` rounds: the evaluation series and the best round, ``margin_`` / ``p_`` of
+        the kept trees, the kept trees' one read-back, and the fitted attributes."""
+        data, ev, esr, n = f.data, f.ev, self.early_stopping_rounds, f.data.n
+        keep = R
+        for k in ('evals_result_', 'eval_sums_', 'best_iteration', 'best_score'):
+            self.__dict__.pop(k, None)
+        if ev is not None:
+            series = self._eval_series(ev, R)
+            best, stop = stop_decision(series, esr, self.eval_metric == 'auc')
+            assert stop == R, (stop, R)  # every round launched was needed
+            self.eval_sums_ = series
+            scores = [metric_score(v, self.eval_metric, ev.n, ev.n_pos) for v in series]
+            self.evals_result_ = {'validation_0': {self.eval_metric: scores}}
+            if series:
+                self.best_iteration, self.best_score = best, scores[best]
+                if esr is not None:
+                    keep = best + 1
+        self.n_rounds_run_ = R
+        if esr is not None and keep:
+            # margin_ / p_ belong to the kept trees: replay them over every row from the base
+            # margin (the predictor's walk and its float32 additions, in tree order)
+            f.margin.fill_(float(base_margin(self.base_score)))
+            for t in range(keep):
+                _apply(data, f.trees[t], f.D, None, n, f.margin, f.p if t == keep - 1 else None, self._launch)
+        else:
+            _grad(self._launch, f.stream, f.margin, None, None, n, None, None, f.p, None)
+        M = f.trees.shape[1]
+        self.trees_ = f.trees[:keep].cpu().numpy().view(NODE_DTYPE).reshape(keep, M).copy()  # the one read-back
+        self.cuts_ = data.cuts
+        self.quant_shift_ = 0 if f.tu is None else f.tu.shift
+        self.column_samples_ = None if f.columns is None else f.columns.features[:keep]
+        self.feature_names_in_ = np.array(data.names, dtype=object)
+        self.n_features_in_ = data.n_features
+        self.classes_ = np.array([0, 1])
+        self.margin_, self.p_ = f.margin[:n], f.p[:n]
+        self.record_ = {'p': f.P[:R, :n], 'margin': f.Mrec[:R, :n]} if f.P is not None else None
+        if f.P is not None and ev is not None:
+            self.record_['eval_p'] = ev.P[:R]
+        self._ensemble = None
+        return self
+
     def fit_binned(self, data: BinnedData, y_dev, rows=None, eval_rows=None, sample_weight=None,
                    row_keys=None) -> 'DeviceGBTClassifier':
         """Fit on binned data and a device label column (uint8 / bool, at least n rows).  The
@@ -981,161 +1128,40 @@ class DeviceGBTClassifier:
         row index, which gives run-to-run identity only: permuting the rows then changes the
         sample.  With every one of these at its neutral value the launches are the unweighted
         fit's and nothing is read from the device before the first round."""
-        import torch
-        esr = self.early_stopping_rounds
-        if esr is not None and eval_rows is None:
-            raise ValueError('early_stopping_rounds needs evaluation rows (eval_rows / eval_set)')
-        lib, d, dev = _native.lib(), data.dev, data.device
+        esr = self._check_eval_rows(eval_rows)
+        f = self._prepare(data, y_dev, rows, eval_rows, sample_weight, row_keys)
+        lib, run, st, d, nb = _native.lib(), self._launch, f.stream, data.dev, len(data.bit_feat)
         n, ld, F = data.n, data.ld, data.n_features
-        T, D = int(self.n_estimators), int(self.max_depth)
-        M = 2 ** (D + 1) - 1
-        y = y_dev.view(torch.uint8) if y_dev.dtype == torch.bool else y_dev
-        if y.dtype != torch.uint8 or y.numel() < n or y.device != dev:
-            raise ValueError('y_dev must be a uint8 / bool device column of at least n rows')
-        y = y.contiguous()
-        mask = None
-        if rows is not None:
-            rows = torch.as_tensor(rows, device=dev)
-            mask = torch.zeros(ld, dtype=torch.uint8, device=dev)
-            if rows.dtype == torch.bool:
-                mask[:n] = rows[:n].to(torch.uint8)
-            else:
-                mask[rows.to(torch.int64)] = 1
-        alpha, spw, seed = float(self.reg_alpha), float(self.scale_pos_weight), int(self.random_state)
-        thr, colsample = row_threshold(self.subsample), float(self.colsample_bytree)
-        plain = sample_weight is None and spw == 1.0 and thr == THR_ALL and colsample == 1.0 and alpha == 0.0
-        e, wd, keys, rounds, fmask = 0, None, None, None, None
-        if not plain:
-            if sample_weight is not None:
-                if isinstance(sample_weight, torch.Tensor) and sample_weight.device == dev:
-                    if sample_weight.numel() < n:
-                        raise ValueError(f'sample_weight has {sample_weight.numel()} entries for {n} rows')
-                    wd = sample_weight.reshape(-1).to(torch.float32).contiguous()
-                else:
-                    host = sample_weight.numpy() if isinstance(sample_weight, torch.Tensor) else sample_weight
-                    if rows is None:
-                        host, _ = check_weights(host, n)
-                    elif len(np.asarray(host).ravel()) != n:
-                        raise ValueError(f'sample_weight has {len(np.asarray(host).ravel())} entries for {n} rows')
-                    with np.errstate(over='ignore'):
-                        host = np.ascontiguousarray(np.asarray(host, np.float64).ravel().astype(np.float32))
-                    wd = torch.from_numpy(host).to(dev)
-            if wd is not None or spw != 1.0:
-                e = self._weight_shift(wd, y, mask, n)
-            if row_keys is not None and thr != THR_ALL:
-                keys = torch.as_tensor(row_keys).reshape(-1).to(dev).to(torch.int64).contiguous()
-                if keys.numel() < n:
-                    raise ValueError(f'row_keys has {keys.numel()} entries for {n} rows')
-            if colsample != 1.0:
-                rounds, fmask, _lists = _column_lists(data, seed, T, colsample)
-        wptr = None if wd is None else wd.data_ptr()
-        kptr = None if keys is None else keys.data_ptr()
-        margin = torch.full((ld,), float(base_margin(self.base_score)), dtype=torch.float32, device=dev)
-        gq = torch.zeros(ld, dtype=torch.int32, device=dev)
-        hq = torch.zeros(ld, dtype=torch.int32, device=dev)
-        node = torch.full((ld,), NO_NODE, dtype=torch.uint8, device=dev)
-        p = torch.empty(ld, dtype=torch.float32, device=dev)
-        P = torch.empty((T, ld), dtype=torch.float32, device=dev) if self.record else None
-        Mrec = torch.empty((T, ld), dtype=torch.float32, device=dev) if self.record else None
-        trees = torch.zeros((max(T, 1), M, NODE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-        top = 2 ** (D - 1)  # nodes of the deepest level that splits
-        hist = torch.empty((top, F, 256, 2), dtype=torch.int64, device=dev)
-        bg = torch.empty(top * F, dtype=torch.float64, device=dev)
-        bc = torch.empty(top * F, dtype=torch.int32, device=dev)
-        st = _stream()
-        nb = len(data.bit_feat)
-        bits_ptr = data.bits.data_ptr() if nb else None
-        bstride = data.bits.shape[1] * 8 if nb else 0
-        mptr = None if mask is None else mask.data_ptr()
-        run = self._launch
-        ev = None if eval_rows is None else self._eval_setup(data, y, eval_rows, T)  # before any training launch
-        maximize = self.eval_metric == 'auc'
-        look, R, self.n_polls_ = esr, T, 0
-        for t in range(T):
-            tree = trees[t]
-            pt = P[t] if P is not None else p
-            if plain:
-                run('grad', lib.sa_boost_grad, margin.data_ptr(), y.data_ptr(), mptr, n, gq.data_ptr(),
-                    hq.data_ptr(), pt.data_ptr(), node.data_ptr(), st)
-            else:
-                run('grad', lib.sa_boost_grad_ex, margin.data_ptr(), y.data_ptr(), mptr, n, wptr, spw, e, kptr, seed,
-                    t, thr, gq.data_ptr(), hq.data_ptr(), pt.data_ptr(), node.data_ptr(), st)
-            cols = None if rounds is None else rounds[t]
-            fptr = None if fmask is None else fmask[t].data_ptr()
-            for level in range(D):
+        look, R, self.n_polls_ = esr, f.T, 0
+        for t in range(f.T):
+            tree = f.trees[t]
+            cols, fmask = (None, None) if f.columns is None else (f.columns.rounds[t], f.columns.mask[t])
+            _grad(run, st, f.margin, f.y, f.mask, n, f.gq, f.hq, f.P[t] if f.P is not None else f.p, f.node,
+                  tu=f.tu, t=t)
+            for level in range(f.D):
                 nn = 2 ** level
-                node0 = nn - 1
-                h = hist[:nn]
+                h = f.hist[:nn]
                 h.zero_()
-                _hist_level(data, gq, hq, node, node0, nn, h, tree, level == 0, run, cols)
-                if plain:
-                    run('split', lib.sa_boost_split, h.data_ptr(), d['cut_start'].data_ptr(), d['cuts'].data_ptr(),
-                        F, node0, nn, 0, float(self.reg_lambda), float(self.min_child_weight), float(self.gamma),
-                        float(self.learning_rate), bg.data_ptr(), bc.data_ptr(), tree.data_ptr(), st)
-                else:
-                    run('split', lib.sa_boost_split_ex, h.data_ptr(), d['cut_start'].data_ptr(),
-                        d['cuts'].data_ptr(), F, node0, nn, 0, float(self.reg_lambda), float(self.min_child_weight),
-                        float(self.gamma), float(self.learning_rate), alpha, e, fptr, bg.data_ptr(), bc.data_ptr(),
-                        tree.data_ptr(), st)
-                run('advance', lib.sa_boost_advance, tree.data_ptr(), node0, nn, d['fmap'].data_ptr(), bits_ptr,
-                    bstride, data.bins.data_ptr(), ld, n, node.data_ptr(), None, st)
-            if plain:
-                run('split', lib.sa_boost_split, None, None, None, F, 2 ** D - 1, 2 ** D, 1, float(self.reg_lambda),
-                    float(self.min_child_weight), float(self.gamma), float(self.learning_rate), None, None,
-                    tree.data_ptr(), st)
-            else:
-                run('split', lib.sa_boost_split_ex, None, None, None, F, 2 ** D - 1, 2 ** D, 1,
-                    float(self.reg_lambda), float(self.min_child_weight), float(self.gamma),
-                    float(self.learning_rate), alpha, e, None, None, None, tree.data_ptr(), st)
+                _hist(run, st, data, f.gq, f.hq, f.node, nn, h, tree, level == 0, cols=cols)
+                _split(run, st, h, d['cut_start'], d['cuts'], F, nn, f.params, f.bg, f.bc, tree, tu=f.tu, fmask=fmask)
+                run('advance', lib.sa_boost_advance, tree.data_ptr(), nn - 1, nn, d['fmap'].data_ptr(),
+                    data.bits.data_ptr() if nb else None, data.bits.shape[1] * 8 if nb else 0, data.bins.data_ptr(),
+                    ld, n, f.node.data_ptr(), None, st)
+            _split(run, st, None, None, None, F, 2 ** f.D, f.params, None, None, tree, tu=f.tu, leaf_only=True)
             run('advance', lib.sa_boost_advance, tree.data_ptr(), 0, 1, None, None, 0, None, ld, n,
-                node.data_ptr(), margin.data_ptr(), st)
-            if Mrec is not None:
-                Mrec[t].copy_(margin)
-            if ev is None:
+                f.node.data_ptr(), f.margin.data_ptr(), st)  # the margin
+            if f.Mrec is not None:
+                f.Mrec[t].copy_(f.margin)
+            if f.ev is None:
                 continue
-            self._eval_round(data, ev, tree, t, st)
-            if esr is not None and t == look and t + 1 < T:  # the rule could first fire here
+            self._eval_round(data, f.ev, tree, t, st)
+            if esr is not None and t == look and t + 1 < f.T:  # the rule could first fire here
                 self.n_polls_ += 1
-                fired, look = stop_look(self._eval_series(ev, t + 1), esr, maximize)
+                fired, look = stop_look(self._eval_series(f.ev, t + 1), esr, self.eval_metric == 'auc')
                 if fired:
                     R = t + 1
                     break
-        keep = R
-        for k in ('evals_result_', 'eval_sums_', 'best_iteration', 'best_score'):
-            self.__dict__.pop(k, None)
-        if ev is not None:
-            series = self._eval_series(ev, R)
-            best, stop = stop_decision(series, esr, maximize)
-            assert stop == R, (stop, R)  # every round launched was needed
-            self.eval_sums_ = series
-            scores = [metric_score(v, self.eval_metric, ev['n'], ev['n_pos']) for v in series]
-            self.evals_result_ = {'validation_0': {self.eval_metric: scores}}
-            if series:
-                self.best_iteration, self.best_score = best, scores[best]
-                if esr is not None:
-                    keep = best + 1
-        self.n_rounds_run_ = R
-        if esr is not None and keep:
-            # margin_ / p_ belong to the kept trees: replay them over every row from the base
-            # margin (the predictor's walk and its float32 additions, in tree order)
-            margin.fill_(float(base_margin(self.base_score)))
-            for t in range(keep):
-                _apply(data, trees[t], D, None, n, margin, p if t == keep - 1 else None, run)
-        else:
-            run('grad', lib.sa_boost_grad, margin.data_ptr(), None, None, n, None, None, p.data_ptr(), None, st)
-        self.trees_ = trees[:keep].cpu().numpy().view(NODE_DTYPE).reshape(keep, M).copy()  # the one read-back
-        self.cuts_ = data.cuts
-        self.quant_shift_ = e
-        self.column_samples_ = None if rounds is None else [r['features'] for r in rounds[:keep]]
-        self.feature_names_in_ = np.array(data.names, dtype=object)
-        self.n_features_in_ = F
-        self.classes_ = np.array([0, 1])
-        self.margin_, self.p_ = margin[:n], p[:n]
-        self.record_ = {'p': P[:R, :n], 'margin': Mrec[:R, :n]} if P is not None else None
-        if P is not None and ev is not None:
-            self.record_['eval_p'] = ev['P'][:R]
-        self._ensemble = None
-        return self
+        return self._finish(f, R)
 
     def fit_blocks(self, blocks, y_dev, rows=None, cuts=None, eval_rows=None, sample_weight=None,
                    row_keys=None) -> 'DeviceGBTClassifier':
@@ -1144,13 +1170,8 @@ class DeviceGBTClassifier:
         explicit cut lists, default :func:`make_cuts` on the training rows; ``eval_rows``: the
         evaluation rows (indices or a bool mask), default none; ``sample_weight`` / ``row_keys``: as
         in :meth:`fit_binned`."""
-        if self.early_stopping_rounds is not None and eval_rows is None:
-            raise ValueError('early_stopping_rounds needs evaluation rows (eval_rows / eval_set)')
-        if rows is not None:
-            import torch
-            rows = torch.as_tensor(rows, device=blocks.device)
-            if rows.dtype == torch.bool:
-                rows = torch.nonzero(rows[:blocks.n]).reshape(-1)
+        self._check_eval_rows(eval_rows)
+        rows = None if rows is None else _row_list(rows, blocks.n, blocks.device)
         return self.fit_binned(bin_blocks(blocks, cuts, rows), y_dev, rows, eval_rows, sample_weight, row_keys)
 
     def fit(self, X, y, cuts=None, eval_set=None, sample_weight=None, row_keys=None) -> 'DeviceGBTClassifier':
@@ -1159,18 +1180,13 @@ class DeviceGBTClassifier:
         are uploaded as one table whose first ``len(X)`` rows train and whose other rows are the
         evaluation rows (the cuts come from the training rows only).  ``sample_weight`` /
         ``row_keys``: one entry per row of ``X`` (host), validated before anything is uploaded."""
-        if self.early_stopping_rounds is not None and eval_set is None:
-            raise ValueError('early_stopping_rounds needs evaluation rows (eval_rows / eval_set)')
+        self._check_eval_rows(eval_set)
         yh = np.asarray(y).astype(bool).astype(np.uint8).ravel()
         n_train = len(yh)
         if sample_weight is not None:
             sample_weight, _ = check_weights(sample_weight, n_train, yh, self.scale_pos_weight)
         if row_keys is not None:
-            row_keys = np.asarray(row_keys).ravel()
-            if len(row_keys) != n_train or row_keys.dtype.kind not in 'iu':
-                raise ValueError('row_keys takes one integer per row')
-            row_keys = row_keys.astype(np.uint64).view(np.int64) if row_keys.dtype == np.uint64 else \
-                row_keys.astype(np.int64)
+            row_keys = check_row_keys(row_keys, n_train)
         rows = eval_rows = None
         if eval_set is not None:
             if len(eval_set) != 1 or len(eval_set[0]) != 2:
@@ -1201,7 +1217,7 @@ class DeviceGBTClassifier:
         yd = torch.zeros(data.ld, dtype=torch.uint8, device=data.device)
         yd[:data.n] = torch.from_numpy(yh).to(data.device)
         if sample_weight is not None:
-            sample_weight = torch.from_numpy(np.ascontiguousarray(sample_weight, np.float32)).to(data.device)
+            sample_weight = weights_to_device(sample_weight, data.device)
         self.fit_binned(data, yd, rows, eval_rows, sample_weight, row_keys)
         if eval_set is not None:  # the fitted columns are the training frame's
             self.margin_, self.p_ = self.margin_[:n_train], self.p_[:n_train]
@@ -1268,12 +1284,7 @@ class DeviceGBTClassifier:
             per[k].append(c)
         dts = {'b': np.uint8, 'f': np.float64, 'i': np.int64}
         dev = torch.device('cuda', torch.cuda.current_device())
-        blk = {}
-        for k in 'bfi':
-            h = np.zeros((1, len(per[k]), ld), dts[k])
-            for r, c in enumerate(per[k]):
-                h[0, r, :n] = c
-            blk[k] = torch.from_numpy(h).to(dev)
+        blk = {k: torch.from_numpy(_padded_block(per[k], n, ld, dts[k])).to(dev) for k in 'bfi'}
         plan = SimpleNamespace(order=order, names=[o[0] for o in order], n_bool=len(per['b']),
                                n_f64=len(per['f']), n_i64=len(per['i']))
         te = getattr(self, '_ensemble', None)

@@ -100,29 +100,6 @@ __global__ __launch_bounds__(BB_THREADS) void boost_bin_kernel(sa_block Bf, sa_b
 }
 
 // ---------------------------------------------------------------------------------------- gradients
-__global__ __launch_bounds__(256) void boost_grad_kernel(const float* __restrict__ margin, const uint8_t* __restrict__ y,
-                                                          const uint8_t* __restrict__ mask, int64_t n,
-                                                          int32_t* __restrict__ gq, int32_t* __restrict__ hq,
-                                                          float* __restrict__ p_out, uint8_t* __restrict__ node) {
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  const float m = margin[j];
-  const float p = 1.0f / (1.0f + expf(-m));
-  if (p_out) p_out[j] = p;
-  if (gq) {
-    const float yy = y[j] ? 1.0f : 0.0f;
-    const float g = p - yy;
-    const float h = p * (1.0f - p);
-    gq[j] = (int32_t)rintf(g * 1073741824.0f);
-    hq[j] = (int32_t)rintf(h * 1073741824.0f);
-  }
-  if (node) node[j] = (!mask || mask[j]) ? 0 : NO_NODE;
-}
-
-// Contract items 13, 14 and 16: the effective weight we = w * (y ? s : 1) folded in before the
-// quantisation at scale 2^(30 - e) (|g| <= we <= 2^e keeps |gq| <= 2^30), and the round's row sample
-// from a counter hash of (seed, round, row key): a row outside it gets gq = hq = 0 -- the histogram
-// kernels skip zero adds -- and still walks the tree.  Each product is its own statement.
 __device__ __host__ __forceinline__ u64 fmix64(u64 z) {  // splitmix64's finaliser
   z ^= z >> 30;
   z *= 0xBF58476D1CE4E5B9ull;
@@ -132,10 +109,23 @@ __device__ __host__ __forceinline__ u64 fmix64(u64 z) {  // splitmix64's finalis
   return z;
 }
 
-__global__ __launch_bounds__(256) void boost_grad_ex_kernel(
-    const float* __restrict__ margin, const uint8_t* __restrict__ y, const uint8_t* __restrict__ mask, int64_t n,
-    const float* __restrict__ weight, float spw, float scale, const int64_t* __restrict__ keys, u64 round_base, u64 thr,
-    int32_t* __restrict__ gq, int32_t* __restrict__ hq, float* __restrict__ p_out, uint8_t* __restrict__ node) {
+struct grad_tuning {  // what sa_boost_grad_ex adds to sa_boost_grad: the TUNED kernel alone reads it
+  const float* weight;
+  float spw, scale;
+  const int64_t* keys;
+  u64 round_base, thr;
+};
+
+// TUNED (contract items 13, 14 and 16): the effective weight we = w * (y ? s : 1) folded in before
+// the quantisation at scale 2^(30 - e) (|g| <= we <= 2^e keeps |gq| <= 2^30), and the round's row
+// sample from a counter hash of (seed, round, row key): a row outside it gets gq = hq = 0 -- the
+// histogram kernels skip zero adds -- and still walks the tree.  Each product is its own statement.
+template <bool TUNED>
+__global__ __launch_bounds__(256) void boost_grad_kernel(const float* __restrict__ margin, const uint8_t* __restrict__ y,
+                                                          const uint8_t* __restrict__ mask, int64_t n,
+                                                          int32_t* __restrict__ gq, int32_t* __restrict__ hq,
+                                                          float* __restrict__ p_out, uint8_t* __restrict__ node,
+                                                          grad_tuning tu) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const float m = margin[j];
@@ -143,17 +133,24 @@ __global__ __launch_bounds__(256) void boost_grad_ex_kernel(
   if (p_out) p_out[j] = p;
   if (gq) {
     const bool pos = y[j] != 0;
-    const u64 key = keys ? (u64)keys[j] : (u64)j;
-    const bool in = thr > 0xFFFFFFFFull || (fmix64(round_base + key) >> 32) < thr;
+    bool in = true;
+    if (TUNED) {
+      const u64 key = tu.keys ? (u64)tu.keys[j] : (u64)j;
+      in = tu.thr > 0xFFFFFFFFull || (fmix64(tu.round_base + key) >> 32) < tu.thr;
+    }
     int32_t gi = 0, hi = 0;
     if (in) {
-      const float w = weight ? weight[j] : 1.0f;
-      const float we = w * (pos ? spw : 1.0f);
       const float yy = pos ? 1.0f : 0.0f;
-      const float d = p - yy;
-      const float g = d * we;
-      const float q = p * (1.0f - p);
-      const float h = q * we;
+      float g = p - yy;
+      float h = p * (1.0f - p);
+      float scale = 1073741824.0f;
+      if (TUNED) {
+        const float w = tu.weight ? tu.weight[j] : 1.0f;
+        const float we = w * (pos ? tu.spw : 1.0f);
+        g = g * we;
+        h = h * we;
+        scale = tu.scale;
+      }
       const float gs = g * scale;
       const float hs = h * scale;
       gi = (int32_t)rintf(gs);
@@ -581,6 +578,23 @@ bool level_ok(int node0, int n_nodes) {
   return n_nodes >= 1 && n_nodes <= SA_BOOST_MAX_LEVEL_NODES && (n_nodes & (n_nodes - 1)) == 0 &&
          node0 == n_nodes - 1;
 }
+
+// a bitmap argument: 8-byte aligned words and a byte stride that holds n rows
+bool bits_ok(const uint64_t* bits, int64_t bits_stride, int64_t n) {
+  return bits_stride % 8 == 0 && bits_stride >= 8 * ((n + 63) / 64) && ((uintptr_t)bits & 7u) == 0;
+}
+
+// `name`: the entry point, for the error text; `tuning_ok`: its check of what it put into `tu`
+template <bool TUNED>
+int grad(const char* name, const float* margin, const uint8_t* y, const uint8_t* row_mask, int64_t n, bool tuning_ok,
+         grad_tuning tu, int32_t* gq, int32_t* hq, float* p, uint8_t* node, void* stream) {
+  if (n < 0 || !margin || (gq && (!hq || !y)) || (!gq && hq)) return fail(SA_EINVAL, "%s: bad arguments", name);
+  if (!tuning_ok) return fail(SA_EINVAL, "%s: bad parameters", name);
+  if (n == 0) return SA_OK;
+  hipLaunchKernelGGL((boost_grad_kernel<TUNED>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     margin, y, row_mask, n, gq, hq, p, node, tu);
+  return check_launch(TUNED ? "boost_grad_ex_kernel" : "boost_grad_kernel");
+}
 }  // namespace
 
 extern "C" int sa_boost_bin(const sa_block* f64_blk, const sa_block* i64_blk, int32_t f32, const int32_t* slots,
@@ -605,29 +619,18 @@ extern "C" int sa_boost_bin(const sa_block* f64_blk, const sa_block* i64_blk, in
 
 extern "C" int sa_boost_grad(const float* margin, const uint8_t* y, const uint8_t* row_mask, int64_t n, int32_t* gq,
                              int32_t* hq, float* p, uint8_t* node, void* stream) {
-  if (n < 0 || !margin || (gq && (!hq || !y)) || (!gq && hq))
-    return fail(SA_EINVAL, "sa_boost_grad: bad arguments");
-  if (n == 0) return SA_OK;
-  hipLaunchKernelGGL(boost_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, margin,
-                     y, row_mask, n, gq, hq, p, node);
-  return check_launch("boost_grad_kernel");
+  return grad<false>("sa_boost_grad", margin, y, row_mask, n, true, grad_tuning{}, gq, hq, p, node, stream);
 }
 
 extern "C" int sa_boost_grad_ex(const float* margin, const uint8_t* y, const uint8_t* row_mask, int64_t n,
                                 const float* weight, float scale_pos_weight, int32_t shift, const int64_t* row_keys,
                                 uint64_t seed, int64_t round, uint64_t thr, int32_t* gq, int32_t* hq, float* p,
                                 uint8_t* node, void* stream) {
-  if (n < 0 || !margin || (gq && (!hq || !y)) || (!gq && hq))
-    return fail(SA_EINVAL, "sa_boost_grad_ex: bad arguments");
-  if (shift < 0 || shift > SA_BOOST_MAX_SHIFT || !(scale_pos_weight > 0.0f) || std::isinf(scale_pos_weight) ||
-      round < 0 || thr > (1ull << 32))
-    return fail(SA_EINVAL, "sa_boost_grad_ex: bad parameters");
-  if (n == 0) return SA_OK;
+  const bool ok = shift >= 0 && shift <= SA_BOOST_MAX_SHIFT && scale_pos_weight > 0.0f &&
+                  !std::isinf(scale_pos_weight) && round >= 0 && thr <= (1ull << 32);
   const u64 round_base = fmix64(fmix64((u64)seed ^ SA_BOOST_SALT_ROWS) + (u64)round);
-  hipLaunchKernelGGL(boost_grad_ex_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, margin,
-                     y, row_mask, n, weight, scale_pos_weight, std::ldexp(1.0f, 30 - shift), row_keys, round_base,
-                     (u64)thr, gq, hq, p, node);
-  return check_launch("boost_grad_ex_kernel");
+  const grad_tuning tu{weight, scale_pos_weight, std::ldexp(1.0f, ok ? 30 - shift : 0), row_keys, round_base, (u64)thr};
+  return grad<true>("sa_boost_grad_ex", margin, y, row_mask, n, ok, tu, gq, hq, p, node, stream);
 }
 
 extern "C" int sa_boost_row_keys(const int64_t* game_id, const int64_t* action_id, int64_t n, int64_t* keys,
@@ -646,8 +649,7 @@ extern "C" int sa_boost_hist_bits(const uint64_t* bits, int64_t bits_stride, con
   if (n < 0 || n_bool < 0 || n_features < 1 || !level_ok(node0, n_nodes))
     return fail(SA_EINVAL, "sa_boost_hist_bits: bad sizes");
   if (!gq || !hq || !node || !hist || !tree) return fail(SA_EINVAL, "sa_boost_hist_bits: null pointer");
-  if (n_bool > 0 && (!bits || !bit_rows || !bit_feat || bits_stride % 8 || bits_stride < 8 * ((n + 63) / 64) ||
-                     ((uintptr_t)bits & 7u)))
+  if (n_bool > 0 && (!bits || !bit_rows || !bit_feat || !bits_ok(bits, bits_stride, n)))
     return fail(SA_EINVAL, "sa_boost_hist_bits: bad bitmaps");
   if (n == 0) return SA_OK;
   int cc = HB_ACC_BYTES / (n_nodes * 16);
@@ -718,9 +720,8 @@ extern "C" int sa_boost_split_ex(const int64_t* hist, const int32_t* cut_start, 
                                  sa_boost_node* tree, void* stream) {
   if (!(reg_alpha >= 0.0) || std::isinf(reg_alpha) || shift < 0 || shift > SA_BOOST_MAX_SHIFT)
     return fail(SA_EINVAL, "sa_boost_split: bad parameters");
-  if (n_features < 1 || n_nodes < 1 || n_nodes > 2 * SA_BOOST_MAX_LEVEL_NODES || (n_nodes & (n_nodes - 1)) ||
-      node0 != n_nodes - 1)
-    return fail(SA_EINVAL, "sa_boost_split: bad sizes");
+  const bool leaf_level = n_nodes == 2 * SA_BOOST_MAX_LEVEL_NODES && node0 == n_nodes - 1;  // below the deepest level
+  if (n_features < 1 || !(level_ok(node0, n_nodes) || leaf_level)) return fail(SA_EINVAL, "sa_boost_split: bad sizes");
   if (!tree || (!leaf_only && (!hist || !cut_start || !cuts || !best_gain || !best_cut)))
     return fail(SA_EINVAL, "sa_boost_split: null pointer");
   if (!leaf_only && n_nodes > SA_BOOST_MAX_LEVEL_NODES) return fail(SA_EINVAL, "sa_boost_split: level too deep");
@@ -753,8 +754,7 @@ extern "C" int sa_boost_advance(const sa_boost_node* tree, int32_t node0, int32_
   if (n < 0 || !tree || !node) return fail(SA_EINVAL, "sa_boost_advance: bad arguments");
   if (!margin) {
     if (!level_ok(node0, n_nodes) || !fmap) return fail(SA_EINVAL, "sa_boost_advance: bad level");
-    if (bits && (bits_stride % 8 || bits_stride < 8 * ((n + 63) / 64) || ((uintptr_t)bits & 7u)))
-      return fail(SA_EINVAL, "sa_boost_advance: bad bitmaps");
+    if (bits && !bits_ok(bits, bits_stride, n)) return fail(SA_EINVAL, "sa_boost_advance: bad bitmaps");
     if (bins && ld < n) return fail(SA_EINVAL, "sa_boost_advance: bad bins");
   }
   if (n == 0) return SA_OK;
@@ -774,8 +774,7 @@ extern "C" int sa_boost_apply(const sa_boost_node* tree, int32_t max_depth, cons
   if (n < 0 || n_rows < 0 || max_depth < 1 || max_depth > SA_BOOST_MAX_DEPTH || ld < n)
     return fail(SA_EINVAL, "sa_boost_apply: bad sizes");
   if (!tree || !fmap || !margin) return fail(SA_EINVAL, "sa_boost_apply: null pointer");
-  if (bits && (bits_stride % 8 || bits_stride < 8 * ((n + 63) / 64) || ((uintptr_t)bits & 7u)))
-    return fail(SA_EINVAL, "sa_boost_apply: bad bitmaps");
+  if (bits && !bits_ok(bits, bits_stride, n)) return fail(SA_EINVAL, "sa_boost_apply: bad bitmaps");
   if (n_rows > (int64_t)0x7FFFFFFF * AP_THREADS) return fail(SA_EINVAL, "sa_boost_apply: too many rows");
   if (n_rows == 0) return SA_OK;
   hipLaunchKernelGGL(boost_apply_kernel, dim3((unsigned)((n_rows + AP_THREADS - 1) / AP_THREADS)), dim3(AP_THREADS), 0,

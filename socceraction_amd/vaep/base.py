@@ -264,30 +264,35 @@ class VAEP:
                 weight, _ = boost.check_weights(weight, len(X), y[col].to_numpy(), params['scale_pos_weight'],
                                                 train_idx)
         if keys is not None:
-            keys = np.asarray(keys).ravel()
-            if len(keys) != len(X) or keys.dtype.kind not in 'iu':
-                raise ValueError('row_keys takes one integer per row')
-            keys = keys.astype(np.uint64).view(np.int64) if keys.dtype == np.uint64 else keys.astype(np.int64)
+            keys = boost.check_row_keys(keys, len(X))
         data = boost.bin_host(X, rows=train_idx)
         rows = torch.from_numpy(train_idx).to(data.device)
         if weight is not None:
-            weight = torch.from_numpy(np.ascontiguousarray(weight)).to(data.device)
+            weight = boost.weights_to_device(weight, data.device)
         if keys is not None:
             keys = torch.from_numpy(np.ascontiguousarray(keys)).to(data.device)
         eval_rows = None
         if stop['early_stopping_rounds'] is not None:
             eval_rows = torch.from_numpy(np.sort(np.asarray(val_idx, np.int64))).to(data.device)
-        self.device_eval_: Dict[str, Dict[str, float]] = {}
+        labels = {}
         for col in list(y.columns):
             yh = np.zeros(data.ld, np.uint8)
             yh[:data.n] = y[col].to_numpy().astype(bool)
-            clf = boost.make_classifier(params, **stop).fit_binned(
-                data, torch.from_numpy(yh).to(data.device), rows, eval_rows, weight, keys)
-            self.__models[col] = clf
+            labels[col] = torch.from_numpy(yh).to(data.device)
+        for col, _, clf in self._fit_labels(labels, params, stop, data, rows, eval_rows, weight, keys):
             if val_size > 0 and len(val_idx):
                 p = clf.predict_proba(X.iloc[val_idx])[:, 1]
                 self.device_eval_[col] = metrics.binary_scores(y[col].to_numpy().astype(bool)[val_idx], p)
         return self
+
+    def _fit_labels(self, labels, params, stop, data, *fit_args):
+        """The per-label tail of both device fits: one classifier per ``labels`` column (name -> device
+        labels), kept as its model and yielded with both for the caller's held-out scores."""
+        from .. import boost
+        self.device_eval_: Dict[str, Dict[str, float]] = {}
+        for col, ycol in labels.items():
+            self.__models[col] = boost.make_classifier(params, **stop).fit_binned(data, ycol, *fit_args)
+            yield col, ycol, self.__models[col]
 
     def fit_batch(self, games: pd.DataFrame, actions: pd.DataFrame, learner: str = 'device',
                   val_size: float = 0.0, nr_actions: int = 10,
@@ -334,14 +339,10 @@ class VAEP:
         keys = boost.row_keys(actions['game_id'].to_numpy(), actions['action_id'].to_numpy(), ab.device) \
             if sampled else None
         if sample_weight is not None:
-            sample_weight = torch.from_numpy(np.ascontiguousarray(sample_weight)).to(ab.device)
-        self.device_eval_ = {}
-        for col in ('scores', 'concedes'):
-            ycol = getattr(lb, col)
-            clf = boost.make_classifier(params, **stop).fit_binned(
-                data, ycol, rows, val_rows if stop['early_stopping_rounds'] is not None else None,
-                sample_weight, keys)
-            self.__models[col] = clf
+            sample_weight = boost.weights_to_device(sample_weight, ab.device)
+        labels = {col: getattr(lb, col) for col in ('scores', 'concedes')}
+        eval_rows = val_rows if stop['early_stopping_rounds'] is not None else None
+        for col, ycol, clf in self._fit_labels(labels, params, stop, data, rows, eval_rows, sample_weight, keys):
             if val_rows is not None and val_rows.numel():
                 p = TreeEnsemble.from_model(clf).predict_blocks(fb)
                 self.device_eval_[col] = metrics.binary_scores(ycol[:ab.n][val_rows].contiguous(),

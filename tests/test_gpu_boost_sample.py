@@ -376,6 +376,33 @@ def test_neutral_parameters_change_nothing(sa, game, monkeypatch):
     assert ones.column_samples_ is None
 
 
+def test_launch_sequence_of_a_tuned_fit(sa, game):
+    """The (family, entry point) sequence of a tuned fit, written out from the contract: per round
+    the tuned gradients; per level the bitmap histograms always, the sampled bin histograms exactly
+    when the round's sample holds a numeric feature, the tuned split search and the advance; then
+    the leaf values and the margin; after the last round the plain gradients for ``p_``."""
+    D, T = 2, 5
+    for which in ('all_on', 'one_column'):
+        clf = sa['boost'].TunedGBTClassifier(**{**FITS[which], 'max_depth': D, 'n_estimators': T})
+        seq = _families(sa, clf, lambda c: c.fit_blocks(game['fb'], game['yd'], cuts=game['cuts'],
+                                                        sample_weight=game['w']))
+        assert len(clf.column_samples_) == T
+        numeric = [bool((~game['is_bool'][S]).any()) for S in clf.column_samples_]
+        if which == 'one_column':  # one feature a round: rounds with and without a numeric one occur
+            assert True in numeric and False in numeric, numeric
+        want = []
+        for t in range(T):
+            want.append(('grad', 'sa_boost_grad_ex'))
+            for _ in range(D):
+                want.append(('hist_bits', 'sa_boost_hist_bits'))
+                if numeric[t]:
+                    want.append(('hist_bins', 'sa_boost_hist_bins_ex'))
+                want += [('split', 'sa_boost_split_ex'), ('advance', 'sa_boost_advance')]
+            want += [('split', 'sa_boost_split_ex'), ('advance', 'sa_boost_advance')]
+        want.append(('grad', 'sa_boost_grad'))
+        assert seq == want, which
+
+
 def test_weight_duplication_on_the_device(sa, game):
     """Uniform weight 2 against the table stacked twice (tests/test_boost_sample_host.py)."""
     boost, fb = sa['boost'], game['fb']
