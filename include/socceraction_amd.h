@@ -718,12 +718,15 @@ int sa_tree_predict_staged(const sa_tree_model* model, const int32_t* bool_cols,
  * SA_GROUP_CHUNK_ROWS rows in an LDS table of SA_GROUP_LDS_SLOTS slots (the slot is the code
  * when n_groups <= SA_GROUP_LDS_SLOTS, else (code * SA_GROUP_HASH_MUL mod 2^32) >> 24 with
  * linear probing) and flushes it with 64-bit integer atomics when a chunk ends or the table is
- * more than half full.  Columns aligned to 16 bytes are read with 16-byte loads.
+ * more than half full.  Columns aligned to 16 bytes are read with 16-byte loads.  The grid is
+ * capped at SA_GROUP_WG_PER_CU workgroups per compute unit: with more chunks than that, a
+ * workgroup takes chunks blockIdx.x, blockIdx.x + gridDim.x, ...
  * sa_group_finalize: out [n_cols][n_groups] f64, each total rounded once (nearest, ties to even)
  * and scaled by 2^(scale_exp - 95). */
 #define SA_GROUP_MAX_COLS 8
 #define SA_GROUP_LDS_SLOTS 256
 #define SA_GROUP_CHUNK_ROWS 8192
+#define SA_GROUP_WG_PER_CU 4
 #define SA_GROUP_HASH_MUL 2654435761u
 #define SA_GROUP_ERR_KEY 1
 #define SA_GROUP_ERR_NONFINITE 2
@@ -751,7 +754,8 @@ int sa_group_finalize(const int64_t* limbs, int32_t n_groups, int32_t n_cols,
  * (NAN), p outside [0, 1] or infinite (RANGE), y neither 0 nor 1 (LABEL); a row that sets a bit
  * adds nothing, its count included.  Each thread sums in int64, the workgroup reduces, and one set
  * of 64-bit integer atomics per workgroup reaches the outputs; a workgroup takes
- * SA_METRIC_CHUNK_ROWS contiguous rows per loop step.
+ * SA_METRIC_CHUNK_ROWS contiguous rows per loop step; the grids of the three row kernels are capped
+ * at SA_METRIC_WG_PER_CU workgroups per compute unit.
  * sa_metric_finalize (host pointers, no device work): out[0] = Brier score, out[1] = log loss,
  * each sa_fx_finalize(limb sums) / count[0].
  * AUROC = U2 / (2 * n_pos * n_neg) with the integer U2 = sum over (positive, negative) pairs of
@@ -768,6 +772,7 @@ int sa_group_finalize(const int64_t* limbs, int32_t n_groups, int32_t n_cols,
 #define SA_METRIC_BRIER_EXP 1
 #define SA_METRIC_LOGLOSS_EXP 6
 #define SA_METRIC_CHUNK_ROWS 4096
+#define SA_METRIC_WG_PER_CU 8
 #define SA_METRIC_ERR_NAN 1
 #define SA_METRIC_ERR_RANGE 2
 #define SA_METRIC_ERR_LABEL 4
@@ -849,7 +854,14 @@ int sa_auc_count(const uint8_t* y, const void* p, int32_t f32, int64_t n, const 
  *   reg_alpha, in place of G, GL and GR in the gain and the leaf value; every integer sum scaled
  *   by 2^(shift - 30) (so min_child_weight compares weighted hessians); and feature_mask
  *   [n_features] (NULL: all): a feature whose byte is 0 is no split candidate (best_cut = -1).
- * sa_boost_row_keys: keys[j] = fm(game_id[j]) + action_id[j], wrapping. */
+ * sa_boost_row_keys: keys[j] = fm(game_id[j]) + action_id[j], wrapping.
+ *
+ * Launch shapes.  sa_boost_hist_bins: feature groups of fg = SA_BOOST_FEATURE_GROUP features,
+ *   halved while fg * n_nodes > 32; grid (gx, groups), gx = max(SA_BOOST_BINS_MIN_GRID_X,
+ *   SA_BOOST_BINS_WG_PER_CU * compute units / groups) capped at the row steps of
+ *   SA_BOOST_BINS_TILE rows; a workgroup takes steps blockIdx.x, blockIdx.x + gx, ...
+ *   sa_boost_hist_bits: one workgroup per SA_BOOST_BITS_TILE rows; the LDS sums of
+ *   SA_BOOST_BITS_ACC_BYTES / (16 * n_nodes) bool columns per pass over the columns. */
 #define SA_BOOST_MAX_DEPTH 6
 #define SA_BOOST_MAX_SHIFT 20
 #define SA_BOOST_SALT_ROWS 0x726F77ull
@@ -862,6 +874,9 @@ int sa_auc_count(const uint8_t* y, const void* p, int32_t f32, int64_t n, const 
 #define SA_BOOST_BITS_TILE 2048
 #define SA_BOOST_BINS_TILE 1024
 #define SA_BOOST_FEATURE_GROUP 4
+#define SA_BOOST_BINS_WG_PER_CU 4
+#define SA_BOOST_BINS_MIN_GRID_X 8
+#define SA_BOOST_BITS_ACC_BYTES 131072
 typedef struct sa_boost_node {
   int64_t G, H;      /* sums of gq, hq over the node's rows */
   double gain;       /* of its split (0 for a leaf) */

@@ -34,10 +34,12 @@ SA_NUM_TILE_QUANTUM = 128
 SA_GROUP_MAX_COLS = 8
 SA_GROUP_LDS_SLOTS = 256  # slots of the grouped sums' LDS table
 SA_GROUP_CHUNK_ROWS = 8192
+SA_GROUP_WG_PER_CU = 4  # sa_group_sums: the grid's cap in workgroups per compute unit
 SA_GROUP_HASH_MUL = 2654435761
 SA_GROUP_ERR_KEY, SA_GROUP_ERR_NONFINITE, SA_GROUP_ERR_RANGE = 1, 2, 4
 SA_METRIC_BRIER_EXP, SA_METRIC_LOGLOSS_EXP = 1, 6  # scale exponents of the score terms
 SA_METRIC_CHUNK_ROWS = 4096
+SA_METRIC_WG_PER_CU = 8  # the score kernels' grid cap in workgroups per compute unit
 SA_METRIC_ERR_NAN, SA_METRIC_ERR_RANGE, SA_METRIC_ERR_LABEL = 1, 2, 4
 SA_AUC_LDS_SAMPLE = 1024  # sorted minority keys sa_auc_count keeps in LDS
 # boosted-tree training (sa_boost.hip; mirrors include/socceraction_amd.h)
@@ -45,6 +47,8 @@ SA_BOOST_MAX_DEPTH, SA_BOOST_MAX_CUTS, SA_BOOST_MISSING_BIN, SA_BOOST_NO_NODE = 
 SA_BOOST_MAX_LEVEL_NODES, SA_BOOST_FEATURE_GROUP = 32, 4
 SA_BOOST_MAX_SHIFT, SA_BOOST_SALT_ROWS, SA_BOOST_SALT_COLS = 20, 0x726F77, 0x636F6C
 SA_BOOST_BIN_TILE, SA_BOOST_BITS_TILE, SA_BOOST_BINS_TILE = 1024, 2048, 1024
+# sa_boost_hist_bins' grid: gx = max(MIN_GRID_X, WG_PER_CU * CUs / groups); sa_boost_hist_bits' LDS sums per pass
+SA_BOOST_BINS_WG_PER_CU, SA_BOOST_BINS_MIN_GRID_X, SA_BOOST_BITS_ACC_BYTES = 4, 8, 131072
 SA_OK, SA_EINVAL, SA_EHIP, SA_EDATA, SA_ENOMEM = 0, -1, -2, -3, -4
 
 # enum sa_xfn (order matters: mirrors include/socceraction_amd.h)

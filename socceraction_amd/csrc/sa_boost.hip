@@ -33,7 +33,7 @@ constexpr int BB_TILE = SA_BOOST_BIN_TILE;
 constexpr int HB_THREADS = 256;                       // sa_boost_hist_bits
 constexpr int HB_TILE = SA_BOOST_BITS_TILE;           // rows per workgroup
 constexpr int HB_WORDS = HB_TILE / 64;
-constexpr int HB_ACC_BYTES = 128 * 1024;              // LDS for the (column, node) sums of one pass
+constexpr int HB_ACC_BYTES = SA_BOOST_BITS_ACC_BYTES; // LDS for the (column, node) sums of one pass
 constexpr int HN_THREADS = 256;                       // sa_boost_hist_bins: 4 rows per thread and step
 constexpr int HN_TILE = SA_BOOST_BINS_TILE;
 constexpr int HN_FG = SA_BOOST_FEATURE_GROUP;
@@ -684,8 +684,8 @@ int hist_bins(const uint8_t* bins, int64_t ld, const int32_t* num_feat, const in
   const size_t lds = (size_t)fg * n_nodes * BINS * 16;
   const int64_t steps = (n + HN_TILE - 1) / HN_TILE;
   const int groups = (n_num + fg - 1) / fg;
-  int64_t gx = (int64_t)device_cus(current_device()) * 4 / groups;
-  if (gx < 8) gx = 8;
+  int64_t gx = (int64_t)device_cus(current_device()) * SA_BOOST_BINS_WG_PER_CU / groups;
+  if (gx < SA_BOOST_BINS_MIN_GRID_X) gx = SA_BOOST_BINS_MIN_GRID_X;
   if (gx > steps) gx = steps;
   if (num_rows)
     hipLaunchKernelGGL((boost_hist_bins_kernel<true>), dim3((unsigned)gx, (unsigned)groups), dim3(HN_THREADS), lds,

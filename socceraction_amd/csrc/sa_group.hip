@@ -251,7 +251,7 @@ extern "C" int sa_group_sums(const int32_t* key, const void* const* cols, int32_
   if (int rc = check_exps("sa_group_sums", scale_exp, n_cols, &C)) return rc;
   if (n == 0) return SA_OK;
   const int64_t n_chunks = (n + GS_CHUNK - 1) / GS_CHUNK;
-  const int64_t resident = (int64_t)device_cus(current_device()) * 4;
+  const int64_t resident = (int64_t)device_cus(current_device()) * SA_GROUP_WG_PER_CU;
   const dim3 grid((unsigned)(n_chunks < resident ? n_chunks : resident));
   if (f32)
     launch_sums<float>(n_cols, grid, (hipStream_t)stream, key, C, n, n_groups, (int)vec, limbs, count, err);

@@ -321,7 +321,7 @@ bool vec_ok(const void* y, const void* p) { return ((uintptr_t)y & 3u) == 0 && a
 
 dim3 rows_grid(int64_t n) {
   const int64_t n_chunks = (n + MT_CHUNK - 1) / MT_CHUNK;
-  const int64_t resident = (int64_t)device_cus(current_device()) * 8;
+  const int64_t resident = (int64_t)device_cus(current_device()) * SA_METRIC_WG_PER_CU;
   return dim3((unsigned)(n_chunks < resident ? n_chunks : resident));
 }
 }  // namespace

@@ -238,7 +238,8 @@ def test_boost_entry_points_validate_without_a_gpu():
     assert b'sa_boost' in lib.sa_last_error()
     for name in ('SA_BOOST_MAX_DEPTH', 'SA_BOOST_MAX_CUTS', 'SA_BOOST_MISSING_BIN', 'SA_BOOST_NO_NODE',
                  'SA_BOOST_MAX_LEVEL_NODES', 'SA_BOOST_BIN_TILE', 'SA_BOOST_BITS_TILE', 'SA_BOOST_BINS_TILE',
-                 'SA_BOOST_FEATURE_GROUP'):
+                 'SA_BOOST_FEATURE_GROUP', 'SA_BOOST_BINS_WG_PER_CU', 'SA_BOOST_BINS_MIN_GRID_X',
+                 'SA_BOOST_BITS_ACC_BYTES'):
         import os
         root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
         with open(os.path.join(root, 'include', 'socceraction_amd.h')) as f:

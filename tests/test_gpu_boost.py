@@ -16,6 +16,9 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
 
 BIN_TILE, BITS_TILE, BINS_TILE, FEATURE_GROUP = 1024, 2048, 1024, 4
+# the launch shapes: sa_boost_hist_bins' gx = max(BINS_MIN_GRID_X, BINS_WG_PER_CU * CUs / groups);
+# sa_boost_hist_bits keeps the sums of BITS_ACC_BYTES / (16 * nodes) bool columns per pass
+BINS_WG_PER_CU, BINS_MIN_GRID_X, BITS_ACC_BYTES = 4, 8, 131072
 
 
 @pytest.fixture(scope='module')
@@ -24,6 +27,8 @@ def sa():
     _native.load_library()
     assert (_native.SA_BOOST_BIN_TILE, _native.SA_BOOST_BITS_TILE, _native.SA_BOOST_BINS_TILE,
             _native.SA_BOOST_FEATURE_GROUP) == (BIN_TILE, BITS_TILE, BINS_TILE, FEATURE_GROUP)
+    assert (_native.SA_BOOST_BINS_WG_PER_CU, _native.SA_BOOST_BINS_MIN_GRID_X, _native.SA_BOOST_BITS_ACC_BYTES) == \
+        (BINS_WG_PER_CU, BINS_MIN_GRID_X, BITS_ACC_BYTES)
     return dict(batch=batch, ops=ops, trees=trees, boost=boost)
 
 
@@ -67,6 +72,33 @@ def test_bins_of_the_golden_game(sa, game, tile):
     data = sa['boost'].bin_blocks(fb)
     assert data.bins.dtype == torch.uint8 and data.bins.shape == (len(data.num_feat), data.ld)
     np.testing.assert_array_equal(data.host_bins(), game['B'])
+
+
+def test_cuts_from_a_sample_of_the_rows(sa):
+    """More than 65,536 actions: the cuts come from the rows floor(i * n / 65536), gathered from
+    the tiled device blocks, not from every row."""
+    from oracle import vaep_oracle as vo
+    from socceraction_amd import synthetic
+    boost, ops = sa['boost'], sa['ops']
+    ab = sa['batch'].ActionBatch.from_columns(synthetic.spadl_games(43, seed=5))
+    n = ab.n
+    assert boost.SAMPLE_ROWS == 65536 < n < 80000
+    assert len(np.unique(br.sample_rows(n))) == 65536 and (np.diff(br.sample_rows(n)) == 2).any()
+    fb = ops.features(ab, vo.SPADL_DEFAULT, 3, bool_bits=True)
+    b, f, i = ops.features(ab, vo.SPADL_DEFAULT, 3).to_numpy()
+    host = {'b': b.astype(bool), 'f': f, 'i': i}
+    cols = [np.ascontiguousarray(host[k][c, :n]) for _, k, c in fb.plan.order]
+    want = [br.cuts_of(c, c.dtype == np.bool_) for c in cols]
+    got = boost.make_cuts(fb)
+    assert len(got) == len(want) == 568
+    for a, w in zip(got, want):
+        np.testing.assert_array_equal(a, w)
+    assert max(len(w) for w in want) == 254  # the rank rule of a column with many values
+    np.testing.assert_array_equal(boost.bin_blocks(fb).host_bins(),
+                                  np.stack([br.bins_of(br.cast32(c), k) for c, k in zip(cols, want)]))
+    rows = np.arange(0, n, 2)
+    for a, c in zip(boost.make_cuts(fb, rows=rows), cols):
+        np.testing.assert_array_equal(a, br.cuts_of(c[rows], c.dtype == np.bool_))
 
 
 def _edge_table(n):
@@ -148,14 +180,9 @@ HIST_CASES = [  # n, F_num, n_bool, nodes
     (70001, 1, 1, 8), (70001, FEATURE_GROUP + 1, 0, 1), (513, 0, 3, 2)]
 
 
-@pytest.mark.parametrize('n,f_num,n_bool,nodes', HIST_CASES)
-def test_histograms_equal_add_at(sa, n, f_num, n_bool, nodes):
-    X, cuts = _hist_table(n, f_num, n_bool, seed=n + nodes)
-    data = sa['boost'].bin_host(X, cuts=cuts)
-    B = data.host_bins()
-    if f_num:
-        np.testing.assert_array_equal(B[0], np.full(n, 7))
-        assert f_num == 1 or n < 256 or set(B[1].tolist()) == set(range(256))
+def _level_rows(n, nodes):
+    """Random gradients and level-local nodes of n rows: node 1 is empty, a tenth of the rows take
+    no part; with two nodes, node 0 holds every row."""
     rng = np.random.default_rng(n)
     gq = rng.integers(-2 ** 30, 2 ** 30 + 1, n).astype(np.int32)
     hq = rng.integers(0, 2 ** 28 + 1, n).astype(np.int32)
@@ -165,6 +192,16 @@ def test_histograms_equal_add_at(sa, n, f_num, n_bool, nodes):
         node[rng.random(n) < 0.1] = 255        # rows that take no part
     if nodes == 2:
         node[:] = 0                            # a node holding every row
+    return gq, hq, node
+
+
+def _check_histograms(sa, X, cuts, n, f_num, n_bool, nodes):
+    data = sa['boost'].bin_host(X, cuts=cuts)
+    B = data.host_bins()
+    if f_num:
+        np.testing.assert_array_equal(B[0], np.full(n, 7))
+        assert f_num == 1 or n < 256 or set(B[1].tolist()) == set(range(256))
+    gq, hq, node = _level_rows(n, nodes)
     hist, tot = sa['boost'].histograms(data, _dev(gq), _dev(hq), _dev(node), nodes, return_totals=True)
     assert hist.dtype == torch.int64 and tuple(hist.shape) == (nodes, f_num + n_bool, 256, 2)
     want = br.histograms(B, gq, hq, node, nodes)
@@ -172,6 +209,94 @@ def test_histograms_equal_add_at(sa, n, f_num, n_bool, nodes):
     np.testing.assert_array_equal(tot, want[:, 0].sum(1))
     if nodes > 1:
         assert not want[1].any()
+    return data, B, want
+
+
+@pytest.mark.parametrize('n,f_num,n_bool,nodes', HIST_CASES)
+def test_histograms_equal_add_at(sa, n, f_num, n_bool, nodes):
+    X, cuts = _hist_table(n, f_num, n_bool, seed=n + nodes)
+    _check_histograms(sa, X, cuts, n, f_num, n_bool, nodes)
+
+
+def bins_launch(f_num, nodes):
+    """(fg, groups, gx before the cap at the row steps) of sa_boost_hist_bins on this device, as
+    include/socceraction_amd.h states the launch shape."""
+    fg = FEATURE_GROUP
+    while fg > 1 and fg * nodes > 32:
+        fg >>= 1
+    groups = (f_num + fg - 1) // fg
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    return fg, groups, max(BINS_MIN_GRID_X, BINS_WG_PER_CU * cus // groups)
+
+
+def _trip_case(nodes, tail):
+    """128 numeric columns and a row count at which some workgroups of the bin histogram kernel
+    take three row steps (s += gridDim.x), the last step partial."""
+    f_num = 128
+    fg, groups, gx = bins_launch(f_num, nodes)
+    assert (fg, groups) == ((1, 128) if nodes == 32 else (4, 32))
+    n = 2 * gx * BINS_TILE + tail
+    assert n < 2 ** 30, f'gx = {gx} puts n = {n} past 2^30 rows'
+    steps = (n + BINS_TILE - 1) // BINS_TILE
+    assert steps > 2 * gx and n % BINS_TILE
+    return n, f_num, gx, steps
+
+
+@pytest.mark.parametrize('nodes,tail', [(32, BINS_TILE + 3), (1, 1027)], ids=['fg=1-gx-at-its-floor', 'fg=4'])
+def test_histograms_over_more_row_steps_than_workgroups(sa, nodes, tail):
+    n, f_num, gx, steps = _trip_case(nodes, tail)
+    print('nodes', nodes, 'gx', gx, 'n', n, 'steps', steps)
+    X, cuts = _hist_table(n, f_num, 0, seed=n + nodes)
+    _check_histograms(sa, X, cuts, n, f_num, 0, nodes)
+
+
+def test_sampled_histograms_over_more_row_steps_than_workgroups(sa):
+    """sa_boost_hist_bins_ex at the first shape: a column list of 64 of the 128 matrix rows, out
+    of order.  Only those features' histograms are filled, and they are the restatement's."""
+    boost, nodes = sa['boost'], 32
+    n, f_num, gx, steps = _trip_case(nodes, BINS_TILE + 3)
+    X, cuts = _hist_table(n, f_num, 0, seed=n + nodes)
+    # a bool feature first: matrix row r holds feature r + 1, so a list entry's two numbers differ
+    X = pd.concat([pd.DataFrame({'flag': np.zeros(n, bool)}), X], axis=1)
+    cuts = [np.array([0.5], np.float32)] + cuts
+    data = boost.bin_host(X, cuts=cuts)
+    B = data.host_bins()
+    assert data.num_feat.tolist() == list(range(1, f_num + 1)) and len(data.bit_feat) == 1
+    gq, hq, node = _level_rows(n, nodes)
+    want = br.histograms(B, gq, hq, node, nodes)
+    rows = np.random.default_rng(4).permutation(f_num)[:64].astype(np.int32)
+    assert (np.diff(rows) < 0).any() and len(set(rows.tolist())) == 64
+    feats = data.num_feat[rows]
+    fg, groups, gx64 = bins_launch(len(rows), nodes)
+    assert steps > gx64  # the sampled launch has fewer groups: its own gx
+    nd = torch.from_numpy(node.astype(np.int64)).cuda()
+    heap = boost._pad(torch.where(nd == 255, nd, nd + nodes - 1).to(torch.uint8), data.ld, torch.uint8, 255)
+    gd, hd = boost._pad(_dev(gq), data.ld, torch.int32), boost._pad(_dev(hq), data.ld, torch.int32)
+    hist = torch.zeros((nodes, data.n_features, 256, 2), dtype=torch.int64, device='cuda')
+    tree = torch.zeros((4 * nodes, boost.NODE_DTYPE.itemsize), dtype=torch.uint8, device='cuda')
+    cols = (None, None, 0, _dev(feats.astype(np.int32)), _dev(rows), len(rows))  # no bool feature sampled
+    boost._hist(boost._run, boost._stream(), data, gd, hd, heap, nodes, hist, tree, True, cols=cols)
+    got = hist.cpu().numpy()
+    np.testing.assert_array_equal(got[:, feats], want[:, feats])
+    rest = np.setdiff1d(np.arange(data.n_features), feats)
+    assert len(rest) == 65 and not got[:, rest].any() and want[:, rest[1:]].any()
+    tab = tree.cpu().numpy().view(boost.NODE_DTYPE).reshape(-1)[nodes - 1:2 * nodes - 1]
+    np.testing.assert_array_equal(np.stack([tab['G'], tab['H']], 1), want[:, 1].sum(1))
+
+
+@pytest.mark.parametrize('n,f_num,n_bool,nodes', [(4101, 1, 300, 32), (4101, 0, 600, 16)])
+def test_bitmap_histograms_over_two_column_passes(sa, n, f_num, n_bool, nodes):
+    """More bool columns than the LDS sums of one pass hold (c0 += cc): the second pass holds a
+    column of ones and a column of zeros, as the first does."""
+    cc = BITS_ACC_BYTES // (16 * nodes)
+    assert cc < n_bool <= 2 * cc
+    X, cuts = _hist_table(n, f_num, n_bool, seed=n + nodes)
+    X[f'b{cc}'] = True
+    X[f'b{cc + 1}'] = False
+    assert X['b0'].all() and not X['b1'].any() and 0 < X[f'b{cc + 2}'].sum() < n
+    _, B, want = _check_histograms(sa, X, cuts, n, f_num, n_bool, nodes)
+    assert B[f_num + cc].all() and not B[f_num + cc + 1].any()
+    assert not want[:, f_num + cc, 0].any() and want[:, f_num + cc, 1].any()
 
 
 def test_histograms_do_not_wrap_and_cancel_exactly(sa):
@@ -307,28 +432,95 @@ def fits(sa, game):
             for k, p in FITS.items()}
 
 
-@pytest.mark.parametrize('which', sorted(FITS))
-def test_whole_fit_replayed_round_by_round(sa, game, fits, which):
-    clf, params = fits[which], FITS[which]
+def _replay(clf, params, B, y, cuts):
+    """A recorded fit against the restatement, round by round: the restated tree is built from
+    the device's p_t; node tables and margins are compared as bytes.  Returns the split nodes."""
     P = clf.record_['p'].cpu().numpy()
     M = clf.record_['margin'].cpu().numpy()
     assert clf.trees_.shape == (params['n_estimators'], 2 ** (params['max_depth'] + 1) - 1)
-    for a, b in zip(clf.cuts_, game['cuts']):
+    for a, b in zip(clf.cuts_, cuts):
         np.testing.assert_array_equal(a, b)
-    m = np.full(len(game['y']), br.base_margin(0.5), np.float32)
+    m = np.full(len(y), br.base_margin(0.5), np.float32)
     split_nodes = 0
     for t in range(params['n_estimators']):
         np.testing.assert_allclose(P[t], br.probability(m), rtol=1e-6, atol=0)
-        gq, hq = br.quantise(P[t], game['y'])       # the restated tree from the device's p_t
-        tab, node = br.build_tree(game['B'], gq, hq, game['cuts'], params)
+        gq, hq = br.quantise(P[t], y)       # the restated tree from the device's p_t
+        tab, node = br.build_tree(B, gq, hq, cuts, params)
         assert tab.tobytes() == clf.trees_[t].tobytes(), (t, tab, clf.trees_[t])
         m = br.update_margin(m, tab, node)
         assert m.tobytes() == M[t].tobytes(), t
         split_nodes += int((tab['feature'] >= 0).sum())
     assert m.tobytes() == clf.margin_.cpu().numpy().tobytes()
+    return split_nodes
+
+
+@pytest.mark.parametrize('which', sorted(FITS))
+def test_whole_fit_replayed_round_by_round(sa, game, fits, which):
+    clf, params = fits[which], FITS[which]
+    split_nodes = _replay(clf, params, game['B'], game['y'], game['cuts'])
     assert split_nodes >= params['n_estimators']  # every round found a split
     if which == 'd6':
         assert (clf.trees_['exists'][:, 63:] != 0).any()  # the deepest level is reached
+
+
+WIDE_ROWS, WIDE_NUM, WIDE_BOOL, WIDE_VALUES = 40000, 128, 260, 64
+WIDE_FIT = dict(n_estimators=2, max_depth=6)
+_WIDE = {}
+
+
+def wide_table():
+    """A host table whose fit takes many workgroups at every level: 40,000 rows (twenty bitmap
+    tiles, forty bin steps), 128 numeric columns of 64 distinct values (about 3% NaN) and 260 bool
+    columns (two bitmap passes at 32 nodes); the labels depend on numeric column 3 and on bool
+    columns 256..259, the columns of the second pass, weakly enough for the trees to split on
+    them down to level 5.  The cuts are fixed: column j's values are
+    k / 4 - j, k < 64, so its cuts are those of k = 1..63 and a value's bin is its k.  Built once."""
+    if not _WIDE:
+        n = WIDE_ROWS
+        rng = np.random.default_rng(40)
+        cols, cuts, B = {}, [], np.empty((WIDE_NUM + WIDE_BOOL, n), np.uint8)
+        for j in range(WIDE_NUM):
+            k = rng.integers(0, WIDE_VALUES, n)
+            v = k * 0.25 - j
+            nan = rng.random(n) < 0.03
+            v[nan] = np.nan
+            cols[f'n{j}'] = v
+            cuts.append((np.arange(1, WIDE_VALUES) * 0.25 - j).astype(np.float32))
+            B[j] = np.where(nan, 255, k)
+        for j in range(WIDE_BOOL):
+            b = rng.random(n) < (0.5 if j % 7 == 2 else 0.1)
+            cols[f'b{j}'] = b
+            cuts.append(np.array([0.5], np.float32))
+            B[WIDE_NUM + j] = b
+        k3 = np.where(B[3] == 255, 32, B[3]).astype(np.float64)
+        late = B[WIDE_NUM + 256:].astype(np.float64)  # the four bool columns of the second pass
+        z = -1.5 + 0.05 * (k3 - 32) + 0.6 * late[0] + 0.8 * late[1] + 0.6 * late[2] + 0.6 * late[3]
+        rng = np.random.default_rng(41)
+        y = (rng.random(n) < 1 / (1 + np.exp(-(z + 0.5 * rng.standard_normal(n))))).astype(np.uint8)
+        _WIDE.update(X=pd.DataFrame(cols), y=y, cuts=cuts, B=B)
+    return _WIDE
+
+
+def test_whole_fit_over_many_workgroups(sa):
+    """Every level's histograms come from more than one row step per workgroup and twenty bitmap
+    tiles; level 5 takes two bitmap passes; twenty workgroups add the node totals."""
+    t = wide_table()
+    X, y, cuts, B = t['X'], t['y'], t['cuts'], t['B']
+    n = len(y)
+    for nodes in (1, 32):
+        fg, groups, gx = bins_launch(WIDE_NUM, nodes)
+        assert (n + BINS_TILE - 1) // BINS_TILE > gx, (nodes, gx)
+    assert WIDE_BOOL > BITS_ACC_BYTES // (16 * 32) and (n + BITS_TILE - 1) // BITS_TILE == 20
+    np.testing.assert_array_equal(sa['boost'].bin_host(X, cuts=cuts).host_bins(), B)
+    clf = sa['boost'].DeviceGBTClassifier(record=True, **WIDE_FIT).fit(X, y, cuts=cuts)
+    _replay(clf, WIDE_FIT, B, y, cuts)
+    splits = (clf.trees_['feature'] >= 0) & (clf.trees_['exists'] != 0)
+    assert splits[:, 0].all()  # both rounds split
+    assert splits[:, 31:63].any(axis=1).all()  # ... down to level 5, whose histograms decide splits
+    assert (clf.trees_['exists'][:, 63:] != 0).any(axis=1).all()
+    # level 5 splits on a bool column its second bitmap pass summed, in both rounds
+    second_pass = splits & (clf.trees_['feature'] >= WIDE_NUM + BITS_ACC_BYTES // (16 * 32))
+    assert second_pass[:, 31:63].any(axis=1).all()
 
 
 def test_export_closes_the_loop(sa, game, fits):

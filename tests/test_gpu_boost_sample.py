@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
 
 FEATURE_GROUP = 4
+BINS_TILE, BINS_WG_PER_CU, BINS_MIN_GRID_X = 1024, 4, 8  # sa_boost_hist_bins' launch shape (tests/test_gpu_boost.py)
 
 
 @pytest.fixture(scope='module')
@@ -25,6 +26,8 @@ def sa():
     from socceraction_amd import _native, batch, boost, ops, trees
     _native.load_library()
     assert _native.SA_BOOST_FEATURE_GROUP == FEATURE_GROUP
+    assert (_native.SA_BOOST_BINS_TILE, _native.SA_BOOST_BINS_WG_PER_CU, _native.SA_BOOST_BINS_MIN_GRID_X) == \
+        (BINS_TILE, BINS_WG_PER_CU, BINS_MIN_GRID_X)
     return dict(batch=batch, ops=ops, trees=trees, boost=boost, native=_native)
 
 
@@ -337,6 +340,46 @@ def test_whole_fit_replayed_round_by_round(sa, game, fits, which):
     assert imp.shape == (F,) and abs(float(imp.sum()) - 1) < 1e-5 and set(np.flatnonzero(imp)) <= set(used.tolist())
     cover = sa['boost'].importances(clf.trees_, F, 'total_cover', e)
     assert abs(float(cover.sum()) - 1) < 1e-5
+
+
+WIDE_TUNED = dict(n_estimators=2, max_depth=6, subsample=0.5, colsample_bytree=0.5, random_state=7)
+
+
+def test_tuned_fit_over_many_workgroups(sa):
+    """The 40,000 x 388 table of tests/test_gpu_boost.py (more row steps than workgroups at every
+    level, twenty bitmap tiles) under a row sample, a column sample -- the sampled bin histograms
+    (sa_boost_hist_bins_ex) past one trip -- and weights with shift 3."""
+    from test_gpu_boost import bins_launch, wide_table
+    t = wide_table()
+    X, y, cuts, B = t['X'], t['y'], t['cuts'], t['B']
+    F, n = B.shape
+    w = (np.random.default_rng(1).random(n) * 5).astype(np.float32)
+    w[::17] = 0
+    w[3] = 8.0
+    params = WIDE_TUNED
+    clf = sa['boost'].TunedGBTClassifier(record=True, **params).fit(X, y, cuts=cuts, sample_weight=w)
+    we = bs.effective_weight(w, y, 1.0)
+    e = bs.shift_of(we.max())
+    assert clf.quant_shift_ == e == 3 and clf.trees_.shape == (2, 127)
+    P = clf.record_['p'].cpu().numpy()
+    M = clf.record_['margin'].cpu().numpy()
+    m = np.full(n, br.base_margin(0.5), np.float32)
+    keys = np.arange(n, dtype=np.int64)
+    for r in range(2):
+        np.testing.assert_allclose(P[r], br.probability(m), rtol=1e-6, atol=0)
+        rows, cols = bs.round_inputs(params, r, F, keys)
+        np.testing.assert_array_equal(clf.column_samples_[r], cols)
+        n_num = int((cols < 128).sum())
+        assert len(cols) == F // 2 and 32 < n_num < 96 and 0.45 * n < rows.sum() < 0.55 * n
+        assert (n + BINS_TILE - 1) // BINS_TILE > bins_launch(n_num, 32)[2]  # level 5: more row steps than workgroups
+        gq, hq = bs.quantise(P[r], y, we, e, rows)       # the restated tree from the device's p_t
+        tab, node = bs.build_tree(B, gq, hq, cuts, params, e, cols)
+        assert tab.tobytes() == clf.trees_[r].tobytes(), (r, tab, clf.trees_[r])
+        m = br.update_margin(m, tab, node)
+        assert m.tobytes() == M[r].tobytes(), r
+    assert m.tobytes() == clf.margin_.cpu().numpy().tobytes()
+    splits = (clf.trees_['feature'] >= 0) & (clf.trees_['exists'] != 0)
+    assert splits[:, 0].all() and splits[:, 31:63].any(axis=1).all()  # both rounds split, down to level 5
 
 
 def _families(sa, clf, fit):

@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
 
 CHUNK, SAMPLE = 4096, 1024
+WG_PER_CU = 8  # the row kernels' grid cap: workgroups per compute unit
 SIZES = [0, 1, 63, 64, 65, 255, 256, 257, CHUNK - 1, CHUNK, CHUNK + 1, 5000]
 NMAX = 5008  # >= max(SIZES), a multiple of 16
 BRIER_EXP, LOGLOSS_EXP = 1, 6
@@ -28,6 +29,7 @@ def sa():
     from socceraction_amd import _native, ops
     _native.load_library()
     assert (_native.SA_METRIC_CHUNK_ROWS, _native.SA_AUC_LDS_SAMPLE) == (CHUNK, SAMPLE)
+    assert _native.SA_METRIC_WG_PER_CU == WG_PER_CU
     assert (_native.SA_METRIC_BRIER_EXP, _native.SA_METRIC_LOGLOSS_EXP) == (BRIER_EXP, LOGLOSS_EXP)
     return ops
 
@@ -208,6 +210,92 @@ def test_auc_keys_drops_the_keys_past_capacity(sa, cap, f32):
         ref_vals, ref_counts = np.unique(want, return_counts=True)
         idx = np.searchsorted(ref_vals, vals)
         assert (idx < len(ref_vals)).all() and (ref_vals[idx] == vals).all() and (counts <= ref_counts[idx]).all()
+
+
+# ----------------------------------------------------------------------------- past the grid cap
+PERIOD = 4099  # prime: consecutive chunks start at different offsets of the base rows
+
+
+def past_the_cap_rows():
+    """A row count just past the grid's cap of R workgroups on this device: workgroups 0 and 1
+    take a second chunk and the last chunk is partial (n is odd: a scalar tail)."""
+    R = WG_PER_CU * torch.cuda.get_device_properties(0).multi_processor_count
+    n = R * CHUNK + CHUNK + 777
+    assert n < 2 ** 30, f'{R} resident workgroups put n = {n} past the 2^30 rows the score kernels take'
+    assert n > R * CHUNK and (n + CHUNK - 1) // CHUNK == R + 2
+    return R, n
+
+
+@DTYPES
+def test_sums_of_more_chunks_than_resident_workgroups(sa, f32):
+    """metric_sums_kernel's second trip.  Row i is row i % PERIOD of rows(): every sum is the
+    base rows' term times its multiplicity -- integers for the counts and the Brier limbs, and
+    math.fsum of the float64 log-loss terms under the 1e-12 bar of
+    test_sums_equal_the_integer_restatement (its reasoning does not depend on n)."""
+    R, n = past_the_cap_rows()
+    y, p, limbs = rows(f32)
+    y, p, limbs = y[:PERIOD], p[:PERIOD], limbs[:PERIOD]
+    mult = n // PERIOD + (np.arange(PERIOD) < n % PERIOD).astype(np.int64)
+    assert int(mult.sum()) == n and mult.max() < 2 ** 12
+    acc = new_acc(sa).add(*padded(np.resize(y, n), np.resize(p, n)))
+    h = acc.buf.cpu().numpy()
+    assert h[8] == 0 and h[9] == 0
+    assert h[:2].tolist() == [n, int((mult * y).sum())]
+    assert h[2:5].tolist() == (mult[:, None] * limbs).sum(axis=0).tolist()
+    res = acc.finalize()
+    assert res['n'] == n and res['brier'] == py_finalize(*h[2:5].tolist(), BRIER_EXP) / n
+    # the kernel's contract for q: the complement and the clip in p's dtype, -log in float64
+    eps = np.finfo(p.dtype).eps
+    q = np.clip(np.where(y == 1, p, p.dtype.type(1) - p), eps, p.dtype.type(1) - eps)
+    assert q.dtype == p.dtype
+    terms = -np.log(q.astype(np.float64))
+    assert abs(math.fsum(terms.tolist()) / PERIOD - ref_log_loss(y, p)) <= 1e-12 * ref_log_loss(y, p)
+    want = math.fsum((terms * mult).tolist()) / n
+    print('f32' if f32 else 'f64', 'n', n, 'log_loss rel', abs(res['log_loss'] - want) / want)
+    assert abs(res['log_loss'] - want) <= 1e-12 * want
+
+
+@DTYPES
+@pytest.mark.parametrize('minority', [1, 0], ids=['few_positives', 'few_negatives'])
+def test_auroc_of_more_chunks_than_resident_workgroups(sa, minority, f32):
+    """The three AUROC kernels' second trip, the key stage carried from chunk to chunk: free
+    (not periodic) probabilities, about 20% minority rows, a band of heavy ties, exact 0 and 1."""
+    from socceraction_amd import _native
+    R, n = past_the_cap_rows()
+    rng = np.random.default_rng([23, minority, int(f32)])
+    y = (rng.random(n) < 0.2).astype(np.uint8)
+    p = np.clip(0.25 * y + 0.8 * rng.random(n), 0, 1)
+    band = rng.random(n) < 0.15
+    p[band] = np.round(p[band] * 64) / 64
+    p[rng.random(n) < 0.01] = 0.0
+    p[rng.random(n) < 0.01] = 1.0
+    p = p.astype(np.float32 if f32 else np.float64)
+    if not minority:
+        y = 1 - y
+    n_pos = int(y.sum())
+    m = n_pos if minority else n - n_pos
+    assert 0.15 * n < m < 0.25 * n and not np.signbit(p).any()
+    yd, pd_ = padded(y, p)
+    acc = sa.binary_metrics(yd, pd_)
+    h = acc.buf.cpu().tolist()
+    assert h[8] == 0 and h[:2] == [n, n_pos]
+    # U2 is a function of the multiset of rows: u2_reference on the rows reordered -- the positives
+    # first, ascending -- looks up sorted values, several times faster at this size
+    a, b = np.sort(p[y == 1]), p[y == 0]
+    assert len(a) == n_pos and len(a) + len(b) == n
+    assert h[9] == u2_reference(np.repeat(np.array([1, 0], np.uint8), [len(a), len(b)]), np.concatenate([a, b]))
+    assert acc.finalize()['auroc'] == h[9] / (2 * n_pos * (n - n_pos))
+    # sa_auc_keys itself: the cursor counts every minority row, the keys are their bit patterns
+    guard, fill = 64, -12345
+    keys = torch.full((m + guard,), fill, dtype=torch.int32 if f32 else torch.int64, device='cuda')
+    cursor = torch.zeros(1, dtype=torch.int64, device='cuda')
+    _native.check(_native.lib().sa_auc_keys(yd.data_ptr(), pd_.data_ptr(), int(f32), n, minority, keys.data_ptr(), m,
+                                            cursor.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    assert int(cursor.item()) == m
+    got = keys.cpu().numpy()
+    assert (got[m:] == fill).all()
+    kdt = np.uint32 if f32 else np.uint64
+    assert (np.sort(got[:m].view(kdt)) == np.sort(p[y == minority].view(kdt))).all()
 
 
 # ----------------------------------------------------------------------------- order independence

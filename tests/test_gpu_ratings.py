@@ -19,6 +19,7 @@ torch = pytest.importorskip('torch')
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SLOTS, CHUNK, HASH_MUL = 256, 8192, 2654435761
+WG_PER_CU = 4  # the grid's cap: workgroups per compute unit
 SIZES = [0, 1, 63, 64, 65, CHUNK - 1, CHUNK, CHUNK + 1, 5000]
 NMAX = 8208  # >= max(SIZES), a multiple of 16: every row of the value block is 16-byte aligned
 EXPS = [2, 1, 0, 3, 2, 5, -3, 2]
@@ -30,6 +31,7 @@ def sa():
     _native.load_library()
     assert (_native.SA_GROUP_LDS_SLOTS, _native.SA_GROUP_CHUNK_ROWS, _native.SA_GROUP_HASH_MUL) == \
         (SLOTS, CHUNK, HASH_MUL)
+    assert _native.SA_GROUP_WG_PER_CU == WG_PER_CU
     return ops
 
 
@@ -177,6 +179,63 @@ def test_tables_do_not_depend_on_order_chunking_or_shards(sa, G):
     assert torch.equal(one.finalize(), perm.finalize())
     one.check_errors()
     assert int(one.count.sum()) == n
+
+
+# ----------------------------------------------------------------------------- past the grid cap
+PERIOD = 4099  # prime: consecutive chunks start at different offsets of the base table
+
+
+def past_the_cap_rows():
+    """(R, n): the grid's cap in workgroups on this device and a row count just past it --
+    workgroups 0 and 1 take a second chunk, the last chunk is partial, n is a multiple of 8."""
+    R = WG_PER_CU * torch.cuda.get_device_properties(0).multi_processor_count
+    n = R * CHUNK + CHUNK + 776
+    assert n < 2 ** 30, f'{R} resident workgroups put n = {n} past the 2^30 rows a table takes'
+    assert n > R * CHUNK and (n + CHUNK - 1) // CHUNK == R + 2 and n % 8 == 0
+    return R, n
+
+
+@pytest.mark.parametrize('G,V,f32', [(40, 3, False), (3000, 3, False), (3000, 1, True)],
+                         ids=['identity-V3-f64', 'hashed-V3-f64', 'hashed-V1-f32'])
+def test_more_chunks_than_resident_workgroups(sa, G, V, f32):
+    """A workgroup that takes a second chunk (c += gridDim.x) after the flush that ends its
+    first.  Row i holds row i % PERIOD of the shared value table, so the exact limb sums are
+    counts[G, PERIOD] @ limbs[PERIOD, 3V] in int64: counts < 2^12 and |limbs| < 2^32, no overflow.
+    A skipped chunk cannot cancel against a doubled one: their offsets into the table differ."""
+    R, n = past_the_cap_rows()
+    v, limbs = values(f32)
+    base, L = v[:V, :PERIOD], limbs[:V, :PERIOD].transpose(1, 0, 2).reshape(PERIOD, 3 * V)
+    assert np.isnan(base).any()  # NaN under a valid key: nothing to its column, the row counts
+    rng = np.random.default_rng([G, V, int(f32), 11])
+    keys = rng.integers(0, G, n).astype(np.int32)
+    skip = np.concatenate([rng.integers(1, n, 200), rng.integers(R * CHUNK, n, 150)])
+    keys[skip] = -1  # rows that add nothing and raise no error bit
+    dv = torch.from_numpy(np.stack([np.resize(base[c], n) for c in range(V)])).cuda()
+    late = torch.from_numpy(skip[skip >= R * CHUNK]).cuda()
+    assert len(late) >= 150
+    dv[:, late] = float('nan')  # ... whatever their values are
+    dk = torch.from_numpy(keys).cuda()
+
+    live = np.flatnonzero(keys >= 0)
+    assert keys[0] >= 0 and len(live) == n - len(np.unique(skip))
+    counts = np.bincount(keys[live].astype(np.int64) * PERIOD + live % PERIOD, minlength=G * PERIOD)
+    counts = counts.reshape(G, PERIOD).astype(np.int64)
+    assert counts.max() < 2 ** 12 and np.abs(L).max() < 2 ** 32
+    want_l, want_c = (counts @ L).reshape(G, V, 3), counts.sum(1)
+
+    acc = sa.group_sums(dk, list(dv), G, scale_exp=EXPS[:V])
+    assert int(acc.err.item()) == 0 and acc.rows == n
+    assert torch.equal(acc.limbs.cpu(), torch.from_numpy(want_l))
+    assert torch.equal(acc.count.cpu(), torch.from_numpy(want_c))
+    check_finalize(acc, EXPS[:V])
+    # the same columns from row 1: off 16-byte alignment, the scalar loads; row 0 (a live row
+    # holding base row 0) leaves the sums
+    acc = sa.group_sums(dk[1:], [c[1:] for c in dv], G, scale_exp=EXPS[:V])
+    want_l[keys[0]] -= L[0].reshape(V, 3)
+    want_c[keys[0]] -= 1
+    assert int(acc.err.item()) == 0 and acc.rows == n - 1
+    assert torch.equal(acc.limbs.cpu(), torch.from_numpy(want_l))
+    assert torch.equal(acc.count.cpu(), torch.from_numpy(want_c))
 
 
 # ----------------------------------------------------------------------------- exactness

@@ -171,7 +171,7 @@ def test_native_constants_match_the_header():
     with open(os.path.join(ROOT, 'include', 'socceraction_amd.h')) as f:
         src = f.read()
     for name in ('SA_METRIC_BRIER_EXP', 'SA_METRIC_LOGLOSS_EXP', 'SA_METRIC_CHUNK_ROWS', 'SA_METRIC_ERR_NAN',
-                 'SA_METRIC_ERR_RANGE', 'SA_METRIC_ERR_LABEL', 'SA_AUC_LDS_SAMPLE'):
+                 'SA_METRIC_ERR_RANGE', 'SA_METRIC_ERR_LABEL', 'SA_AUC_LDS_SAMPLE', 'SA_METRIC_WG_PER_CU'):
         line = [ln for ln in src.splitlines() if ln.startswith(f'#define {name} ')]
         assert len(line) == 1, name
         assert int(line[0].split()[2]) == getattr(_native, name), name

@@ -226,7 +226,7 @@ def test_native_constants_match_the_header():
     with open(os.path.join(ROOT, 'include', 'socceraction_amd.h')) as f:
         src = f.read()
     for name in ('SA_GROUP_MAX_COLS', 'SA_GROUP_LDS_SLOTS', 'SA_GROUP_CHUNK_ROWS', 'SA_GROUP_HASH_MUL',
-                 'SA_GROUP_ERR_KEY', 'SA_GROUP_ERR_NONFINITE', 'SA_GROUP_ERR_RANGE'):
+                 'SA_GROUP_ERR_KEY', 'SA_GROUP_ERR_NONFINITE', 'SA_GROUP_ERR_RANGE', 'SA_GROUP_WG_PER_CU'):
         line = [ln for ln in src.splitlines() if ln.startswith(f'#define {name} ')]
         assert len(line) == 1, name
         assert int(line[0].split()[2].rstrip('u')) == getattr(_native, name), name
