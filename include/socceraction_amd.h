@@ -559,9 +559,20 @@ typedef struct sa_atomic_frame {
   uint8_t* bodypart_id;
 } sa_atomic_frame;
 
+/* SA_ATOMIC_BLOCK_ROWS bounds the input rows one workgroup of the count / emit kernels below
+ * (and of sa_dribble_count / sa_dribble_emit) expands: block b holds rows
+ * [b * SA_ATOMIC_BLOCK_ROWS, (b + 1) * SA_ATOMIC_BLOCK_ROWS) and stages at most 5 (dribbles: 2)
+ * output rows per input row in LDS.
+ * SA_ATOMIC_SCAN_TILE bounds the block totals the single-workgroup prefix scan between the two
+ * passes holds at once: with more blocks it walks them tile by tile and carries the running
+ * sum, so an input of more than SA_ATOMIC_BLOCK_ROWS * SA_ATOMIC_SCAN_TILE rows needs a
+ * second tile. */
+#define SA_ATOMIC_BLOCK_ROWS 256
+#define SA_ATOMIC_SCAN_TILE 16384
+
 /* Device scratch the two calls below share (bytes, 16-byte aligned). */
 int64_t sa_atomic_scratch_bytes(int64_t n);
-/* Pass 1: the output row count of every 1024-row block and their exclusive prefix;
+/* Pass 1: the output row count of every SA_ATOMIC_BLOCK_ROWS-row block and their exclusive prefix;
  * *n_out [host] receives the total.  Synchronises the stream. */
 int sa_atomic_count(const sa_spadl_frame* in, void* scratch, int64_t* n_out, void* stream);
 /* Pass 2: writes the n_out output rows (scratch from sa_atomic_count, same input). */

@@ -31,6 +31,8 @@ SA_XT_SOLVE_EXACT = 1  # sa_xt_solve_ex / sa_xt_solve_compact: the reference's s
 XT_SOLVE_PATHS = ('sequential', 'reordered', 'inside-bound', 'unavailable', 'timeout')
 SA_BOOL_TILE_QUANTUM = 1024
 SA_NUM_TILE_QUANTUM = 128
+SA_ATOMIC_BLOCK_ROWS = 256  # input rows per workgroup of the convert / dribble count and emit kernels
+SA_ATOMIC_SCAN_TILE = 16384  # block totals per trip of the scan between them
 SA_GROUP_MAX_COLS = 8
 SA_GROUP_LDS_SLOTS = 256  # slots of the grouped sums' LDS table
 SA_GROUP_CHUNK_ROWS = 8192

@@ -29,10 +29,12 @@
 
 namespace sa {
 
-constexpr int AC_THREADS = 256;
+constexpr int AC_BLOCK_ROWS = SA_ATOMIC_BLOCK_ROWS;  // sorted rows per block
 constexpr int AC_PER_THREAD = 1;
-constexpr int AC_BLOCK_ROWS = AC_THREADS * AC_PER_THREAD;  // 256 sorted rows per block
-constexpr int AC_MAX_OUT = AC_BLOCK_ROWS * 5;              // worst-case output rows per block
+constexpr int AC_THREADS = AC_BLOCK_ROWS / AC_PER_THREAD;
+constexpr int AC_MAX_OUT = AC_BLOCK_ROWS * 5;  // worst-case output rows per block
+static_assert(AC_THREADS * AC_PER_THREAD == SA_ATOMIC_BLOCK_ROWS && AC_THREADS % 64 == 0,
+              "a block is whole waves, one row per thread");
 
 // atomic/spadl/config.py:25-36 ids; `actiontypes.index('interception')` is the FIRST
 // position, 10 (base.py:96-99)
@@ -209,7 +211,7 @@ __device__ __forceinline__ Elem elem_of(const Group& G, int kind) {
   return e;
 }
 
-// exclusive block scan of one int per thread (256 threads = 4 waves)
+// exclusive block scan of one int per thread (AC_THREADS threads = 4 waves)
 __device__ __forceinline__ int64_t block_excl_scan(int64_t v, int64_t* wsum, int64_t& total) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   int64_t incl = v;
@@ -242,9 +244,10 @@ __global__ __launch_bounds__(AC_THREADS) void atomic_count_kernel(sa_spadl_frame
 
 // exclusive prefix of the block totals, in place; bsum[nb] = grand total (one workgroup of
 // 1024 threads).  Tiles of SC_THREADS * SC_K entries are staged through LDS with coalesced
-// loads (block totals are <= 5 * 256, so int32 holds them), each thread scans SC_K
+// loads (block totals are <= AC_MAX_OUT, so int32 holds them), each thread scans SC_K
 // consecutive entries serially, and ONE block scan per tile combines the threads.
-constexpr int SC_THREADS = 1024, SC_K = 16, SC_TILE = SC_THREADS * SC_K;
+constexpr int SC_THREADS = 1024, SC_K = 16, SC_TILE = SA_ATOMIC_SCAN_TILE;
+static_assert(SC_THREADS * SC_K == SA_ATOMIC_SCAN_TILE, "a scan tile is SC_K entries per thread");
 
 __global__ __launch_bounds__(SC_THREADS) void atomic_scan_kernel(int64_t* __restrict__ bsum, int64_t nb) {
   __shared__ int32_t tile[SC_TILE];  // 64 KiB

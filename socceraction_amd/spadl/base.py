@@ -79,9 +79,10 @@ def add_dribbles_device(frame, action_id: np.ndarray) -> SpadlRows:
     m = int(n_out.value)
     nd = m - n
     dest = None
-    if nd > 0 and n_bad.value != 0:
+    if n > 0 and n_bad.value != 0:
         # general placement: the stable lexsort of the concatenated keys (the reference's
-        # sort_values over its concat, spadl/base.py:91)
+        # sort_values over its concat, spadl/base.py:91) -- also without a single dribble: the
+        # reference sorts the rows it was given either way
         g = frame.cols['game'][:n].cpu().numpy()
         per = frame.cols['period_id'][:n].cpu().numpy()
         j = np.flatnonzero(flags[:n].cpu().numpy())

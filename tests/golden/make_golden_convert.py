@@ -15,7 +15,12 @@ Imports ``/root/reference`` with the same shims as ``make_golden.py`` (pandera s
   corners / goalkicks, goals, owngoal results on non-shot actions, yellow / red cards, and a
   pair of consecutive games whose boundary actions qualify for a cross-game dribble;
 * unsorted frames (games in descending game_id order; rows swapped inside a game), where the
-  first pass reads input-order neighbours before the reference's sort.
+  first pass reads input-order neighbours before the reference's sort;
+* ``enum``: the reduced enumeration of tests/convert_cases.py (``enum_frame`` on GOLDEN_TYPES x
+  GOLDEN_SUCCESSORS), which holds every group shape -- a pass with a card among them, which the
+  synthetic frames never produce.
+
+Case names on the command line (``... make_golden_convert.py enum``) write only those files.
 
 Inputs and outputs are stored as plain arrays (original_event_id as a unicode array plus a
 missing-value mask: no pickles).
@@ -46,6 +51,7 @@ IN_COLS = ['game_id', 'original_event_id', 'action_id', 'period_id', 'time_secon
            'bodypart_id']
 OUT_COLS = ['game_id', 'original_event_id', 'action_id', 'period_id', 'time_seconds', 'team_id',
             'player_id', 'x', 'y', 'dx', 'dy', 'type_id', 'bodypart_id']
+ONLY = set(sys.argv[1:]) if __name__ == '__main__' else set()  # case names: write only these
 
 
 def _check(df: pd.DataFrame) -> None:
@@ -70,6 +76,8 @@ def _store(out: dict, prefix: str, df: pd.DataFrame, cols) -> None:
 
 
 def case(name: str, df: pd.DataFrame) -> None:
+    if ONLY and name not in ONLY:
+        return
     df = df[IN_COLS].reset_index(drop=True)
     _check(df)
     res = convert_to_atomic(df.copy())
@@ -135,6 +143,14 @@ def cross_game_pair() -> pd.DataFrame:
     return pd.DataFrame(rows)
 
 
+def enum_case() -> pd.DataFrame:
+    """The reduced enumeration of tests/convert_cases.py (type x result x successor type x team
+    x distance x period x game as two-row runs): every group shape, cards on passes included."""
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import convert_cases as cc
+    return pd.DataFrame(cc.enum_frame(cc.GOLDEN_TYPES, cc.GOLDEN_SUCCESSORS))
+
+
 def main() -> None:
     rng = np.random.default_rng(2024)
     sp = pd.read_json(os.path.join(REF, 'tests/datasets/spadl/spadl.json'), orient='records')
@@ -152,6 +168,7 @@ def main() -> None:
     for j in rng.choice(len(sw) - 1, 12, replace=False):
         idx[j], idx[j + 1] = idx[j + 1], idx[j]
     case('unsorted_rows', sw.iloc[idx])
+    case('enum', enum_case())
 
 
 if __name__ == '__main__':

@@ -14,7 +14,13 @@ Imports ``/root/reference`` with the shims of ``make_golden.py`` and calls
   boundary sorts into the next game) with extra columns: ``timestamp`` (strings, copied from
   the successor), an int64 and a bool column (missing on dribble rows);
 * the two-game cross-boundary pair of ``make_golden_convert.py``;
-* unsorted frames (games in descending game_id order; swapped rows inside a game).
+* unsorted frames (games in descending game_id order; swapped rows inside a game);
+* ``enum``: the reduced enumeration of tests/convert_cases.py (per-game action ids, so the
+  dribbles into a next game sort behind that game's first row);
+* ``unsorted_plain``: rows in descending key order without one qualifying pair (sorted all the
+  same).
+
+Case names on the command line (``... make_golden_dribbles.py enum``) write only those files.
 
 Inputs and outputs are stored as plain arrays (object columns as unicode + missing mask).
 """
@@ -34,11 +40,12 @@ sys.path.insert(0, os.path.join(HERE, '_shims'))
 sys.path.insert(0, REF)
 sys.path.insert(0, REPO)
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.join(REPO, 'tests'))
 np.NaN = np.nan  # noqa: N816
 
 from socceraction.spadl.base import _add_dribbles  # noqa: E402
 
-from make_golden_convert import IN_COLS, _check, cross_game_pair, synthetic_frame  # noqa: E402
+from make_golden_convert import IN_COLS, _check, cross_game_pair, enum_case, synthetic_frame  # noqa: E402
 
 
 def _store(out: dict, prefix: str, df: pd.DataFrame) -> None:
@@ -56,7 +63,12 @@ def _store(out: dict, prefix: str, df: pd.DataFrame) -> None:
             out[prefix + c] = v.to_numpy()
 
 
+ONLY = set(sys.argv[1:]) if __name__ == '__main__' else set()  # case names: write only these
+
+
 def case(name: str, df: pd.DataFrame, extra=()) -> None:
+    if ONLY and name not in ONLY:
+        return
     df = df[IN_COLS + list(extra)].reset_index(drop=True)
     _check(df)
     res = _add_dribbles(df.copy())
@@ -75,6 +87,13 @@ def with_extras(df: pd.DataFrame, rng: np.random.Generator) -> pd.DataFrame:
     df['xtra_int'] = rng.integers(0, 1000, len(df)).astype(np.int64)
     df['xtra_bool'] = rng.random(len(df)) < 0.5
     return df
+
+
+def unsorted_plain() -> pd.DataFrame:
+    """41 rows in descending key order of which no neighbours qualify (alternating teams): the
+    reference inserts nothing and still sorts what it was given."""
+    import convert_cases as cc
+    return pd.DataFrame(cc.sparse_frame(41)).iloc[::-1]
 
 
 def main() -> None:
@@ -97,6 +116,8 @@ def main() -> None:
     for j in rng.choice(len(sw) - 1, 12, replace=False):
         idx[j], idx[j + 1] = idx[j + 1], idx[j]
     case('unsorted_rows', with_extras(sw.iloc[idx], rng), extra)
+    case('enum', enum_case())
+    case('unsorted_plain', unsorted_plain())
 
 
 if __name__ == '__main__':

@@ -9,11 +9,19 @@ import numpy as np
 import pandas as pd
 import pytest
 
+import convert_cases as cc
 from golden_io import assert_frame_same, cases, dribbles_frame, load
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip('torch')
+
+from socceraction_amd._native import SA_ATOMIC_BLOCK_ROWS as B, SA_ATOMIC_SCAN_TILE as T  # noqa: E402
+
+# the frame's last row on either side of the first and the second block edge
+BLOCK_EDGES = (B - 1, B, B + 1, 2 * B - 1, 2 * B, 2 * B + 1)
+# (rows, blocks): one block into the scan's second tile, one into its third
+SCAN_SIZES = ((T * B + 1, T + 1), (2 * T * B + 77, 2 * T + 1))
 
 
 @pytest.fixture(scope='module')
@@ -71,6 +79,84 @@ def test_add_dribbles_general_placement(sb):
     glob = df.copy()
     glob['action_id'] = np.arange(len(glob), dtype=np.int64)
     _vs_oracle(sb._add_dribbles(glob), glob, 'global-ids')
+
+
+def _vs_oracle_exact(got: pd.DataFrame, df: pd.DataFrame, name: str):
+    """_vs_oracle, and every float column bit for bit."""
+    from oracle import atomic_convert_oracle as co
+    _vs_oracle(got, df, name)
+    ref = co.add_dribbles({c: df[c].to_numpy() for c in co.COLS})
+    for c in ('time_seconds', 'start_x', 'start_y', 'end_x', 'end_y'):
+        np.testing.assert_array_equal(got[c].to_numpy().view(np.int64),
+                                      np.asarray(ref[c], np.float64).view(np.int64),
+                                      err_msg=f'{name} {c}')
+
+
+@pytest.fixture(scope='module')
+def enum():
+    return cc.enum_frame()
+
+
+@pytest.mark.parametrize('layout', ['per_game_ids', 'global_ids', 'shuffled', 'shuffled_runs'])
+def test_add_dribbles_enumeration_vs_oracle(sb, enum, layout):
+    """Every combination of (type, result, successor type, team, distance, period, game)
+    (tests/convert_cases.py) == the restatement: with action ids restarting in every game (a
+    dribble into the next game sorts behind that game's first row: lexsort placement), with
+    global ids (the fast layout), with the rows shuffled (hardly two neighbours of one team left: the
+    rows sorted back) and with the runs shuffled (every dribble, placed by the
+    lexsort)."""
+    f = enum
+    if layout == 'global_ids':
+        f = dict(f, action_id=np.arange(len(f['type_id']), dtype=np.int64))
+    elif layout == 'shuffled':
+        f = cc.shuffled(f)
+    elif layout == 'shuffled_runs':
+        f = cc.shuffled_runs(f)
+    df = pd.DataFrame(f)
+    got = sb._add_dribbles(df)
+    if layout != 'shuffled':
+        assert len(got) > len(df) + 1000
+    _vs_oracle_exact(got, df, layout)
+
+
+@pytest.mark.parametrize('n', BLOCK_EDGES)
+@pytest.mark.parametrize('kind', ['dense', 'sparse'])
+def test_add_dribbles_full_and_empty_blocks(sb, kind, n):
+    """Blocks in which every row gets a dribble (2n - 1 rows out) or none does, with the frame's
+    last row (no successor) on either side of a block edge."""
+    df = pd.DataFrame(cc.dense_frame(n) if kind == 'dense' else cc.sparse_frame(n))
+    got = sb._add_dribbles(df)
+    assert len(got) == (2 * n - 1 if kind == 'dense' else n)
+    _vs_oracle_exact(got, df, f'{kind}-{n}')
+
+
+SPADL_DEVICE_COLS = {'game_id': 'game', 'original_event_id': 'event', 'period_id': 'period_id',
+                     'time_seconds': 'time_seconds', 'team_id': 'team', 'player_id': 'player',
+                     'start_x': 'start_x', 'start_y': 'start_y', 'end_x': 'end_x', 'end_y': 'end_y',
+                     'type_id': 'type_id', 'result_id': 'result_id', 'bodypart_id': 'bodypart_id',
+                     'src': 'src'}
+
+
+@pytest.mark.parametrize('n, n_blocks', SCAN_SIZES)
+def test_add_dribbles_scan_tiles(sb, n, n_blocks):
+    """The scan of the block totals one block into its second tile and into its third: a 30-game
+    base repeated to n rows with global action ids (the fast layout), every output column, ``src``
+    and the row count against the oracle's output for the base, compared on the device."""
+    from oracle import atomic_convert_oracle as co
+    from socceraction_amd import _native
+    from socceraction_amd.atomic.spadl import base as cb
+    assert _native.lib().sa_atomic_scratch_bytes(n) == (n_blocks + 2) * 8  # the library's n_blocks
+    t = cc.tiled(cc.tile_base(), n, co.add_dribbles)
+    assert t.part is not None
+    for ref in (t.full, t.part):
+        ref['src'] = cc.dribble_src(ref)
+    frame = cb.SpadlFrame.from_columns(t.cols)
+    assert frame.n == n and 'order' not in frame.cols
+    # from_columns has no event ids: give every row its own (the code is the id)
+    frame.cols['event'].copy_(torch.arange(n, dtype=torch.int32, device=frame.buffer.device))
+    out = sb.add_dribbles_device(frame, t.cols['action_id'])
+    assert out.n_dribbles == out.n - n > 0
+    cc.assert_tiled_on_device(t, out.cols, out.n, frame.uniques, SPADL_DEVICE_COLS)
 
 
 def test_add_dribbles_thresholds_are_module_globals(sb):
