@@ -394,7 +394,8 @@ int sa_xt_count_from_buckets_ex(int32_t nsets, const uint16_t* const* buckets,
  *                  C > SA_XT_SOLVE_MAX_C (the large-grid iteration reads the counts directly)
  *   heatmaps[(max_iter+1)*C] = x after 0..n_iter iterations
  * *n_iter [host] receives the iteration count (-1: max_iter reached first).
- * Synchronises the stream. */
+ * Synchronises the stream.  Like the counts, every entry point that takes a grid needs
+ * l * w <= 46340 (int32 indexing of the C x C counts) and returns SA_EINVAL above. */
 int sa_xt_solve(const int64_t* shot, const int64_t* goal, const int64_t* move,
                 const int32_t* trans, int32_t l, int32_t w, double eps, int32_t max_iter,
                 double* mats, double* trans_t, double* heatmaps, int32_t* n_iter, void* stream);

@@ -31,6 +31,57 @@ struct Scratch {
 };
 int scratch_acquire(size_t bytes, hipStream_t st, Scratch* out);
 void scratch_release(const Scratch& s, hipStream_t st);
+// A slot held for a scope, released against the stream it was acquired on.  The release records
+// an event there, so the guard outlives the last enqueue that uses the memory.
+struct ScratchGuard {
+  Scratch s;
+  hipStream_t st = nullptr;
+  ScratchGuard() = default;
+  ScratchGuard(const ScratchGuard&) = delete;
+  ScratchGuard& operator=(const ScratchGuard&) = delete;
+  ~ScratchGuard() { scratch_release(s, st); }
+  int acquire(size_t bytes, hipStream_t stream) { return scratch_acquire(bytes, st = stream, &s); }
+  template <class T>
+  T* at(size_t byte_offset = 0) const { return reinterpret_cast<T*>(static_cast<char*>(s.ptr) + byte_offset); }
+};
+
+// Argument checks shared by the xT entry points.  A grid: l, w >= 1 and l * w (in 64 bits) at
+// most max_cells; 46340: the C x C transition counts are indexed in int32.
+inline int check_grid(int l, int w, int64_t max_cells = 46340) {
+  if (l >= 1 && w >= 1 && (int64_t)l * w <= max_cells) return SA_OK;
+  return fail(SA_EINVAL, "bad l or w (l, w >= 1 and l * w <= %lld)", (long long)max_cells);
+}
+inline int check_xy_columns(const sa_frame& F) {  // what the xT passes read of frames[0]
+  return F.type_id && F.result_id && F.c0 && F.c1 && F.c2 && F.c3 ? SA_OK : fail(SA_EINVAL, "null input column");
+}
+// The kernels' vector loads: the coordinate columns (and `out`) 16-byte aligned, the ids even.
+inline bool coords_vec_ok(const sa_frame& F, const void* out = nullptr) {
+  return aligned16(F.c0) && aligned16(F.c1) && aligned16(F.c2) && aligned16(F.c3) && aligned16(out) &&
+         ((uintptr_t)F.type_id & 1u) == 0 && ((uintptr_t)F.result_id & 1u) == 0;
+}
+
+// The host loop of a solve that launches once per iteration: enqueue(it) launches iteration it,
+// which leaves dflags[it] != 0 when some cell moved by more than eps.  The flags come back every
+// 8 iterations (one copy, one synchronise); *n_iter = the first iteration, counted from 1, whose
+// flag is 0, or -1 when max_iter comes first.
+template <class Enqueue>
+int iterate_to_convergence(int max_iter, const int32_t* dflags, hipStream_t st, int* n_iter, Enqueue enqueue) {
+  int32_t hflags[8];
+  *n_iter = -1;
+  for (int it0 = 0; it0 < max_iter; it0 += 8) {
+    const int nb = max_iter - it0 < 8 ? max_iter - it0 : 8;
+    for (int k = 0; k < nb; ++k)
+      if (int rc = enqueue(it0 + k)) return rc;
+    if (int rc = check_hip(hipMemcpyAsync(hflags, dflags + it0, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st),
+                           "copy flags"))
+      return rc;
+    if (int rc = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize")) return rc;
+    for (int k = 0; k < nb && *n_iter < 0; ++k)
+      if (hflags[k] == 0) *n_iter = it0 + k + 1;
+    if (*n_iter > 0) break;
+  }
+  return SA_OK;
+}
 
 // Large-grid xT (sa_xt_large.hip).  xt_band_ok: the band-owned count holds a grid of C cells;
 // xt_count_bands: that count of one batch, added into the caller's counts.  xt_compact_*: the

@@ -1029,12 +1029,10 @@ extern "C" int sa_xt_count_codes(const sa_actions* a, int32_t l, int32_t w, int6
                                  int64_t* goal, int64_t* move, int32_t* trans, int32_t* err_flags,
                                  uint32_t* codes, int32_t flags, void* stream) {
   if (!a || a->n < 0) return fail(SA_EINVAL, "bad sa_actions");
-  if (l < 1 || w < 1) return fail(SA_EINVAL, "l and w must be >= 1");
-  if ((int64_t)l * w > 46340) return fail(SA_EINVAL, "grid too large (C*C must fit int32 indexing)");
+  if (int rc = check_grid(l, w)) return rc;
   if (!shot || !goal || !move || !trans || !err_flags) return fail(SA_EINVAL, "null output");
-  const sa_frame& F = a->frames[0];
-  if (a->n > 0 && (!F.type_id || !F.result_id || !F.c0 || !F.c1 || !F.c2 || !F.c3))
-    return fail(SA_EINVAL, "null input column");
+  if (a->n > 0)
+    if (int rc = check_xy_columns(a->frames[0])) return rc;
   if (codes && !aligned16(codes)) return fail(SA_EINVAL, "codes must be 16-byte aligned");
   if (codes && (int64_t)l * w > 65535) return fail(SA_EINVAL, "rate codes need l * w <= 65535");
   if (a->n == 0) return SA_OK;
@@ -1047,9 +1045,8 @@ extern "C" int sa_xt_cells(const sa_actions* a, int32_t l, int32_t w, uint32_t* 
   if (l < 1 || w < 1 || (int64_t)l * w > SA_XT_CELLS_MAX_C)
     return fail(SA_EINVAL, "cell codes need 1 <= l * w <= %d", SA_XT_CELLS_MAX_C);
   if (a->n == 0) return SA_OK;
-  const sa_frame& F = a->frames[0];
-  if (!F.type_id || !F.result_id || !F.c0 || !F.c1 || !F.c2 || !F.c3 || !cells)
-    return fail(SA_EINVAL, "null input column or output");
+  if (int rc = check_xy_columns(a->frames[0])) return rc;
+  if (!cells) return fail(SA_EINVAL, "null output");
   if (!aligned16(cells)) return fail(SA_EINVAL, "cells must be 16-byte aligned");
   const int64_t threads = (a->n + 3) / 4;
   hipLaunchKernelGGL(xt_cells_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
@@ -1071,39 +1068,51 @@ extern "C" int sa_xt_count_cells(const uint32_t* cells, int64_t n, int32_t l, in
                       (hipStream_t)stream);
 }
 
+static const unsigned long long* u64(const int64_t* p) { return reinterpret_cast<const unsigned long long*>(p); }
+
+// The probabilities of the counts: mats[0..3) = scoring | shot | move, gs, pmove, and with
+// trans_t the dense transposed transition matrix (the small-grid solve reads it).
+static int normalise(const int64_t* shot, const int64_t* goal, const int64_t* move, const int32_t* trans, int C,
+                     double* mats, double* gs, double* pmove, double* trans_t, hipStream_t st) {
+  hipLaunchKernelGGL(xt_prob_kernel, dim3((C + 255) / 256), dim3(256), 0, st, u64(shot), u64(goal), u64(move), C, mats,
+                     gs, pmove);
+  if (trans_t) {
+    const dim3 tgrid((C + 31) / 32, (C + 31) / 32);
+    hipLaunchKernelGGL(xt_transpose_kernel, tgrid, dim3(256), 0, st, trans, u64(move), C, trans_t);
+  }
+  return check_launch("xt normalise");
+}
+
+// The whole value iteration of a grid of <= XT_SOLVE_MAX_C cells in one launch: the matrix in
+// registers up to XR_MAX_C cells, one workgroup streaming it above.  *n_iter_dev: the count or -1.
+static int launch_small_solve(const double* trans_t, const double* gs, const double* pmove, int C, double eps,
+                              int max_iter, double* heat, double* xt_out, int32_t* n_iter_dev, hipStream_t st) {
+  if (C <= XR_MAX_C) {
+    hipLaunchKernelGGL(xt_solve_reg_kernel<SA_XR_PARTS>, dim3(1), dim3(SA_XR_PARTS * XR_MAX_C), 0, st, trans_t, gs,
+                       pmove, C, eps, max_iter, heat, xt_out, n_iter_dev);
+    return check_launch("xt_solve_reg_kernel");
+  }
+  hipLaunchKernelGGL(xt_solve_small_kernel, dim3(1), dim3(((C + 63) / 64) * 64), 0, st, trans_t, gs, pmove, C, eps,
+                     max_iter, heat, xt_out, n_iter_dev);
+  return check_launch("xt_solve_small_kernel");
+}
+
 extern "C" int sa_xt_solve_async(const int64_t* shot, const int64_t* goal, const int64_t* move,
                                  const int32_t* trans, int32_t l, int32_t w, double eps, int32_t max_iter,
                                  double* mats, double* trans_t, double* heatmaps, int32_t* n_iter_dev,
                                  void* stream) {
-  if (l < 1 || w < 1 || max_iter < 0) return fail(SA_EINVAL, "bad l, w or max_iter");
+  if (int rc = check_grid(l, w)) return rc;
+  if (max_iter < 0) return fail(SA_EINVAL, "bad max_iter");
   const int C = l * w;
   if (C > XT_SOLVE_MAX_C) return fail(SA_EINVAL, "the asynchronous solve takes grids of <= %d cells", XT_SOLVE_MAX_C);
   if (!shot || !goal || !move || !trans || !mats || !trans_t || !heatmaps || !n_iter_dev)
     return fail(SA_EINVAL, "null pointer");
   hipStream_t st = (hipStream_t)stream;
-  auto* us = reinterpret_cast<const unsigned long long*>(shot);
-  auto* ug = reinterpret_cast<const unsigned long long*>(goal);
-  auto* um = reinterpret_cast<const unsigned long long*>(move);
-  Scratch sc;  // gs[C] | pmove[C]
-  int rc = scratch_acquire(sizeof(double) * 2 * C, st, &sc);
-  if (rc) return rc;
-  double* gs = static_cast<double*>(sc.ptr);
-  double* pm = gs + C;
-  hipLaunchKernelGGL(xt_prob_kernel, dim3((C + 255) / 256), dim3(256), 0, st, us, ug, um, C, mats, gs, pm);
-  const dim3 tgrid((C + 31) / 32, (C + 31) / 32);
-  hipLaunchKernelGGL(xt_transpose_kernel, tgrid, dim3(256), 0, st, trans, um, C, trans_t);
-  rc = check_launch("xt normalise");
-  if (!rc && C <= XR_MAX_C) {
-    hipLaunchKernelGGL(xt_solve_reg_kernel<SA_XR_PARTS>, dim3(1), dim3(SA_XR_PARTS * XR_MAX_C), 0, st, trans_t, gs,
-                       pm, C, eps, max_iter, heatmaps, mats + 3 * C, n_iter_dev);
-    rc = check_launch("xt_solve_reg_kernel");
-  } else if (!rc) {
-    hipLaunchKernelGGL(xt_solve_small_kernel, dim3(1), dim3(((C + 63) / 64) * 64), 0, st, trans_t, gs, pm, C, eps,
-                       max_iter, heatmaps, mats + 3 * C, n_iter_dev);
-    rc = check_launch("xt_solve_small_kernel");
-  }
-  scratch_release(sc, st);
-  return rc;
+  ScratchGuard sc;  // gs[C] | pmove[C]
+  if (int rc = sc.acquire(sizeof(double) * 2 * C, st)) return rc;
+  double* gs = sc.at<double>();
+  if (int rc = normalise(shot, goal, move, trans, C, mats, gs, gs + C, trans_t, st)) return rc;
+  return launch_small_solve(trans_t, gs, gs + C, C, eps, max_iter, heatmaps, mats + 3 * C, n_iter_dev, st);
 }
 
 extern "C" int sa_xt_solve(const int64_t* shot, const int64_t* goal, const int64_t* move,
@@ -1114,24 +1123,67 @@ extern "C" int sa_xt_solve(const int64_t* shot, const int64_t* goal, const int64
                         nullptr, nullptr, stream);
 }
 
-static int solve_ex(const int64_t* shot, const int64_t* goal, const int64_t* move, const int32_t* trans, int32_t l,
-                    int32_t w, double eps, int32_t max_iter, int32_t flags, double* mats, double* trans_t,
-                    double* heatmaps, int32_t* n_iter, int32_t* path, const uint32_t* ell_in,
-                    const int32_t* row_len_in, void* stream, SolveHook* hook);
-
-extern "C" int sa_xt_solve_ex(const int64_t* shot, const int64_t* goal, const int64_t* move,
-                              const int32_t* trans, int32_t l, int32_t w, double eps, int32_t max_iter,
-                              int32_t flags, double* mats, double* trans_t, double* heatmaps, int32_t* n_iter,
-                              int32_t* path, const uint32_t* ell_in, const int32_t* row_len_in, void* stream) {
-  return solve_ex(shot, goal, move, trans, l, w, eps, max_iter, flags, mats, trans_t, heatmaps, n_iter, path, ell_in,
-                  row_len_in, stream, nullptr);
+// The three solves of sa_xt_solve_ex.  Each leaves the iterates in `heat`, the surface in `xt`
+// and *n_iter = the iteration count or -1, and returns with the stream synchronised.
+static int copy_surface(const double* heat, int n_iter, int max_iter, int C, double* xt, hipStream_t st) {
+  const int last = n_iter < 0 ? max_iter : n_iter;
+  if (int rc = check_hip(hipMemcpyAsync(xt, heat + (int64_t)last * C, sizeof(double) * C, hipMemcpyDeviceToDevice, st),
+                         "copy xT"))
+    return rc;
+  return check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
 }
 
+// C <= XT_SOLVE_MAX_C: one launch, which writes the surface itself; n_dev is device scratch.
+static int solve_small(const double* trans_t, const double* gs, const double* pmove, int C, double eps, int max_iter,
+                       double* heat, double* xt, int32_t* n_dev, int32_t* n_iter, hipStream_t st) {
+  if (int rc = launch_small_solve(trans_t, gs, pmove, C, eps, max_iter, heat, xt, n_dev, st)) return rc;
+  if (int rc = check_hip(hipMemcpyAsync(n_iter, n_dev, sizeof(int32_t), hipMemcpyDeviceToHost, st), "copy n_iter"))
+    return rc;
+  return check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+}
+
+// Up to the compact form's limit (sa_xt_large.hip): over the compact rows, [ell | row_len]
+// prebuilt by the count (sa_xt_count_from_buckets_ex) or built here; reordered under the error
+// bound or in the reference's order (*path).  heat row 0 is zero already.
+static int solve_compact(const int32_t* trans, const int64_t* move, const double* gs, const double* pmove, int C,
+                         double eps, int max_iter, int flags, const uint32_t* ell, const int32_t* row_len,
+                         double* heat, double* xt, int32_t* n_iter, int* path, SolveHook* hook, hipStream_t st) {
+  ScratchGuard ce;
+  if (!ell) {
+    const size_t eb = (xt_compact_bytes(C, C) + 255) & ~(size_t)255;
+    if (int rc = ce.acquire(eb + sizeof(int32_t) * (size_t)C, st)) return rc;
+    if (int rc = xt_compact_build(trans, C, C, ce.at<uint32_t>(), ce.at<int32_t>(eb), st)) return rc;
+    ell = ce.at<uint32_t>();
+    row_len = ce.at<int32_t>(eb);
+  }
+  if (int rc = xt_compact_solve(ell, row_len, trans, move, gs, pmove, C, eps, max_iter, flags, heat, n_iter, path, st,
+                                xt, hook))
+    return rc;
+  if (*path == SA_XT_PATH_REORDERED) return SA_OK;  // the reordered solve wrote the surface itself
+  return copy_surface(heat, *n_iter, max_iter, C, xt, st);
+}
+
+// Above the compact form's limit: one xt_iter_kernel launch over the dense count rows per
+// iteration.  heat row 0 is zero already; dflags: device scratch [max_iter + 1].
+static int solve_dense(const int32_t* trans, const int64_t* move, const double* gs, const double* pmove, int C,
+                       double eps, int max_iter, double* heat, double* xt, int32_t* dflags, int32_t* n_iter,
+                       hipStream_t st) {
+  if (int rc = check_hip(hipMemsetAsync(dflags, 0, sizeof(int32_t) * (max_iter + 1), st), "memset")) return rc;
+  const int rc = iterate_to_convergence(max_iter, dflags, st, n_iter, [&](int it) {
+    double* xi = heat + (int64_t)it * C;
+    return sa_xt_iterate_rows(trans, move, gs, pmove, C, 0, C, xi, eps, xi + C, it > 0 ? dflags + it - 1 : nullptr,
+                              dflags + it, st);
+  });
+  return rc ? rc : copy_surface(heat, *n_iter, max_iter, C, xt, st);
+}
+
+// sa_xt_solve_ex, with the hook of the fused fit + rate (sa_internal.h: SolveHook).
 static int solve_ex(const int64_t* shot, const int64_t* goal, const int64_t* move, const int32_t* trans, int32_t l,
                     int32_t w, double eps, int32_t max_iter, int32_t flags, double* mats, double* trans_t,
                     double* heatmaps, int32_t* n_iter, int32_t* path, const uint32_t* ell_in,
                     const int32_t* row_len_in, void* stream, SolveHook* hook) {
-  if (l < 1 || w < 1 || max_iter < 0) return fail(SA_EINVAL, "bad l, w or max_iter");
+  if (int rc = check_grid(l, w)) return rc;
+  if (max_iter < 0) return fail(SA_EINVAL, "bad max_iter");
   const int C = l * w;
   if (!shot || !goal || !move || !trans || !mats || (!trans_t && C <= XT_SOLVE_MAX_C) || !heatmaps || !n_iter)
     return fail(SA_EINVAL, "null pointer");
@@ -1140,100 +1192,39 @@ static int solve_ex(const int64_t* shot, const int64_t* goal, const int64_t* mov
   if (ell_in && (C <= XT_SOLVE_MAX_C || !xt_compact_ok(C) || !aligned16(ell_in)))
     return fail(SA_EINVAL, "a prebuilt compact form is for %d < C <= the compact limit (16-byte aligned)",
                 XT_SOLVE_MAX_C);
-  if (path) *path = SA_XT_PATH_SEQUENTIAL;
+  int32_t iters = -1, p = SA_XT_PATH_SEQUENTIAL;
+  if (path) *path = p;
   hipStream_t st = (hipStream_t)stream;
-  auto* us = reinterpret_cast<const unsigned long long*>(shot);
-  auto* ug = reinterpret_cast<const unsigned long long*>(goal);
-  auto* um = reinterpret_cast<const unsigned long long*>(move);
-  // scratch: gs[C] | pmove[C] | n_iter | convergence flags[max_iter + 1]
-  Scratch sc;
-  int rc = scratch_acquire(sizeof(double) * 2 * C + sizeof(int32_t) * (max_iter + 2), st, &sc);
+  ScratchGuard sc;  // gs[C] | pmove[C] | n_iter | the dense solve's flags[max_iter + 1]
+  int rc = sc.acquire(sizeof(double) * 2 * C + sizeof(int32_t) * (max_iter + 2), st);
   if (rc) return rc;
-  double* gs = static_cast<double*>(sc.ptr);
+  double* gs = sc.at<double>();
   double* pm = gs + C;
   int32_t* dn = reinterpret_cast<int32_t*>(pm + C);
-  int32_t* dflags = dn + 1;
-  int32_t iters = -1;
-  hipLaunchKernelGGL(xt_prob_kernel, dim3((C + 255) / 256), dim3(256), 0, st, us, ug, um, C, mats, gs, pm);
-  if (trans_t) {  // the dense transposed matrix: read by the small-grid solve, optional above
-    const dim3 tgrid((C + 31) / 32, (C + 31) / 32);
-    hipLaunchKernelGGL(xt_transpose_kernel, tgrid, dim3(256), 0, st, trans, um, C, trans_t);
-  }
-  rc = check_launch("xt normalise");
+  double* xt = mats + 3 * C;
+  // trans_t: read by the small-grid solve, optional above
+  rc = normalise(shot, goal, move, trans, C, mats, gs, pm, trans_t, st);
   if (!rc && C <= XT_SOLVE_MAX_C) {
-    if (C <= XR_MAX_C) {
-      hipLaunchKernelGGL(xt_solve_reg_kernel<SA_XR_PARTS>, dim3(1), dim3(SA_XR_PARTS * XR_MAX_C), 0, st, trans_t, gs, pm, C, eps,
-                         max_iter, heatmaps, mats + 3 * C, dn);
-      rc = check_launch("xt_solve_reg_kernel");
-    } else {
-      hipLaunchKernelGGL(xt_solve_small_kernel, dim3(1), dim3(((C + 63) / 64) * 64), 0, st, trans_t, gs, pm, C,
-                         eps, max_iter, heatmaps, mats + 3 * C, dn);
-      rc = check_launch("xt_solve_small_kernel");
-    }
-    if (!rc) rc = check_hip(hipMemcpyAsync(&iters, dn, sizeof(int32_t), hipMemcpyDeviceToHost, st),
-                            "copy n_iter");
-    if (!rc) rc = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+    rc = solve_small(trans_t, gs, pm, C, eps, max_iter, heatmaps, xt, dn, &iters, st);
   } else if (!rc) {
-    // the compact form of the count rows, built once (sa_xt_large.hip): [ell | row_len]
-    const bool compact = xt_compact_ok(C);
     rc = check_hip(hipMemsetAsync(heatmaps, 0, sizeof(double) * C, st), "memset");
-    if (!rc && !compact)  // the dense loop's flags (the compact solve keeps its own)
-      rc = check_hip(hipMemsetAsync(dflags, 0, sizeof(int32_t) * (max_iter + 1), st), "memset");
-    Scratch ce;
-    const uint32_t* ell = ell_in;  // prebuilt by the count (sa_xt_count_from_buckets_ex), or built here
-    const int32_t* slen = row_len_in;
-    if (!rc && compact && !ell) {
-      const size_t eb = (xt_compact_bytes(C, C) + 255) & ~(size_t)255;
-      rc = scratch_acquire(eb + sizeof(int32_t) * (size_t)C, st, &ce);
-      if (!rc) {
-        uint32_t* e = static_cast<uint32_t*>(ce.ptr);
-        int32_t* sl = reinterpret_cast<int32_t*>(static_cast<char*>(ce.ptr) + eb);
-        rc = xt_compact_build(trans, C, C, e, sl, st);
-        ell = e;
-        slen = sl;
-      }
-    }
-    bool surface_done = false;  // the reordered solve wrote the surface itself
-    if (compact && !rc) {  // reordered under the error bound, or the reference's order
-      int p = SA_XT_PATH_SEQUENTIAL;
-      rc = xt_compact_solve(ell, slen, trans, move, gs, pm, C, eps, max_iter, flags, heatmaps, &iters, &p, st,
-                            mats + 3 * C, hook);
-      if (path) *path = p;
-      surface_done = p == SA_XT_PATH_REORDERED;
-    }
-    std::vector<int32_t> hflags(max_iter + 1, 0);
-    const int batch = 8;
-    for (int it0 = 0; !compact && !rc && it0 < max_iter && iters < 0; it0 += batch) {
-      const int it1 = it0 + batch < max_iter ? it0 + batch : max_iter;
-      for (int it = it0; it < it1 && !rc; ++it) {  // above the compact form's C: the dense rows
-        double* xi = heatmaps + (int64_t)it * C;
-        const int32_t* fp = it > 0 ? dflags + it - 1 : nullptr;
-        hipLaunchKernelGGL(xt_iter_kernel, dim3((C + XI_ROWS - 1) / XI_ROWS), dim3(XI_THREADS), 0, st, trans, um,
-                           gs, pm, C, 0, C, eps, xi, xi + C, fp, dflags + it);
-        rc = check_launch("xt_iter_kernel");
-      }
-      if (!rc) rc = check_hip(hipMemcpyAsync(hflags.data() + it0, dflags + it0,
-                                             sizeof(int32_t) * (it1 - it0), hipMemcpyDeviceToHost, st),
-                              "copy flags");
-      if (!rc) rc = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-      for (int it = it0; !rc && it < it1; ++it)
-        if (hflags[it] == 0) {
-          iters = it + 1;
-          break;
-        }
-    }
-    if (!rc && !surface_done) {
-      const int last = iters < 0 ? max_iter : iters;
-      rc = check_hip(hipMemcpyAsync(mats + 3 * C, heatmaps + (int64_t)last * C, sizeof(double) * C,
-                                    hipMemcpyDeviceToDevice, st),
-                     "copy xT");
-      if (!rc) rc = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-    }
-    if (compact && !ell_in) scratch_release(ce, st);
+    if (!rc && xt_compact_ok(C))
+      rc = solve_compact(trans, move, gs, pm, C, eps, max_iter, flags, ell_in, row_len_in, heatmaps, xt, &iters, &p,
+                         hook, st);
+    else if (!rc)
+      rc = solve_dense(trans, move, gs, pm, C, eps, max_iter, heatmaps, xt, dn + 1, &iters, st);
   }
-  scratch_release(sc, st);
+  if (path) *path = p;
   *n_iter = iters;
   return rc;
+}
+
+extern "C" int sa_xt_solve_ex(const int64_t* shot, const int64_t* goal, const int64_t* move,
+                              const int32_t* trans, int32_t l, int32_t w, double eps, int32_t max_iter,
+                              int32_t flags, double* mats, double* trans_t, double* heatmaps, int32_t* n_iter,
+                              int32_t* path, const uint32_t* ell_in, const int32_t* row_len_in, void* stream) {
+  return solve_ex(shot, goal, move, trans, l, w, eps, max_iter, flags, mats, trans_t, heatmaps, n_iter, path, ell_in,
+                  row_len_in, stream, nullptr);
 }
 
 extern "C" int sa_xt_interp_grid(const double* xT, const double* cx, const double* cy, int32_t l,
@@ -1251,38 +1242,55 @@ extern "C" int sa_xt_interp_grid(const double* xT, const double* cx, const doubl
 extern "C" int sa_xt_normalize(const int64_t* shot, const int64_t* goal, const int64_t* move,
                                const int32_t* trans, int32_t l, int32_t w, double* mats,
                                double* trans_t, void* stream) {
-  if (l < 1 || w < 1) return fail(SA_EINVAL, "bad l or w");
+  if (int rc = check_grid(l, w)) return rc;
   if (!shot || !goal || !move || !trans || !mats || !trans_t) return fail(SA_EINVAL, "null pointer");
   const int C = l * w;
   hipStream_t st = (hipStream_t)stream;
-  auto* us = reinterpret_cast<const unsigned long long*>(shot);
-  auto* ug = reinterpret_cast<const unsigned long long*>(goal);
-  auto* um = reinterpret_cast<const unsigned long long*>(move);
-  Scratch sc;  // gs[C] | pmove[C] (not returned by this entry point)
-  int rc = scratch_acquire(sizeof(double) * 2 * C, st, &sc);
-  if (rc) return rc;
-  double* gs = static_cast<double*>(sc.ptr);
-  hipLaunchKernelGGL(xt_prob_kernel, dim3((C + 255) / 256), dim3(256), 0, st, us, ug, um, C, mats, gs,
-                     gs + C);
-  const dim3 tgrid((C + 31) / 32, (C + 31) / 32);
-  hipLaunchKernelGGL(xt_transpose_kernel, tgrid, dim3(256), 0, st, trans, um, C, trans_t);
-  rc = check_launch("xt normalise");
-  scratch_release(sc, st);
-  return rc;
+  ScratchGuard sc;  // gs[C] | pmove[C] (not returned by this entry point)
+  if (int rc = sc.acquire(sizeof(double) * 2 * C, st)) return rc;
+  return normalise(shot, goal, move, trans, C, mats, sc.at<double>(), sc.at<double>() + C, trans_t, st);
 }
 
 extern "C" int sa_xt_rate(const sa_actions* a, const double* grid, int32_t L, int32_t W, double* out,
                           int32_t* err_flags, void* stream) {
   if (!a || a->n < 0 || !grid || !out || L < 1 || W < 1) return fail(SA_EINVAL, "bad xt_rate args");
   if (a->n == 0) return SA_OK;
-  const sa_frame& F = a->frames[0];
-  const int vec = aligned16(F.c0) && aligned16(F.c1) && aligned16(F.c2) && aligned16(F.c3) && aligned16(out) &&
-                  ((uintptr_t)F.type_id & 1u) == 0 && ((uintptr_t)F.result_id & 1u) == 0;
+  const int vec = coords_vec_ok(a->frames[0], out);
   const int64_t threads = (a->n + 1) / 2;
   hipLaunchKernelGGL(xt_rate_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, *a, grid, L, W, out, err_flags, vec);
   return check_launch("xt_rate_kernel");
 }
+
+// What the interpolated rate needs besides the surface: the node tables frac[L + W] | idx[L + W]
+// (xt_axes_kernel, in scratch held until this goes out of scope), the LDS bytes of the kernels
+// that stage surface and tables, whether this device has them, and those kernels' grid.
+struct XriTables {
+  size_t lds;
+  bool in_lds;
+  ScratchGuard sc;
+  double* frac = nullptr;
+  int32_t* idx = nullptr;
+
+  XriTables(int l, int w, int L, int W)
+      : lds(sizeof(double) * ((size_t)l * w + L + W) + sizeof(int32_t) * (size_t)(L + W)),
+        in_lds(lds <= XRI_LDS_MAX && lds <= (size_t)device_lds_max(current_device())) {}
+  int build(const double* cx, const double* cy, int l, int w, const double* xs, int L, const double* ys, int W,
+            hipStream_t st) {
+    if (int rc = sc.acquire((sizeof(double) + sizeof(int32_t)) * (size_t)(L + W), st)) return rc;
+    frac = sc.at<double>();
+    idx = reinterpret_cast<int32_t*>(frac + (L + W));
+    hipLaunchKernelGGL(xt_axes_kernel, dim3((unsigned)((L + W + 255) / 256)), dim3(256), 0, st, cx, cy, l, w, xs, L,
+                       ys, W, idx, frac);
+    return check_launch("xt_axes_kernel");
+  }
+  // workgroups of XRI_THREADS for n actions, two per lane: at most SA_XRI_BPC per CU
+  static unsigned blocks(int64_t n) {
+    const int64_t need = ((n + 1) / 2 + XRI_THREADS - 1) / XRI_THREADS;
+    const int64_t most = (int64_t)device_cus(current_device()) * SA_XRI_BPC;
+    return (unsigned)(need < most ? need : most);
+  }
+};
 
 extern "C" int sa_xt_rate_interp(const sa_actions* a, const double* xT, const double* cx, const double* cy,
                                  int32_t l, int32_t w, const double* xs, int32_t L, const double* ys, int32_t W,
@@ -1293,69 +1301,52 @@ extern "C" int sa_xt_rate_interp(const sa_actions* a, const double* xT, const do
   if ((int64_t)L * W > INT32_MAX) return fail(SA_EINVAL, "interpolated grid too large");
   if (a->n == 0) return SA_OK;
   hipStream_t st = (hipStream_t)stream;
-  Scratch sc;  // frac[L + W] | idx[L + W]
-  int rc = scratch_acquire((sizeof(double) + sizeof(int32_t)) * (size_t)(L + W), st, &sc);
-  if (rc) return rc;
-  double* frac = static_cast<double*>(sc.ptr);
-  int32_t* idx = reinterpret_cast<int32_t*>(frac + (L + W));
-  hipLaunchKernelGGL(xt_axes_kernel, dim3((unsigned)((L + W + 255) / 256)), dim3(256), 0, st, cx, cy, l, w, xs, L,
-                     ys, W, idx, frac);
-  const sa_frame& F = a->frames[0];
-  const int vec = aligned16(F.c0) && aligned16(F.c1) && aligned16(F.c2) && aligned16(F.c3) && aligned16(out) &&
-                  ((uintptr_t)F.type_id & 1u) == 0 && ((uintptr_t)F.result_id & 1u) == 0;
-  const int64_t threads = (a->n + 1) / 2;
-  const size_t lds = sizeof(double) * ((size_t)l * w + L + W) + sizeof(int32_t) * (size_t)(L + W);
-  const int dev = current_device();
-  if (lds <= XRI_LDS_MAX && lds <= (size_t)device_lds_max(dev)) {  // surface + node tables in LDS
-    const int cus = device_cus(dev);
-    const int64_t need = (threads + XRI_THREADS - 1) / XRI_THREADS;
-    const int64_t most = (int64_t)cus * SA_XRI_BPC;
-    const unsigned blocks = (unsigned)(need < most ? need : most);
-    hipLaunchKernelGGL(xt_rate_interp_lds_kernel, dim3(blocks), dim3(XRI_THREADS), lds, st, *a, xT, l, w, L, W, idx,
-                       frac, out, err_flags, vec);
-    rc = check_launch("xt_rate_interp_lds_kernel");
-  } else {
-    hipLaunchKernelGGL(xt_rate_interp_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, *a, xT, l,
-                       L, W, idx, frac, out, err_flags, vec);
-    rc = check_launch("xt_rate_interp_kernel");
+  XriTables T(l, w, L, W);
+  if (int rc = T.build(cx, cy, l, w, xs, L, ys, W, st)) return rc;
+  const int vec = coords_vec_ok(a->frames[0], out);
+  if (T.in_lds) {  // surface + node tables in LDS
+    hipLaunchKernelGGL(xt_rate_interp_lds_kernel, dim3(T.blocks(a->n)), dim3(XRI_THREADS), T.lds, st, *a, xT, l, w, L,
+                       W, T.idx, T.frac, out, err_flags, vec);
+    return check_launch("xt_rate_interp_lds_kernel");
   }
-  scratch_release(sc, st);
-  return rc;
+  const int64_t threads = (a->n + 1) / 2;
+  hipLaunchKernelGGL(xt_rate_interp_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, *a, xT, l, L, W,
+                     T.idx, T.frac, out, err_flags, vec);
+  return check_launch("xt_rate_interp_kernel");
+}
+
+// The sets of an interpolated rate from operand codes: every non-empty set has codes and out,
+// both 16-byte aligned.  *most_n: the largest set.
+static int check_rate_sets(int nsets, const uint64_t* const* codes, const int64_t* n, double* const* out,
+                           int64_t* most_n) {
+  *most_n = 0;
+  if (nsets < 0 || (nsets > 0 && (!codes || !n || !out))) return fail(SA_EINVAL, "bad rate sets");
+  for (int q = 0; q < nsets; ++q) {
+    if (n[q] < 0) return fail(SA_EINVAL, "set %d: negative action count", q);
+    if (n[q] > 0 && (!codes[q] || !out[q])) return fail(SA_EINVAL, "set %d: null codes or out", q);
+    if (n[q] > 0 && (!aligned16(codes[q]) || !aligned16(out[q])))
+      return fail(SA_EINVAL, "codes and out must be 16-byte aligned");
+    *most_n = n[q] > *most_n ? n[q] : *most_n;
+  }
+  return SA_OK;
 }
 
 extern "C" int sa_xt_rate_interp_codes_many(int32_t nsets, const uint64_t* const* interp_codes, const int64_t* n,
                                             const double* xT, const double* cx, const double* cy, int32_t l, int32_t w,
                                             const double* xs, int32_t L, const double* ys, int32_t W,
                                             double* const* out, int32_t* err_flags, void* stream) {
-  if (nsets < 0 || (nsets > 0 && (!interp_codes || !n || !out)) || !xT || !cx || !cy || !xs || !ys || L < 1 || W < 1)
-    return fail(SA_EINVAL, "bad xt_rate_interp_codes args");
+  if (!xT || !cx || !cy || !xs || !ys || L < 1 || W < 1) return fail(SA_EINVAL, "bad xt_rate_interp_codes args");
   if (l < 2 || w < 2) return fail(SA_EINVAL, "interpolation needs at least 2 cells per axis");
   if ((int64_t)L * W > INT32_MAX) return fail(SA_EINVAL, "interpolated grid too large");
   int64_t most_n = 0;
-  for (int q = 0; q < nsets; ++q) {
-    if (n[q] < 0) return fail(SA_EINVAL, "set %d: negative action count", q);
-    if (n[q] > 0 && (!interp_codes[q] || !out[q])) return fail(SA_EINVAL, "set %d: null codes or out", q);
-    if (n[q] > 0 && (!aligned16(interp_codes[q]) || !aligned16(out[q])))
-      return fail(SA_EINVAL, "codes and out must be 16-byte aligned");
-    most_n = n[q] > most_n ? n[q] : most_n;
-  }
-  const size_t lds = sizeof(double) * ((size_t)l * w + L + W) + sizeof(int32_t) * (size_t)(L + W);
-  const int dev = current_device();
-  if (lds > XRI_LDS_MAX || lds > (size_t)device_lds_max(dev))
-    return fail(SA_EINVAL, "surface and node tables exceed the LDS");
+  if (int rc = check_rate_sets(nsets, interp_codes, n, out, &most_n)) return rc;
+  XriTables T(l, w, L, W);
+  if (!T.in_lds) return fail(SA_EINVAL, "surface and node tables exceed the LDS");
   if (most_n == 0) return SA_OK;
   hipStream_t st = (hipStream_t)stream;
-  Scratch sc;  // frac[L + W] | idx[L + W]
-  int rc = scratch_acquire((sizeof(double) + sizeof(int32_t)) * (size_t)(L + W), st, &sc);
-  if (rc) return rc;
-  double* frac = static_cast<double*>(sc.ptr);
-  int32_t* idx = reinterpret_cast<int32_t*>(frac + (L + W));
-  hipLaunchKernelGGL(xt_axes_kernel, dim3((unsigned)((L + W + 255) / 256)), dim3(256), 0, st, cx, cy, l, w, xs, L,
-                     ys, W, idx, frac);
-  const int64_t threads = (most_n + 1) / 2;
-  const int64_t need = (threads + XRI_THREADS - 1) / XRI_THREADS;
-  const int64_t most = (int64_t)device_cus(dev) * SA_XRI_BPC;
-  for (int q0 = 0; q0 < nsets && !rc; q0 += XRI_MAX_SETS) {
+  if (int rc = T.build(cx, cy, l, w, xs, L, ys, W, st)) return rc;
+  const unsigned blocks = T.blocks(most_n);
+  for (int q0 = 0; q0 < nsets; q0 += XRI_MAX_SETS) {
     XriSets S{};
     for (int q = q0; q < nsets && q < q0 + XRI_MAX_SETS; ++q) {
       if (n[q] == 0) continue;
@@ -1365,12 +1356,11 @@ extern "C" int sa_xt_rate_interp_codes_many(int32_t nsets, const uint64_t* const
       ++S.n;
     }
     if (!S.n) continue;
-    hipLaunchKernelGGL(xt_rate_icodes_lds_kernel, dim3((unsigned)(need < most ? need : most)), dim3(XRI_THREADS),
-                       lds, st, S, xT, l, w, L, W, idx, frac, err_flags);
-    rc = check_launch("xt_rate_icodes_lds_kernel");
+    hipLaunchKernelGGL(xt_rate_icodes_lds_kernel, dim3(blocks), dim3(XRI_THREADS), T.lds, st, S, xT, l, w, L, W, T.idx,
+                       T.frac, err_flags);
+    if (int rc = check_launch("xt_rate_icodes_lds_kernel")) return rc;
   }
-  scratch_release(sc, st);
-  return rc;
+  return SA_OK;
 }
 
 // ExpectedThreat.fit + rate(use_interpolation=True) of the same actions in one call: sa_xt_solve_ex
@@ -1386,37 +1376,24 @@ extern "C" int sa_xt_fit_rate_interp_codes(const int64_t* shot, const int64_t* g
                                            const uint64_t* const* interp_codes, const int64_t* n, const double* cx,
                                            const double* cy, const double* xs, int32_t L, const double* ys,
                                            int32_t W, double* const* out, int32_t* err_flags, void* stream) {
-  if (l < 1 || w < 1 || !mats || !path) return fail(SA_EINVAL, "bad l, w or null mats / path");
+  if (int rc = check_grid(l, w)) return rc;
+  if (!mats || !path) return fail(SA_EINVAL, "null mats / path");
   if (l * w <= XT_SOLVE_MAX_C) return fail(SA_EINVAL, "the fused fit + rate is for grids above %d cells", XT_SOLVE_MAX_C);
   // the rate's arguments checked before anything is launched (sa_xt_rate_interp_codes_many's own
   // checks would first run behind the solve)
-  if (nsets < 0 || (nsets > 0 && (!interp_codes || !n || !out)) || !cx || !cy || !xs || !ys || L < 1 || W < 1 ||
-      l < 2 || w < 2 || (int64_t)L * W > INT32_MAX)
+  if (!cx || !cy || !xs || !ys || L < 1 || W < 1 || l < 2 || w < 2 || (int64_t)L * W > INT32_MAX)
     return fail(SA_EINVAL, "bad rate arguments");
-  for (int q = 0; q < nsets; ++q)
-    if (n[q] < 0 || (n[q] > 0 && (!interp_codes[q] || !out[q] || !aligned16(interp_codes[q]) || !aligned16(out[q]))))
-      return fail(SA_EINVAL, "set %d: bad count, codes or out", q);
-  struct Rate {
-    int32_t nsets;
-    const uint64_t* const* codes;
-    const int64_t* n;
-    const double *xT, *cx, *cy, *xs, *ys;
-    int32_t l, w, L, W;
-    double* const* out;
-    int32_t* err;
-    void* stream;
-  } r{nsets, interp_codes, n, mats + 3 * (int64_t)(l * w), cx, cy, xs, ys, l, w, L, W, out, err_flags, stream};
-  auto rate = [](void* p) -> int {
-    const Rate& q = *static_cast<const Rate*>(p);
-    return sa_xt_rate_interp_codes_many(q.nsets, q.codes, q.n, q.xT, q.cx, q.cy, q.l, q.w, q.xs, q.L, q.ys, q.W,
-                                        q.out, q.err, q.stream);
+  int64_t most_n = 0;
+  if (int rc = check_rate_sets(nsets, interp_codes, n, out, &most_n)) return rc;
+  auto rate = [&]() {  // over the surface in mats[3]
+    return sa_xt_rate_interp_codes_many(nsets, interp_codes, n, mats + 3 * (int64_t)(l * w), cx, cy, l, w, xs, L, ys, W,
+                                        out, err_flags, stream);
   };
-  SolveHook hook{rate, &r, false};
-  int rc = solve_ex(shot, goal, move, trans, l, w, eps, max_iter, flags, mats, nullptr, heatmaps, n_iter, path, ell,
-                    row_len, stream, &hook);
-  if (rc) return rc;
-  if (!hook.ran || *path != SA_XT_PATH_REORDERED) rc = rate(&r);  // the surface the solve returned
-  return rc;
+  SolveHook hook{[](void* p) { return (*static_cast<decltype(rate)*>(p))(); }, &rate, false};
+  if (int rc = solve_ex(shot, goal, move, trans, l, w, eps, max_iter, flags, mats, nullptr, heatmaps, n_iter, path, ell,
+                        row_len, stream, &hook))
+    return rc;
+  return !hook.ran || *path != SA_XT_PATH_REORDERED ? rate() : SA_OK;  // the surface the solve returned
 }
 
 extern "C" int sa_xt_rate_interp_codes(const uint64_t* interp_codes, int64_t n, const double* xT, const double* cx,
@@ -1429,11 +1406,7 @@ extern "C" int sa_xt_rate_interp_codes(const uint64_t* interp_codes, int64_t n, 
 extern "C" int sa_xt_probabilities(const int64_t* shot, const int64_t* goal, const int64_t* move, int32_t C,
                                    double* mats, double* gs, double* pmove, void* stream) {
   if (C < 1 || !shot || !goal || !move || !mats || !gs || !pmove) return fail(SA_EINVAL, "bad xt probability args");
-  hipLaunchKernelGGL(xt_prob_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                     reinterpret_cast<const unsigned long long*>(shot),
-                     reinterpret_cast<const unsigned long long*>(goal),
-                     reinterpret_cast<const unsigned long long*>(move), C, mats, gs, pmove);
-  return check_launch("xt_prob_kernel");
+  return normalise(shot, goal, move, nullptr, C, mats, gs, pmove, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int sa_xt_iterate_rows(const int32_t* cnt_rows, const int64_t* move, const double* gs,

@@ -1369,6 +1369,21 @@ static bool xt_band_shape(int C, XbShape* s) {
   return true;
 }
 
+// A valid grid that the band-owned count holds, and its shape.
+static int band_grid(int l, int w, XbShape* s) {
+  if (int rc = check_grid(l, w)) return rc;
+  if (!xt_band_shape(l * w, s)) return fail(SA_EINVAL, "the band-owned count does not hold %d cells", l * w);
+  return SA_OK;
+}
+
+// Bucket sets as sa_xt_count_bucket leaves them: keys and band offsets per set.
+static int check_bucket_sets(int nsets, const xb_key_t* const* buckets, const int64_t* const* band_off) {
+  if (nsets < 0 || (nsets > 0 && (!buckets || !band_off))) return fail(SA_EINVAL, "bad bucket sets");
+  for (int k = 0; k < nsets; ++k)
+    if (!band_off[k]) return fail(SA_EINVAL, "null band offsets");
+  return SA_OK;
+}
+
 // K1 -> K2 -> K3 of one batch: its keys sorted into buckets[] by band, band_off[NB + 1].
 static int bucket_batch(const sa_actions& A, const uint32_t* cells, int64_t n, int l, int w, const XbShape& S,
                         xb_key_t* buckets, int64_t* band_off, int32_t* err, const XkRate& RO, hipStream_t st) {
@@ -1389,37 +1404,27 @@ static int bucket_batch(const sa_actions& A, const uint32_t* cells, int64_t n, i
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t nbb = al((size_t)S.NB * 4), rcb = al((size_t)regions * 4);
   const size_t bytes = 2 * nbb + rcb + (size_t)regions * XK_CHUNK * 4;
-  Scratch sc;
-  int rc = scratch_acquire(bytes, st, &sc);
-  if (rc) return rc;
-  char* base = static_cast<char*>(sc.ptr);
-  uint32_t* band_cnt = reinterpret_cast<uint32_t*>(base);
-  uint32_t* cursor = reinterpret_cast<uint32_t*>(base + nbb);
-  uint32_t* region_cnt = reinterpret_cast<uint32_t*>(base + 2 * nbb);
-  uint32_t* keys = reinterpret_cast<uint32_t*>(base + 2 * nbb + rcb);
-  rc = check_hip(hipMemsetAsync(band_cnt, 0, 2 * nbb, st), "memset band counts and cursors");
-  if (!rc) {
-    sa_actions none;
-    memset(&none, 0, sizeof(none));
-    const sa_frame& F = A.frames[0];
-    const int vec = !cells && n >= 2 && aligned16(F.c0) && aligned16(F.c1) && aligned16(F.c2) && aligned16(F.c3) &&
-                    ((uintptr_t)F.type_id & 1u) == 0 && ((uintptr_t)F.result_id & 1u) == 0;
-    if (cells)
-      hipLaunchKernelGGL((xt_keys_kernel<true>), dim3((unsigned)regions), dim3(XK_THREADS), (size_t)S.NB * 4, st, none,
-                         cells, n, l, w, S, keys, region_cnt, band_cnt, err, XkRate{nullptr, nullptr, 0, 0}, 0, chunk);
-    else
-      hipLaunchKernelGGL((xt_keys_kernel<false>), dim3((unsigned)regions), dim3(XK_THREADS), (size_t)S.NB * 4, st, A,
-                         nullptr, n, l, w, S, keys, region_cnt, band_cnt, err, RO, vec, chunk);
-    rc = check_launch("xt_keys_kernel");
-  }
-  if (!rc) {
-    const size_t lds = ((size_t)2 * S.NB + XK_CHUNK) * 4;
-    hipLaunchKernelGGL(xt_keys_scatter_kernel, dim3((unsigned)regions), dim3(XS_THREADS), lds, st, keys,
-                       region_cnt, S, band_cnt, band_off, cursor, buckets);
-    rc = check_launch("xt_keys_scatter_kernel");
-  }
-  scratch_release(sc, st);
-  return rc;
+  ScratchGuard sc;
+  if (int rc = sc.acquire(bytes, st)) return rc;
+  uint32_t* band_cnt = sc.at<uint32_t>();
+  uint32_t* cursor = sc.at<uint32_t>(nbb);
+  uint32_t* region_cnt = sc.at<uint32_t>(2 * nbb);
+  uint32_t* keys = sc.at<uint32_t>(2 * nbb + rcb);
+  if (int rc = check_hip(hipMemsetAsync(band_cnt, 0, 2 * nbb, st), "memset band counts and cursors")) return rc;
+  sa_actions none;
+  memset(&none, 0, sizeof(none));
+  const int vec = !cells && n >= 2 && coords_vec_ok(A.frames[0]);
+  if (cells)
+    hipLaunchKernelGGL((xt_keys_kernel<true>), dim3((unsigned)regions), dim3(XK_THREADS), (size_t)S.NB * 4, st, none,
+                       cells, n, l, w, S, keys, region_cnt, band_cnt, err, XkRate{nullptr, nullptr, 0, 0}, 0, chunk);
+  else
+    hipLaunchKernelGGL((xt_keys_kernel<false>), dim3((unsigned)regions), dim3(XK_THREADS), (size_t)S.NB * 4, st, A,
+                       nullptr, n, l, w, S, keys, region_cnt, band_cnt, err, RO, vec, chunk);
+  if (int rc = check_launch("xt_keys_kernel")) return rc;
+  const size_t lds = ((size_t)2 * S.NB + XK_CHUNK) * 4;
+  hipLaunchKernelGGL(xt_keys_scatter_kernel, dim3((unsigned)regions), dim3(XS_THREADS), lds, st, keys, region_cnt, S,
+                     band_cnt, band_off, cursor, buckets);
+  return check_launch("xt_keys_scatter_kernel");
 }
 
 static int count_from_buckets(int nsets, const xb_key_t* const* buckets, const int64_t* const* band_off,
@@ -1458,23 +1463,20 @@ int xt_count_bands(const sa_actions& A, const uint32_t* cells, int64_t n, int l,
                    int64_t* goal, int64_t* move, int32_t* trans, int32_t* err, uint32_t* codes, hipStream_t st) {
   XbShape S;
   if (!xt_band_shape(l * w, &S)) return fail(SA_EINVAL, "grid outside the band-owned count");
-  Scratch sc;  // buckets [n] | band_off [NB + 1]
+  ScratchGuard sc;  // buckets [n] | band_off [NB + 1]
   const size_t bb = ((size_t)n * sizeof(xb_key_t) + 255) & ~(size_t)255;
-  int rc = scratch_acquire(bb + ((size_t)S.NB + 1) * 8, st, &sc);
-  if (rc) return rc;
-  xb_key_t* buckets = static_cast<xb_key_t*>(sc.ptr);
-  int64_t* band_off = reinterpret_cast<int64_t*>(static_cast<char*>(sc.ptr) + bb);
-  rc = bucket_batch(A, cells, n, l, w, S, buckets, band_off, err, XkRate{codes, nullptr, 0, 0}, st);
-  if (!rc) {
-    const xb_key_t* bk[1] = {buckets};
-    const int64_t* bo[1] = {band_off};
-    rc = count_from_buckets(1, bk, bo, S, 0, S.NB, shot, goal, move, trans, 0, st);
-  }
-  scratch_release(sc, st);
-  return rc;
+  if (int rc = sc.acquire(bb + ((size_t)S.NB + 1) * 8, st)) return rc;
+  const xb_key_t* buckets = sc.at<xb_key_t>();
+  const int64_t* band_off = sc.at<int64_t>(bb);
+  if (int rc = bucket_batch(A, cells, n, l, w, S, sc.at<xb_key_t>(), sc.at<int64_t>(bb), err,
+                            XkRate{codes, nullptr, 0, 0}, st))
+    return rc;
+  return count_from_buckets(1, &buckets, &band_off, S, 0, S.NB, shot, goal, move, trans, 0, st);
 }
 
-// Compact form + iteration used by sa_xt_solve for C > SA_XT_SOLVE_MAX_C.
+// The compact form of count rows (ell | row_len) and one value iteration over it, for grids of
+// up to XE_XMAX cells: sa_xt_solve_ex above SA_XT_SOLVE_MAX_C cells, sa_xt_compact_rows,
+// sa_xt_iterate_compact and the row-sharded solve.
 bool xt_compact_ok(int C) { return C >= 1 && C <= XE_XMAX; }
 size_t xt_compact_bytes(int C, int nrows) { return (size_t)(nrows > 0 ? nrows : 0) * (size_t)xe_pitch(C) * 4; }
 int xt_compact_build(const int32_t* cnt_rows, int C, int nrows, uint32_t* ell, int32_t* row_len, hipStream_t st) {
@@ -1542,29 +1544,26 @@ static int xt_solve_reordered(const uint32_t* ell, const int32_t* row_len, const
   const size_t xbytes = (size_t)(max_iter + 1) * (size_t)hp * 8;
   if (xbytes > ((size_t)512 << 20)) return SA_OK;
   const size_t cbytes = ((size_t)(XF_FLAGS + max_iter + 4) * 4 + 255) & ~(size_t)255;
-  Scratch sc;
-  int rc = scratch_acquire(cbytes + xbytes, st, &sc);
-  if (rc) return rc;
-  int32_t* ctrl = static_cast<int32_t*>(sc.ptr);
-  double* xb = reinterpret_cast<double*>(static_cast<char*>(sc.ptr) + cbytes);
+  ScratchGuard sc;  // held until the host has waited for the solve
+  if (int rc = sc.acquire(cbytes + xbytes, st)) return rc;
+  int32_t* ctrl = sc.at<int32_t>();
+  double* xb = sc.at<double>(cbytes);
   int32_t hl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int32_t* pin = pinned_ctrl();
   int32_t* h = pin ? pin : hl;
-  rc = check_hip(hipMemsetAsync(ctrl, 0, cbytes, st), "memset solve control");
-  if (!rc) {
-    hipLaunchKernelGGL(xt_solve_reordered_kernel, dim3((unsigned)G), dim3(XF_THREADS), lds, st, ell, row_len,
-                       reinterpret_cast<const unsigned long long*>(move), gs, pmove, C, hp, eps, max_iter, pmax, kov,
-                       xb, heat, xt_out, ctrl, SA_DEBUG ? g_xf_force_abort : -1);
-    rc = check_launch("xt_solve_reordered_kernel");
-  }
-  if (!rc) rc = check_hip(hipMemcpyAsync(h, ctrl, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, st), "copy solve control");
-  if (!rc && hook) {  // queued behind the solve: no host round trip between the two
-    rc = hook->fn(hook->ctx);
+  if (int rc = check_hip(hipMemsetAsync(ctrl, 0, cbytes, st), "memset solve control")) return rc;
+  hipLaunchKernelGGL(xt_solve_reordered_kernel, dim3((unsigned)G), dim3(XF_THREADS), lds, st, ell, row_len,
+                     reinterpret_cast<const unsigned long long*>(move), gs, pmove, C, hp, eps, max_iter, pmax, kov, xb,
+                     heat, xt_out, ctrl, SA_DEBUG ? g_xf_force_abort : -1);
+  if (int rc = check_launch("xt_solve_reordered_kernel")) return rc;
+  if (int rc = check_hip(hipMemcpyAsync(h, ctrl, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, st), "copy solve control"))
+    return rc;
+  if (hook) {  // queued behind the solve: no host round trip between the two
+    const int rc = hook->fn(hook->ctx);
     hook->ran = true;
+    if (rc) return rc;
   }
-  if (!rc) rc = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-  scratch_release(sc, st);
-  if (rc) return rc;
+  if (int rc = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize")) return rc;
   if (h[XF_ABORT])  // 1: a barrier timed out; 2 / 4: a bound or an escaped count (not launchable)
     *status = h[XF_ABORT] == 1 ? 3 : 2;
   else if (h[XF_AMB])
@@ -1597,35 +1596,15 @@ int xt_compact_solve(const uint32_t* ell, const int32_t* row_len, const int32_t*
     }
     *path = status == 1 ? SA_XT_PATH_INSIDE_BOUND : status == 3 ? SA_XT_PATH_TIMEOUT : SA_XT_PATH_UNAVAILABLE;
   }
-  Scratch sc;  // convergence flags [max_iter + 1]
-  int rc = scratch_acquire(sizeof(int32_t) * ((size_t)max_iter + 1), st, &sc);
-  if (rc) return rc;
-  int32_t* dflags = static_cast<int32_t*>(sc.ptr);
-  rc = check_hip(hipMemsetAsync(dflags, 0, sizeof(int32_t) * ((size_t)max_iter + 1), st), "memset");
-  std::vector<int32_t> hflags(max_iter + 1, 0);
-  const int batch = 8;
-  int iters = -1;
-  for (int it0 = 0; !rc && it0 < max_iter && iters < 0; it0 += batch) {
-    const int it1 = it0 + batch < max_iter ? it0 + batch : max_iter;
-    for (int it = it0; it < it1 && !rc; ++it) {
-      double* xi = heat + (int64_t)it * C;
-      rc = xt_compact_iterate(ell, row_len, cnt_rows, move, gs, pmove, C, 0, C, xi, eps, xi + C,
+  ScratchGuard sc;  // convergence flags [max_iter + 1]
+  if (int rc = sc.acquire(sizeof(int32_t) * ((size_t)max_iter + 1), st)) return rc;
+  int32_t* dflags = sc.at<int32_t>();
+  if (int rc = check_hip(hipMemsetAsync(dflags, 0, sizeof(int32_t) * ((size_t)max_iter + 1), st), "memset")) return rc;
+  return iterate_to_convergence(max_iter, dflags, st, n_iter, [&](int it) {
+    double* xi = heat + (int64_t)it * C;
+    return xt_compact_iterate(ell, row_len, cnt_rows, move, gs, pmove, C, 0, C, xi, eps, xi + C,
                               it > 0 ? dflags + it - 1 : nullptr, dflags + it, st);
-    }
-    if (!rc)
-      rc = check_hip(hipMemcpyAsync(hflags.data() + it0, dflags + it0, sizeof(int32_t) * (it1 - it0),
-                                    hipMemcpyDeviceToHost, st),
-                     "copy flags");
-    if (!rc) rc = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-    for (int it = it0; !rc && it < it1; ++it)
-      if (hflags[it] == 0) {
-        iters = it + 1;
-        break;
-      }
-  }
-  scratch_release(sc, st);
-  *n_iter = iters;
-  return rc;
+  });
 }
 }  // namespace sa
 
@@ -1641,9 +1620,8 @@ extern "C" int sa_debug_xt_solve_abort(int32_t iteration) {
 }
 
 extern "C" int sa_xt_band_shape(int32_t l, int32_t w, int32_t* rows_per_band, int32_t* n_bands) {
-  if (l < 1 || w < 1 || (int64_t)l * w > 46340) return fail(SA_EINVAL, "bad l or w");
   XbShape S;
-  if (!xt_band_shape(l * w, &S)) return fail(SA_EINVAL, "the band-owned count does not hold %d cells", l * w);
+  if (int rc = band_grid(l, w, &S)) return rc;
   if (rows_per_band) *rows_per_band = S.R;
   if (n_bands) *n_bands = S.NB;
   return SA_OK;
@@ -1652,9 +1630,8 @@ extern "C" int sa_xt_band_shape(int32_t l, int32_t w, int32_t* rows_per_band, in
 extern "C" int sa_xt_count_bucket(const sa_actions* a, const uint32_t* cells, int64_t n, int32_t l, int32_t w,
                                   uint16_t* buckets, int64_t* band_off, int32_t* err_flags, uint32_t* codes,
                                   uint64_t* interp_codes, int32_t L, int32_t W, void* stream) {
-  if (l < 1 || w < 1 || (int64_t)l * w > 46340) return fail(SA_EINVAL, "bad l or w");
   XbShape S;
-  if (!xt_band_shape(l * w, &S)) return fail(SA_EINVAL, "the band-owned count does not hold %d cells", l * w);
+  if (int rc = band_grid(l, w, &S)) return rc;
   if (!band_off || !err_flags) return fail(SA_EINVAL, "null output");
   if (cells) {
     if (n < 0 || (int64_t)l * w > SA_XT_CELLS_MAX_C) return fail(SA_EINVAL, "cell codes need l * w <= %d", SA_XT_CELLS_MAX_C);
@@ -1662,9 +1639,8 @@ extern "C" int sa_xt_count_bucket(const sa_actions* a, const uint32_t* cells, in
   } else {
     if (!a || a->n < 0 || a->atomic) return fail(SA_EINVAL, "bad sa_actions (SPADL actions required)");
     n = a->n;
-    const sa_frame& F = a->frames[0];
-    if (n > 0 && (!F.type_id || !F.result_id || !F.c0 || !F.c1 || !F.c2 || !F.c3))
-      return fail(SA_EINVAL, "null input column");
+    if (n > 0)
+      if (int rc = check_xy_columns(a->frames[0])) return rc;
     if (codes && !aligned16(codes)) return fail(SA_EINVAL, "codes must be 16-byte aligned");
     if (codes && (int64_t)l * w > 65535) return fail(SA_EINVAL, "rate codes need l * w <= 65535");
     if (interp_codes && (!aligned16(interp_codes) || L < 1 || W < 1 || (int64_t)L * W > INT32_MAX))
@@ -1692,12 +1668,9 @@ extern "C" int sa_xt_count_from_buckets_ex(int32_t nsets, const uint16_t* const*
                                            const int64_t* const* band_off, int32_t l, int32_t w, int64_t* shot,
                                            int64_t* goal, int64_t* move, int32_t* trans, int32_t flags,
                                            uint32_t* ell, int32_t* row_len, void* stream) {
-  if (l < 1 || w < 1 || (int64_t)l * w > 46340) return fail(SA_EINVAL, "bad l or w");
   XbShape S;
-  if (!xt_band_shape(l * w, &S)) return fail(SA_EINVAL, "the band-owned count does not hold %d cells", l * w);
-  if (nsets < 0 || (nsets > 0 && (!buckets || !band_off))) return fail(SA_EINVAL, "bad bucket sets");
-  for (int k = 0; k < nsets; ++k)
-    if (!band_off[k]) return fail(SA_EINVAL, "null band offsets");
+  if (int rc = band_grid(l, w, &S)) return rc;
+  if (int rc = check_bucket_sets(nsets, buckets, band_off)) return rc;
   if (!shot || !goal || !move || !trans) return fail(SA_EINVAL, "null count buffer");
   if (flags & ~(SA_XT_COUNT_OVERWRITE | SA_XT_COUNT_COMPACT_ONLY)) return fail(SA_EINVAL, "unknown flags");
   if (!ell != !row_len) return fail(SA_EINVAL, "ell and row_len come together");
@@ -1718,13 +1691,10 @@ extern "C" int sa_xt_count_band_rows(int32_t nsets, const uint16_t* const* bucke
                                      int32_t l, int32_t w, int32_t band0, int32_t nbands, int64_t* shot_rows,
                                      int64_t* goal_rows, int64_t* move_rows, int32_t* trans_rows, int32_t flags,
                                      void* stream) {
-  if (l < 1 || w < 1 || (int64_t)l * w > 46340) return fail(SA_EINVAL, "bad l or w");
   XbShape S;
-  if (!xt_band_shape(l * w, &S)) return fail(SA_EINVAL, "the band-owned count does not hold %d cells", l * w);
+  if (int rc = band_grid(l, w, &S)) return rc;
   if (band0 < 0 || nbands < 0 || band0 + nbands > S.NB) return fail(SA_EINVAL, "band range outside [0, %d)", S.NB);
-  if (nsets < 0 || (nsets > 0 && (!buckets || !band_off))) return fail(SA_EINVAL, "bad bucket sets");
-  for (int k = 0; k < nsets; ++k)
-    if (!band_off[k]) return fail(SA_EINVAL, "null band offsets");
+  if (int rc = check_bucket_sets(nsets, buckets, band_off)) return rc;
   if (nbands > 0 && (!shot_rows || !goal_rows || !move_rows || !trans_rows))
     return fail(SA_EINVAL, "null count buffer");
   if (flags & ~SA_XT_COUNT_OVERWRITE) return fail(SA_EINVAL, "unknown flags");

@@ -127,6 +127,52 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     assert fit_rate(16, 12, 0, 1050) == _native.SA_EINVAL and b'above' in lib.sa_last_error()
     assert fit_rate(105, 68, -1, 1050) == _native.SA_EINVAL and b'rate' in lib.sa_last_error()
     assert fit_rate(105, 68, 0, 0) == _native.SA_EINVAL and b'rate' in lib.sa_last_error()
+    # the entry points behind the shared grid, bucket-set and column checks
+    einval = lambda rc, word: rc == _native.SA_EINVAL and word in lib.sa_last_error()  # noqa: E731
+    ptrs = lambda *v: ctypes.cast((ctypes.c_void_p * len(v))(*v), ctypes.POINTER(ctypes.c_void_p))  # noqa: E731
+    band_rows = lambda nsets, bk, bo, l, band0, nbands: lib.sa_xt_count_band_rows(  # noqa: E731
+        nsets, bk, bo, l, 68, band0, nbands, fake, fake, fake, fake, _native.SA_XT_COUNT_OVERWRITE, None)
+    assert einval(band_rows(1, ptrs(256), ptrs(None), 105, 0, 1), b'null band offsets')
+    assert einval(band_rows(1, none_p, none_p, 105, 0, 1), b'bucket sets')
+    assert einval(band_rows(0, none_p, none_p, 105, -1, 1), b'band range')
+    assert einval(band_rows(0, none_p, none_p, 105, 0, 1 << 20), b'band range')
+    assert einval(band_rows(0, none_p, none_p, 0, 0, 1), b'bad l')
+    assert einval(lib.sa_xt_count_from_buckets_ex(1, ptrs(256), ptrs(None), 105, 68, fake, fake, fake, fake,
+                                                  _native.SA_XT_COUNT_OVERWRITE, None, None, None),
+                  b'null band offsets')
+    bucket = lambda a, l, w: lib.sa_xt_count_bucket(a, None, 0, l, w, fake, fake, fake, None, None,  # noqa: E731
+                                                   0, 0, None)
+    assert einval(bucket(ctypes.byref(s), 105, 68), b'null input column')  # n = 10, no columns
+    assert einval(bucket(ctypes.byref(s), 0, 68), b'bad l')
+    assert einval(bucket(ctypes.byref(s), 1000, 1000), b'bad l')
+    assert einval(lib.sa_xt_count_codes(ctypes.byref(s), 16, 12, fake, fake, fake, fake, fake, None, 0, None),
+                  b'null input column')
+    assert einval(lib.sa_xt_compact_rows(fake, 0, 1, fake, fake, None), b'compact')
+    assert einval(lib.sa_xt_compact_rows(fake, 9473, 1, fake, fake, None), b'compact')
+    assert einval(lib.sa_xt_iterate_compact(fake, fake, fake, fake, fake, fake, 9473, 0, 1, fake, 1e-5, fake,
+                                            None, fake, None), b'compact')
+    assert einval(lib.sa_xt_iterate_compact(fake, fake, fake, fake, fake, fake, 1200, 1199, 2, fake, 1e-5,
+                                            fake, None, fake, None), b'row range')
+    solve_compact = lambda C, ell: lib.sa_xt_solve_compact(  # noqa: E731
+        ell, fake, fake, fake, fake, fake, C, 1e-5, 100, 0, fake, ctypes.byref(n_iter), ctypes.byref(path), None)
+    assert einval(solve_compact(9473, fake), b'compact')
+    assert einval(solve_compact(1200, ctypes.c_void_p(264)), b'aligned')
+    normalize = lambda l, w: lib.sa_xt_normalize(fake, fake, fake, fake, l, w, fake, fake, None)  # noqa: E731
+    assert einval(normalize(0, 12), b'bad l')
+    assert einval(lib.sa_xt_normalize(fake, fake, fake, fake, 16, 12, fake, None, None), b'null pointer')
+    solve_async = lambda l, w, m: lib.sa_xt_solve_async(fake, fake, fake, fake, l, w, 1e-5, m, fake,  # noqa: E731
+                                                        fake, fake, fake, None)
+    assert einval(solve_async(16, 0, 100), b'bad l')
+    assert einval(solve_async(16, 12, -1), b'max_iter')
+    assert einval(solve_async(40, 30, 100), b'asynchronous')
+    # l * w is bounded in 64 bits wherever a grid comes in: 65536 * 65536 is 0 in 32 bits
+    solve_ex = lambda l, w: lib.sa_xt_solve_ex(fake, fake, fake, fake, l, w, 1e-5, 100, 0, fake, fake,  # noqa: E731
+                                               fake, ctypes.byref(n_iter), ctypes.byref(path), None, None, None)
+    for l, w in ((65536, 65536), (46341, 1), (300, 300)):
+        assert einval(solve_ex(l, w), b'bad l')
+        assert einval(solve_async(l, w, 100), b'bad l')
+        assert einval(normalize(l, w), b'bad l')
+        assert einval(fit_rate(l, w, 0, 1050), b'bad l')
 
 
 # ----------------------------------------------------------------------------- catalogue

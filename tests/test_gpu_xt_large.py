@@ -550,3 +550,173 @@ def test_fused_fit_rate_equals_solve_then_rate(sa, hot):
     assert int(err.item()) == int(ref_err.item())
     with pytest.raises(ValueError):
         ops.xt_fit_rate_interp_codes(ops.xt_count_many(bs, 16, 12), ic, ns)
+
+
+# ---------------------------------------------------------------- the host loops of the solve
+def _solve_ex(sa, acc, eps, max_iter, transition=True):
+    """sa_xt_solve_ex through the library, without ops.xt_solve's raise when max_iter is reached:
+    (mats [4, C], trans_t or None, heatmaps [max_iter + 1, C], n_iter, path)."""
+    _native = sa['_native']
+    from socceraction_amd.batch import stream_handle
+    C, dev = acc.C, acc.shot.device
+    mats = torch.full((4, C), -1.0, dtype=torch.float64, device=dev)
+    tt = torch.empty((C, C), dtype=torch.float64, device=dev) if transition else None
+    heat = torch.full((max_iter + 1, C), -1.0, dtype=torch.float64, device=dev)
+    n_iter, path = _native.ctypes.c_int32(7), _native.ctypes.c_int32(7)
+    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    _native.check(_native.lib().sa_xt_solve_ex(
+        p(acc.shot), p(acc.goal), p(acc.move), p(acc.trans), acc.l, acc.w, float(eps), int(max_iter), 0,
+        p(mats), p(tt), p(heat), _native.ctypes.byref(n_iter), _native.ctypes.byref(path), None, None,
+        stream_handle()))
+    return mats, tt, heat, n_iter.value, _native.XT_SOLVE_PATHS[path.value]
+
+
+def _dense_loop(sa, acc, eps, max_iter):
+    """The value iteration driven from here, as shard._solve_row_block drives it: the
+    probabilities, then one sa_xt_iterate_rows launch per iteration over rows [0, C) and the
+    first zero flag: (mats [3, C], heatmaps [max_iter + 1, C], n_iter or -1)."""
+    _native = sa['_native']
+    from socceraction_amd.batch import stream_handle
+    lib = _native.lib()
+    C, dev = acc.C, acc.shot.device
+    mats = torch.empty((3, C), dtype=torch.float64, device=dev)
+    gp = torch.empty((2, C), dtype=torch.float64, device=dev)
+    p = lambda t: t.data_ptr()  # noqa: E731
+    _native.check(lib.sa_xt_probabilities(p(acc.shot), p(acc.goal), p(acc.move), C, p(mats), p(gp[0]),
+                                          p(gp[1]), stream_handle()))
+    heat = torch.zeros((max_iter + 1, C), dtype=torch.float64, device=dev)
+    flags = torch.zeros(max_iter + 1, dtype=torch.int32, device=dev)
+    for it in range(max_iter):
+        _native.check(lib.sa_xt_iterate_rows(p(acc.trans), p(acc.move), p(gp[0]), p(gp[1]), C, 0, C,
+                                             p(heat[it]), float(eps), p(heat[it + 1]), None, p(flags[it:]),
+                                             stream_handle()))
+    done = np.flatnonzero(flags[:max_iter].cpu().numpy() == 0)
+    return mats, heat, int(done[0]) + 1 if len(done) else -1
+
+
+def _sparse_counts(ops, l, w, dev):
+    """Counts of a grid too large to count actions into quickly, written directly: 300 non-zero
+    rows (rows 0 and C - 1 among them), every other one with a single entry and the rest with
+    about 400 spread over the whole width, most of the weight on the columns of those same rows
+    so that the iteration keeps moving for tens of iterations."""
+    C = l * w
+    rng = np.random.default_rng(C)
+    hot = np.unique(np.concatenate([[0, C - 1], rng.choice(C, 298, replace=False)]))
+    rows, cols, vals = [], [], []
+    for i, r in enumerate(hot):
+        if i % 2:
+            c = np.array([hot[(i * 7 + 3) % len(hot)]])
+            v = rng.integers(20, 400, 1)
+        else:
+            c = np.unique(np.concatenate([rng.choice(C, 300, replace=False),
+                                          rng.choice(hot, 100, replace=False), [0, C - 1]]))
+            v = np.where(np.isin(c, hot), rng.integers(20, 120, len(c)), rng.integers(1, 4, len(c)))
+        rows.append(np.full(len(c), r))
+        cols.append(c)
+        vals.append(v)
+    rows, cols, vals = (np.concatenate(a).astype(np.int64) for a in (rows, cols, vals))
+    assert (np.bincount(cols // 128, minlength=(C + 127) // 128) > 0).all()  # every 128-column chunk
+    shot = rng.integers(1, 30, C)
+    goal = rng.integers(0, shot + 1)
+    move = rng.integers(1, 40, C)
+    np.add.at(move, rows, vals)
+    acc = ops.xt_zero_counts(l, w, dev)
+    acc.shot.copy_(torch.from_numpy(shot))
+    acc.goal.copy_(torch.from_numpy(goal))
+    acc.move.copy_(torch.from_numpy(move))
+    acc.trans[torch.from_numpy(rows * C + cols).to(dev)] = torch.from_numpy(vals.astype(np.int32)).to(dev)
+    return acc
+
+
+def _steps(heat):
+    """The largest move of each iteration (what the solve compares with eps), [max_iter]."""
+    h = heat.cpu().numpy()
+    return (h[1:] - h[:-1]).max(axis=1)
+
+
+def test_dense_solve_above_the_compact_limit(sa):
+    """9473 x 1, the smallest grid the compact form does not take: sa_xt_solve_ex's dense loop
+    (one xt_iter_kernel launch per iteration, flags read back every 8) == the same iterations
+    driven from here, bit for bit -- heatmaps, surface and count -- with convergence inside the
+    first batch of 8, inside the second, and not within max_iter (n_iter -1, the surface the
+    last iterate)."""
+    ops = sa['ops']
+    l, w, m = 9473, 1, 18
+    assert l * w == sa['_native'].SA_XT_COMPACT_MAX_C + 1
+    acc = _sparse_counts(ops, l, w, torch.device('cuda'))
+    ref_mats, ref, n = _dense_loop(sa, acc, 0.0, m)
+    d = _steps(ref)
+    assert n == -1 and d[-1] > 0 and (d[1:] < d[:-1]).all()  # eps between two steps stops there
+    for k in (5, 12):
+        eps = 0.5 * (d[k - 1] + d[k - 2])  # iteration k is the first that moves no cell by more
+        mats, heat, n = _dense_loop(sa, acc, eps, m)
+        assert n == k and torch.equal(heat[:k + 1], ref[:k + 1])
+        sol = ops.xt_solve(acc, eps=eps, max_iter=m, transition=False)
+        assert sol.n_iter == k and sol.path == 'sequential' and sol.trans_t is None
+        assert torch.equal(sol.heatmaps, heat[:k + 1])
+        assert torch.equal(sol.mats[:3], mats) and torch.equal(sol.mats[3], heat[k])
+    for mi in (10, 16):  # max_iter reached inside a batch and at the end of one
+        mats, _, heat, n, path = _solve_ex(sa, acc, 0.5 * d[-1], mi, transition=False)
+        assert n == -1 and path == 'sequential'
+        assert torch.equal(heat, ref[:mi + 1])
+        assert torch.equal(mats[:3], ref_mats) and torch.equal(mats[3], ref[mi])
+
+
+def test_sequential_compact_loop_at_a_batch_boundary(sa):
+    """The reference-order loop over the compact rows reads its flags back every 8 iterations:
+    convergence at iteration 8 (the last flag of the first read-back) and at 9 (the first of the
+    second), with max_iter exactly 8 and 9, against the same counts at max_iter 1000."""
+    rng = np.random.default_rng(1025)
+    cnt, move, gs, pm = _fit_like_rows(rng, 1025, 0.05)
+    h, n, path = _compact_solve(sa, cnt, move, gs, pm, 0.0, max_iter=12, exact=True)
+    d = (h[1:] - h[:-1]).max(axis=1)
+    assert n == -1 and path == 'sequential' and d[-1] > 0 and (d[1:] < d[:-1]).all()
+    for k in (8, 9):
+        eps = 0.5 * (d[k - 1] + d[k - 2])
+        h0, n0, p0 = _compact_solve(sa, cnt, move, gs, pm, eps, exact=True)
+        assert n0 == k and p0 == 'sequential' and np.array_equal(h0, h[:k + 1])
+        for m in (8, 9):
+            hm, nm, p = _compact_solve(sa, cnt, move, gs, pm, eps, max_iter=m, exact=True)
+            assert p == 'sequential' and nm == (k if m >= k else -1)
+            assert np.array_equal(hm, h0[:m + 1])
+
+
+@pytest.fixture(scope='module')
+def few_games(sa):
+    return sa['batch'].ActionBatch.from_columns(sa['synthetic'].spadl_games(30))
+
+
+@pytest.mark.parametrize('l,w', [(8, 6), (30, 20)])
+def test_small_grid_solve_reaching_max_iter(sa, few_games, l, w):
+    """The register solve (8 x 6) and the one-workgroup solve (30 x 20) stopped at max_iter = 2:
+    ops.xt_solve raises, sa_xt_solve_ex reports -1, sa_xt_solve_async's device count holds the
+    same -1, and both leave the same matrices and the iterates of an unstopped solve."""
+    ops = sa['ops']
+    acc = ops.xt_count(few_games, l, w)
+    with pytest.raises(RuntimeError):
+        ops.xt_solve(acc, max_iter=2)
+    mats, tt, heat, n, path = _solve_ex(sa, acc, 1e-5, 2)
+    assert n == -1 and path == 'sequential'
+    asy = ops.xt_solve_async(acc, max_iter=2)
+    assert int(asy.n_iter.item()) == n
+    assert torch.equal(asy.mats, mats) and torch.equal(asy.heatmaps[:3], heat[:3])
+    assert torch.equal(asy.trans_t, tt)
+    full = ops.xt_solve(acc)
+    assert full.n_iter > 2 and torch.equal(full.heatmaps[:3], heat) and torch.equal(mats[3], heat[2])
+    assert torch.equal(full.mats[:3], mats[:3]) and torch.equal(full.trans_t, tt)
+
+
+@pytest.mark.parametrize('l,w,path', [(8, 6, 'sequential'), (30, 20, 'sequential'), (40, 30, 'unavailable')])
+def test_solve_with_max_iter_zero(sa, few_games, l, w, path):
+    """max_iter = 0 on each solve path (register, one workgroup, compact rows): no iteration
+    runs, so the call succeeds with n_iter -1 (not converged), heatmap row 0 and the surface all
+    zero, and the matrices normalised; above the small grids the reordered solve declines."""
+    ops = sa['ops']
+    acc = ops.xt_count(few_games, l, w)
+    mats, tt, heat, n, p = _solve_ex(sa, acc, 1e-5, 0)
+    assert n == -1 and p == path
+    assert not heat.any() and not mats[3].any()
+    ref_mats, ref_tt = ops.xt_normalize(acc)
+    assert torch.equal(mats[:3], ref_mats) and torch.equal(tt, ref_tt)
+    with pytest.raises(RuntimeError):
+        ops.xt_solve(acc, max_iter=0)
