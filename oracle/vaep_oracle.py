@@ -106,6 +106,19 @@ def features(cols: Dict[str, np.ndarray], k: int, xfns: Sequence[str], atomic: b
                            ('end_y', FIELD_W)):
                 w[c] = np.where(away, ext - w[c], w[c])
         W.append(w)
+    return features_frames(W, xfns, atomic, seg_off=so)
+
+
+def features_frames(frames: Sequence[Dict[str, np.ndarray]], xfns: Sequence[str],
+                    atomic: bool = False, seg_off=None) -> List[Tuple[str, str, np.ndarray]]:
+    """Feature columns of an explicit list of k game-state frames (equal-length column dicts),
+    as the reference's module-level transformers compute them on any such list
+    (vaep/features.py:135-143, 448-539): window i of row j is row j of ``frames[i]``.  No flip
+    is applied; ``goalscore`` reads frame 0 alone, as one segment unless ``seg_off`` is given
+    (:func:`features` passes its own)."""
+    W = list(frames)
+    k = len(W)
+    so = segments_of(len(W[0]['type_id']), seg_off)
     out: List[Tuple[str, str, np.ndarray]] = []
     types = ATOMIC_TYPES if atomic else SPADL_TYPES
     for x in xfns:
@@ -190,7 +203,7 @@ def features(cols: Dict[str, np.ndarray], k: int, xfns: Sequence[str], atomic: b
                 out += [(f'dx_a0{i}', 'f', dx), (f'dy_a0{i}', 'f', dy),
                         (f'mov_a0{i}', 'f', np.sqrt(dx ** 2 + dy ** 2))]
         elif x == 'goalscore':
-            out += goalscore(cols, atomic, so)
+            out += goalscore(a0, atomic, so)
     return out
 
 

@@ -66,6 +66,29 @@ def test_atomic_oracle(name):
             np.testing.assert_allclose(v[c], g[f'{c}_{tag}'], rtol=1e-6, atol=1e-12)
 
 
+@pytest.mark.parametrize('atomic', [False, True])
+def test_explicit_frames_oracle(atomic):
+    """features_frames on frames that are not shifts of one another == the reference's own
+    module-level transformers on them (tests/golden/make_golden_explicit.py), as built and after
+    the reference's play_left_to_right; and features() on one frame still equals its emitter."""
+    import window_cases as wc
+    g = wc.explicit_golden(atomic)
+    xfns = vo.ATOMIC_DEFAULT if atomic else vo.SPADL_DEFAULT
+    for tag in ('plain', 'ltr'):
+        frames = wc.frame_cols(wc.golden_frames(g, tag, atomic), atomic)
+        assert len(frames) == 4 and len(frames[0]['type_id']) == 70
+        got = vo.features_frames(frames, xfns, atomic)
+        _check_features(got, {f'k4_{key[len(tag) + 1:]}': v for key, v in g.items()
+                              if key.startswith(tag + '_')}, 4)
+    t = [f['time_seconds'] for f in frames]
+    assert (t[1] != t[0][np.maximum(np.arange(70) - 1, 0)]).mean() > 0.9  # no shifted copies
+    a = vo.features(frames[0], 1, xfns, atomic=atomic)
+    b = vo.features_frames(frames[:1], xfns, atomic)
+    assert [c[:2] for c in a] == [c[:2] for c in b]
+    for x, y in zip(a, b):
+        np.testing.assert_array_equal(x[2], y[2])
+
+
 @pytest.mark.parametrize('name', cases('xt'))
 def test_xt_oracle(name):
     g = load('xt', name)
