@@ -868,6 +868,23 @@ int sa_auc_count(const uint8_t* y, const void* p, int32_t f32, int64_t n, const 
  *   [n_features] (NULL: all): a feature whose byte is 0 is no split candidate (best_cut = -1).
  * sa_boost_row_keys: keys[j] = fm(game_id[j]) + action_id[j], wrapping.
  *
+ * The level exchange of a fit whose rows are split over ranks (contract item 18): the used entries
+ * of a level's histogram as one contiguous payload of (G, H) pairs that the ranks sum with one
+ * int64 all-reduce.  pairs [n_pair_bool + n_pair_num] (int32) lists one node's payload pairs as
+ * dense pair offsets feature * 256 + bin: bin 1 of every bool feature in model order, then of
+ * every numeric feature in model order its bins 0 .. m (m = its number of cuts) and bin 255.
+ * payload, in int64 words: at level 0 the root's G, H; then for every node its n_pair_bool bool
+ * pairs; then for every node its n_pair_num numeric pairs -- 2 * [node0 == 0] + 2 * n_nodes *
+ * (n_pair_bool + n_pair_num) words.  hist, tree and payload are 16-byte aligned.
+ * sa_boost_hist_pack: payload = those entries of hist (at level 0 tree[0].G / .H first: after
+ *   sa_boost_hist_bits(add_totals = 1) this rank's totals).  A bool feature's bin 0 does not
+ *   travel: past level 0 a rank's bin 0 is "global total minus local bin 1" and must not be summed.
+ * sa_boost_hist_unpack: the inverse -- hist's listed entries = payload (at level 0 tree[0].G / .H
+ *   = its first pair) -- and then bin 0 of every bool feature bit_feat[c], c < n_bool (the list the
+ *   level's sa_boost_hist_bits call got: a round's column sample), = tree[node0 + k].G / .H minus
+ *   bin 1.  Entries of hist outside the payload keep their values.
+ * Both are index-mapped copies: one thread per pair, one 16-byte load and one 16-byte store.
+ *
  * Launch shapes.  sa_boost_hist_bins: feature groups of fg = SA_BOOST_FEATURE_GROUP features,
  *   halved while fg * n_nodes > 32; grid (gx, groups), gx = max(SA_BOOST_BINS_MIN_GRID_X,
  *   SA_BOOST_BINS_WG_PER_CU * compute units / groups) capped at the row steps of
@@ -939,6 +956,13 @@ int sa_boost_split_ex(const int64_t* hist, const int32_t* cut_start, const float
                       int32_t* best_cut, sa_boost_node* tree, void* stream);
 int sa_boost_row_keys(const int64_t* game_id, const int64_t* action_id, int64_t n, int64_t* keys,
                       void* stream);
+int sa_boost_hist_pack(const int64_t* hist, const sa_boost_node* tree, const int32_t* pairs,
+                       int32_t n_pair_bool, int32_t n_pair_num, int32_t node0, int32_t n_nodes,
+                       int32_t n_features, int64_t* payload, void* stream);
+int sa_boost_hist_unpack(const int64_t* payload, const int32_t* pairs, int32_t n_pair_bool,
+                         int32_t n_pair_num, const int32_t* bit_feat, int32_t n_bool, int32_t node0,
+                         int32_t n_nodes, int32_t n_features, int64_t* hist, sa_boost_node* tree,
+                         void* stream);
 
 /* ---- runtime ------------------------------------------------------------------ */
 int sa_abi_version(void);

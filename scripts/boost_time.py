@@ -30,10 +30,20 @@ ratio to the default's; ``--parent-json FILE`` (this script's ``--out`` file fro
 commit, run on the same device in the same session) puts the parent's default figures beside
 the first.
 
+``--sharded-record`` writes the record of the sharded fit (``profiles/boost_fit_sharded.json``),
+measured with ONE rank through RCCL (backend nccl, world 1 -- nothing about more ranks can be
+measured on one device): `--reps` default ``fit_batch`` calls without a process group (with
+``--parent-json`` held against the parent commit's own runs: no exchange code may run without a
+group; ``--self-json``: this commit's ``--out`` file of the default mode from the same session, the
+like-for-like figure), the same calls through ``process_group=``, and from one instrumented sharded fit per learner
+the cost of pack + all-reduce + unpack per level and the payload bytes per tree against the dense
+level histograms they replace.
+
     python scripts/boost_time.py [--games 1000] [--reps 3] [--val-size 0.25]
         [--early-stopping-rounds 10] [--eval-metric auc|logloss] [--sklearn] [--out FILE]
         [--subsample S] [--colsample-bytree C] [--reg-alpha A] [--scale-pos-weight P]
         [--random-state R] [--max-weight W] [--sampling-record [--parent-json FILE]]
+        [--sharded-record [--parent-json FILE] [--self-json FILE]]
 """
 from __future__ import annotations
 
@@ -117,6 +127,90 @@ def sampling_record(args, games, actions, data, lb) -> dict:
     return out
 
 
+EXCHANGE_FAMILIES = ('pack', 'allreduce', 'unpack')
+
+
+def sharded_record(args, games, actions, data, lb) -> dict:
+    """``--sharded-record``: the default fit with and without a one-rank RCCL process group."""
+    import torch.distributed as dist
+
+    def walls_of(group):
+        walls = []
+        for _ in range(args.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            m = VAEP().fit_batch(games, actions, process_group=group)
+            torch.cuda.synchronize()
+            walls.append(round((time.perf_counter() - t0) * 1e3, 1))
+        return {'fit_batch_wall_ms': walls, 'fit_batch_wall_ms_median': statistics.median(walls),
+                'fit_batch_wall_ms_spread': round(max(walls) - min(walls), 1)}, \
+            {c: json.dumps(m._VAEP__models[c].to_xgboost_json()) for c in ('scores', 'concedes')}
+
+    def families_of(group):
+        fams, levels = {}, 0
+        for col in ('scores', 'concedes'):  # one instrumented fit per learner
+            clf = boost.make_classifier({})
+            clf._events = []
+            clf.fit_binned(data, getattr(lb, col), process_group=group)
+            torch.cuda.synchronize()
+            for fam, a, b in clf._events:
+                fams[fam] = fams.get(fam, 0.0) + a.elapsed_time(b)
+            levels += sum(1 for fam, _, _ in clf._events if fam == 'allreduce')
+            clf._events = None
+        return fams, levels
+
+    out, models = {}, {}
+    # the default call first, in a process that has not yet started RCCL and, as in the default mode, after the
+    # instrumented fits: what the parent commit's run measures
+    plain_fams, _ = families_of(None)
+    out['unsharded'], models['unsharded'] = walls_of(None)
+    for k, v in (('MASTER_ADDR', '127.0.0.1'), ('MASTER_PORT', '29541'), ('RANK', '0'), ('WORLD_SIZE', '1')):
+        os.environ.setdefault(k, v)
+    dist.init_process_group('nccl', device_id=torch.device('cuda', 0))
+    pg = dist.group.WORLD
+    out.update(backend=dist.get_backend(pg), world=dist.get_world_size(pg),
+               note='one rank: every collective is an identity; nothing here says what N > 1 ranks cost')
+    VAEP().fit_batch(games, actions, process_group=pg)  # warm-up (RCCL's setup, the payload buffers)
+    out['sharded_world1'], models['sharded_world1'] = walls_of(pg)
+    out['unsharded_after_rccl_init'], _ = walls_of(None)
+    out['models_equal'] = models['unsharded'] == models['sharded_world1']
+    fams, levels = families_of(pg)
+    exchange = sum(fams.get(f, 0.0) for f in EXCHANGE_FAMILIES)
+    lay, D = boost._exchange(data)[0], int(boost.DEFAULTS['max_depth'])
+    payload = 8 * sum(lay.words(2 ** level) for level in range(D))
+    dense = 16 * 256 * data.n_features * sum(2 ** level for level in range(D))
+    out['instrumented'] = {
+        'family_sum_ms_both_learners': {f: round(v, 2) for f, v in fams.items()},
+        'unsharded_family_sum_ms_both_learners': {f: round(v, 2) for f, v in plain_fams.items()},
+        'level_collectives_both_learners': levels,
+        'exchange_ms_per_level': {f: round(fams.get(f, 0.0) / levels, 4) for f in EXCHANGE_FAMILIES},
+        'exchange_ms_per_level_total': round(exchange / levels, 4),
+        'exchange_share_of_kernel_time': round(exchange / sum(fams.values()), 4)}
+    out['payload'] = {'pairs_per_node': lay.n_bool + lay.n_num, 'bool_pairs': lay.n_bool, 'numeric_pairs': lay.n_num,
+                      'payload_bytes_per_tree': payload, 'dense_bytes_per_tree': dense,
+                      'payload_over_dense': round(payload / dense, 4),
+                      'payload_bytes_per_level': [8 * lay.words(2 ** level) for level in range(D)]}
+    if args.parent_json:
+        with open(args.parent_json) as f:
+            parent = json.load(f)
+        pw = parent['fit_batch_wall_ms']
+        out['parent_commit_unsharded'] = {'fit_batch_wall_ms': pw, 'fit_batch_wall_ms_median': statistics.median(pw),
+                                          'fit_batch_wall_ms_spread': round(max(pw) - min(pw), 1),
+                                          'device': parent.get('device'), 'rows': parent.get('rows')}
+        mine = out['unsharded']
+        if args.self_json:  # this commit's own default-mode run: the parent's procedure, call for call
+            with open(args.self_json) as f:
+                sw = json.load(f)['fit_batch_wall_ms']
+            mine = out['this_commit_default_mode'] = {
+                'fit_batch_wall_ms': sw, 'fit_batch_wall_ms_median': statistics.median(sw),
+                'fit_batch_wall_ms_spread': round(max(sw) - min(sw), 1)}
+        med = mine['fit_batch_wall_ms_median']
+        out['unsharded_median_within_parent_runs'] = bool(min(pw) <= med <= max(pw))
+        out['unsharded_minus_parent_wall_ms'] = round(med - statistics.median(pw), 1)
+    dist.destroy_process_group()
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument('--games', type=int, default=1000)
@@ -134,6 +228,8 @@ def main() -> None:
     ap.add_argument('--max-weight', type=float, default=0.0)
     ap.add_argument('--sampling-record', action='store_true')
     ap.add_argument('--parent-json', default='')
+    ap.add_argument('--sharded-record', action='store_true')
+    ap.add_argument('--self-json', default='')
     args = ap.parse_args()
     tp = {k: v for k, v in dict(subsample=args.subsample, colsample_bytree=args.colsample_bytree,
                                 reg_alpha=args.reg_alpha, scale_pos_weight=args.scale_pos_weight,
@@ -181,8 +277,11 @@ def main() -> None:
     res['bin_GBs'] = round(n * (8 * f_num + f_num) / e0.elapsed_time(e1) * 1e-6, 1)
     bytes_level = {'hist_bits': n * (n_bool / 8 + 9), 'hist_bins': n * (f_num + 9)}
     res['bytes_per_row_per_level'] = {'bitmaps': n_bool / 8, 'bins': f_num, 'gradients_and_node': 9}
+    if args.sharded_record:
+        res['sharded'] = sharded_record(args, games, actions, data, lb)
     if args.sampling_record:
         res['configurations'] = sampling_record(args, games, actions, data, lb)
+    if args.sharded_record or args.sampling_record:
         line = json.dumps(res)
         if args.out:
             with open(args.out, 'w') as f:

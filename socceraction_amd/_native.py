@@ -294,6 +294,10 @@ _SIGNATURES = {
                                          ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                          ctypes.c_double, ctypes.c_double, ctypes.c_int32, _p, _p, _p, _p, _p]),
     'sa_boost_row_keys': (ctypes.c_int, [_p, _p, ctypes.c_int64, _p, _p]),
+    'sa_boost_hist_pack': (ctypes.c_int, [_p, _p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                          ctypes.c_int32, _p, _p]),
+    'sa_boost_hist_unpack': (ctypes.c_int, [_p, _p, ctypes.c_int32, ctypes.c_int32, _p, ctypes.c_int32,
+                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p, _p]),
     'sa_device_alloc': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
     'sa_device_free': (ctypes.c_int, [_p]),
     'sa_copy2d_async': (ctypes.c_int, [_p, ctypes.c_int64, _p, ctypes.c_int64, ctypes.c_int64,

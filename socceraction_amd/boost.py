@@ -27,6 +27,13 @@ row key or feature)``, so a tuned model is as reproducible as a plain one.  The 
 are :class:`TunedGBTClassifier`'s; :class:`DeviceGBTClassifier` keeps its seven.  No weighted
 evaluation, bylevel / bynode column sampling, categorical splits or learned default directions
 (missing values always go right).
+
+The sharded fit (contract items 18-22; ``tests/test_gpu_boost_shard.py``): with ``process_group=``
+every rank of a ``torch.distributed`` group holds a shard of the rows; the cuts come from the
+ranks' joint sample, each level's histogram is joined by one int64 all-reduce of its used entries
+(:func:`exchange_layout`, ``sa_boost_hist_pack`` / ``sa_boost_hist_unpack``,
+``shard.allreduce_boost_level``), and every rank ends with the trees of the single-device fit of
+the ranks' rows in rank order, byte for byte.  Without a process group none of it runs.
 """
 from __future__ import annotations
 
@@ -120,27 +127,116 @@ def _kind(col: np.ndarray) -> str:
     return 'b' if col.dtype == np.bool_ else ('i' if col.dtype.kind in 'iu' else 'f')
 
 
-def make_cuts(data, rows=None) -> List[np.ndarray]:
+def shard_sample_rows(counts: Sequence[int], rank: int) -> np.ndarray:
+    """The part of the global cut sample that falls to ``rank`` (contract item 19): the ranks'
+    training rows, ``counts[q]`` of rank q, are numbered rank 0's first, then rank 1's, ...; the
+    sample is ``sample_rows(sum(counts))``; returned are its rows inside rank ``rank``'s slice as
+    indices into that rank's own training rows, ascending.  The ranks' parts, concatenated in rank
+    order, are the global sample."""
+    counts = [int(c) for c in counts]
+    off = sum(counts[:rank])
+    idx = sample_rows(sum(counts))
+    return idx[(idx >= off) & (idx < off + counts[rank])] - off
+
+
+def _gather_records(group, dev, record) -> np.ndarray:
+    """Every rank's float64 ``record`` (equal lengths) as ``[world, len]`` on the host: one
+    all-gather (``shard._all_gather``), the exchange behind every agreement of a sharded fit."""
+    import torch
+    import torch.distributed as dist
+
+    from . import shard
+    rec = torch.from_numpy(np.asarray(record, np.float64).ravel().copy()).to(dev)
+    out = torch.empty(dist.get_world_size(group) * rec.numel(), dtype=torch.float64, device=dev)
+    shard._all_gather(out, rec, group=group)
+    return out.cpu().numpy().reshape(dist.get_world_size(group), -1)
+
+
+def _group_device(group):
+    """Where a host-side exchange stages its tensors: the current GPU under RCCL, else the host."""
+    import torch
+
+    from . import shard
+    return torch.device('cuda', torch.cuda.current_device()) if shard._on_device(group) else torch.device('cpu')
+
+
+def agree(group, dev, err: Optional[Exception], what: str = 'fit') -> None:
+    """One rank's ``ValueError`` raised on every rank (contract item 22): every rank calls this
+    with its pending error or None; the failing rank re-raises its own, the others a ``ValueError``
+    naming it.  No rank goes on to a collective another rank will not reach."""
+    import torch.distributed as dist
+    flags = _gather_records(group, dev, [0.0 if err is None else 1.0])[:, 0]
+    if err is not None:
+        raise err
+    if flags.any():
+        raise ValueError(f'sharded {what}: rank {int(np.flatnonzero(flags)[0])} of the process group refused its '
+                         f'arguments (this is rank {dist.get_rank(group)})')
+
+
+def _gather_sample(group, dev, local, counts: Sequence[int]) -> np.ndarray:
+    """The ranks' float32 sample parts ``[S_r, C]`` (a device or host tensor on ``dev``) as the one
+    host array ``[S, C]`` every rank computes its cuts from: padded to the largest part, ONE
+    all-gather, the true parts concatenated in rank order."""
+    import torch
+
+    from . import shard
+    W = len(counts)
+    sizes = [len(shard_sample_rows(counts, q)) for q in range(W)]
+    C, top = local.shape[1], max(max(sizes), 1)
+    send = torch.zeros((top, C), dtype=torch.float32, device=dev)
+    send[:local.shape[0]] = local
+    recv = torch.empty((W, top, C), dtype=torch.float32, device=dev)
+    shard._all_gather(recv.reshape(-1), send.reshape(-1), group=group)
+    host = recv.cpu().numpy()
+    return np.concatenate([host[q, :sizes[q]] for q in range(W)], 0)
+
+
+def _train_counts(group, dev, count: int) -> List[int]:
+    return [int(c) for c in _gather_records(group, dev, [float(count)])[:, 0]]
+
+
+def make_cuts(data, rows=None, process_group=None) -> List[np.ndarray]:
     """Every feature's cuts (model order) from the deterministic row sample of ``data``: device
     feature blocks (``ops.FeatureBlocks``; the sample is gathered on the device and copied back
     once) or a host frame / 2-D array.  ``rows``: the training rows (indices) the sample is
-    taken from, default all."""
+    taken from, default all.  With ``process_group`` every rank passes its own shard of the rows
+    and all get the cuts of the concatenated table (contract item 19): an all-gather of the row
+    counts, then one of the ranks' parts of the global sample (:func:`shard_sample_rows`)."""
     if hasattr(data, 'plan'):
-        return _make_cuts_blocks(data, rows)
+        return _make_cuts_blocks(data, rows, process_group)
     names, cols = _host_columns(data)
     n = len(cols[0]) if cols else 0
     sel = None if rows is None else np.asarray(rows, np.int64)
+    if process_group is not None:
+        import torch
+        import torch.distributed as dist
+        dev = _group_device(process_group)
+        counts = _train_counts(process_group, dev, n if sel is None else len(sel))
+        idx = shard_sample_rows(counts, dist.get_rank(process_group))
+        if sel is not None:
+            idx = sel[idx]
+        local = np.zeros((len(idx), len(cols)), np.float32)
+        for j, c in enumerate(cols):
+            local[:, j] = cast32(c[idx])
+        host = _gather_sample(process_group, dev, torch.from_numpy(local).to(dev), counts)
+        return [cuts_from_sample(host[:, j], _kind(c) == 'b') for j, c in enumerate(cols)]
     idx = sample_rows(n if sel is None else len(sel))
     if sel is not None:
         idx = sel[idx]
     return [cuts_from_sample(c[idx], _kind(c) == 'b') for c in cols]
 
 
-def _make_cuts_blocks(blocks, rows=None) -> List[np.ndarray]:
+def _make_cuts_blocks(blocks, rows=None, group=None) -> List[np.ndarray]:
     import torch
     dev = blocks.device
     sel = None if rows is None else torch.as_tensor(rows, device=dev).to(torch.int64)
-    idx = torch.from_numpy(sample_rows(blocks.n if sel is None else sel.numel())).to(dev)
+    n_train = blocks.n if sel is None else sel.numel()
+    if group is None:
+        idx = torch.from_numpy(sample_rows(n_train)).to(dev)
+    else:
+        import torch.distributed as dist
+        counts = _train_counts(group, dev, n_train)
+        idx = torch.from_numpy(shard_sample_rows(counts, dist.get_rank(group))).to(dev)
     if sel is not None:
         idx = sel[idx]
     parts = []
@@ -151,7 +247,10 @@ def _make_cuts_blocks(blocks, rows=None) -> List[np.ndarray]:
             v = v.to(torch.float64)
         parts.append(v.to(torch.float32))
     nf = parts[0].shape[1]
-    host = torch.cat(parts, 1).cpu().numpy() if len(idx) else np.zeros((0, nf + parts[1].shape[1]), np.float32)
+    if group is not None:
+        host = _gather_sample(group, dev, torch.cat(parts, 1), counts)
+    else:
+        host = torch.cat(parts, 1).cpu().numpy() if len(idx) else np.zeros((0, nf + parts[1].shape[1]), np.float32)
     out = []
     for _, kind, col in blocks.plan.order:
         if kind == 'b':
@@ -293,6 +392,58 @@ def _flat_cuts(cuts: Sequence[np.ndarray]):
     return cut_start, np.concatenate(list(cuts) + [np.zeros(1, np.float32)]).astype(np.float32)
 
 
+class ExchangeLayout(namedtuple('ExchangeLayout', 'pairs n_bool n_num n_features')):
+    """One node's payload pairs of the level exchange (:func:`exchange_layout`): ``pairs`` (int32)
+    = ``feature * 256 + bin`` of its ``n_bool`` bool pairs, then of its ``n_num`` numeric pairs."""
+
+    def words(self, n_nodes: int) -> int:
+        """The payload's length in int64 words for a level of ``n_nodes`` nodes."""
+        return 2 * int(n_nodes == 1) + 2 * int(n_nodes) * (self.n_bool + self.n_num)
+
+    def dense_pairs(self, n_nodes: int) -> np.ndarray:
+        """The dense pair index ``(node * F + feature) * 256 + bin`` of every payload pair after
+        the level-0 head, in payload order (int64): every node's bool pairs, then every node's
+        numeric pairs."""
+        base = np.arange(int(n_nodes), dtype=np.int64)[:, None] * (self.n_features * 256)
+        p = self.pairs.astype(np.int64)
+        return np.concatenate([(base + p[None, :self.n_bool]).ravel(), (base + p[None, self.n_bool:]).ravel()])
+
+
+def exchange_layout(cut_start, is_bool) -> ExchangeLayout:
+    """The layout of the level exchange (contract item 18), from the features' cut counts and
+    kinds alone, so every rank derives the same: of a node's dense ``[F, 256]`` pairs the payload
+    carries bin 1 of every bool feature (model order; bin 0 is rebuilt from the node total after
+    the sum) and then, of every numeric feature with m cuts (model order), bins ``0 .. m`` and the
+    missing bin 255."""
+    cut_start = np.asarray(cut_start, np.int64).ravel()
+    is_bool = np.asarray(is_bool, bool).ravel()
+    F = len(is_bool)
+    if len(cut_start) != F + 1:
+        raise ValueError('cut_start has one entry per feature and one more')
+    m = np.diff(cut_start)
+    if (m < 0).any() or (m > MAX_CUTS).any():
+        raise ValueError(f'a feature has 0 .. {MAX_CUTS} cuts')
+    out = [f * 256 + 1 for f in range(F) if is_bool[f]]
+    n_bool = len(out)
+    for f in range(F):
+        if not is_bool[f]:
+            out.extend(range(f * 256, f * 256 + int(m[f]) + 1))
+            out.append(f * 256 + MISSING_BIN)
+    return ExchangeLayout(np.array(out, np.int32), n_bool, len(out) - n_bool, F)
+
+
+def _exchange(data: 'BinnedData'):
+    """``data``'s :class:`ExchangeLayout` and its pair table on the device, built once per table."""
+    import torch
+    if 'exchange' not in data.dev:
+        is_bool = np.zeros(data.n_features, bool)
+        is_bool[data.bit_feat] = True
+        lay = exchange_layout(_flat_cuts(data.cuts)[0], is_bool)
+        table = torch.from_numpy(np.concatenate([lay.pairs, np.zeros(1, np.int32)])).to(data.device)  # (never empty)
+        data.dev['exchange'] = (lay, table)
+    return data.dev['exchange']
+
+
 def _padded_block(cols, n: int, ld: int, dtype) -> np.ndarray:
     """Host columns as one zero-padded ``[1, C, ld]`` block of ``dtype``."""
     h = np.zeros((1, len(cols), ld), dtype)
@@ -344,29 +495,31 @@ def _bin(names, kinds_cols, bits, f_blk, i_blk, f32: bool, n: int, cuts) -> Binn
                       fmap, d)
 
 
-def bin_blocks(blocks, cuts: Optional[Sequence[np.ndarray]] = None, rows=None) -> BinnedData:
+def bin_blocks(blocks, cuts: Optional[Sequence[np.ndarray]] = None, rows=None, process_group=None) -> BinnedData:
     """Bin device feature blocks (``ops.features(..., bool_bits=True)``; float64 / int64 or
     float32 numeric blocks): ``sa_boost_bin`` for the numeric features, the bitmaps as they are.
-    ``cuts``: explicit cut lists (model order), default :func:`make_cuts` on ``rows``."""
+    ``cuts``: explicit cut lists (model order), default :func:`make_cuts` on ``rows`` (with
+    ``process_group``: of all ranks' rows)."""
     plan = blocks.plan
     if plan.n_bool and blocks.bool_bits is None:
         raise ValueError('the bool features must come as bitmaps (ops.features(..., bool_bits=True))')
     if cuts is None:
-        cuts = make_cuts(blocks, rows)
+        cuts = make_cuts(blocks, rows, process_group)
     kc = [(kind, col) for _, kind, col in plan.order]
     return _bin(list(plan.names), kc, blocks.bool_bits, blocks.f64_block, blocks.i64_block, blocks.num32,
                 blocks.n, cuts)
 
 
-def bin_host(X, cuts: Optional[Sequence[np.ndarray]] = None, rows=None, device=None) -> BinnedData:
+def bin_host(X, cuts: Optional[Sequence[np.ndarray]] = None, rows=None, device=None, process_group=None) -> BinnedData:
     """Upload a host frame / 2-D array -- bool columns as bitmaps, float and integer columns as
-    float64 / int64 blocks -- and bin it with the same kernel."""
+    float64 / int64 blocks -- and bin it with the same kernel (``process_group``: as in
+    :func:`bin_blocks`)."""
     import torch
     names, cols = _host_columns(X)
     n = len(cols[0]) if cols else 0
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     if cuts is None:
-        cuts = make_cuts(X, rows)
+        cuts = make_cuts(X, rows, process_group)
     ld = _ld(n)
     kinds = [_kind(c) for c in cols]
     kc, per = [], {'b': [], 'f': [], 'i': []}
@@ -553,6 +706,55 @@ def histograms(data: BinnedData, gq, hq, node, n_nodes: int, return_totals: bool
         return hist
     tab = tree.cpu().numpy().view(NODE_DTYPE).reshape(-1)[node0:node0 + n_nodes]
     return hist, np.stack([tab['G'], tab['H']], 1)
+
+
+def level_histogram(data: BinnedData, gq, hq, node, n_nodes: int, totals=None):
+    """One rank's part of a level, as the sharded fit forms it before the exchange: ``(hist, tree)``
+    on the device -- the dense histogram of this table's rows and the round's node table.
+    ``totals`` None: the level's node totals are summed from the rows (level 0 of a fit);
+    ``totals [n_nodes, 2]``: they are preset (past level 0 they are the global ones) and every bool
+    feature's bin 0 is derived from them."""
+    import torch
+    node0 = _level(n_nodes)
+    dev = data.device
+    nd = node.to(torch.int64)
+    heap = _pad(torch.where(nd == NO_NODE, nd, nd + node0).to(torch.uint8), data.ld, torch.uint8, NO_NODE)
+    gq, hq = _pad(gq, data.ld, torch.int32), _pad(hq, data.ld, torch.int32)
+    hist = torch.zeros((n_nodes, data.n_features, 256, 2), dtype=torch.int64, device=dev)
+    tab = np.zeros(4 * n_nodes, NODE_DTYPE)
+    if totals is not None:
+        tot = np.asarray(totals, np.int64).reshape(n_nodes, 2)
+        tab['G'][node0:node0 + n_nodes], tab['H'][node0:node0 + n_nodes] = tot[:, 0], tot[:, 1]
+    tree = torch.from_numpy(tab.view(np.uint8).reshape(4 * n_nodes, -1).copy()).to(dev)
+    _hist(_run, _stream(), data, gq, hq, heap, n_nodes, hist, tree, totals is None)
+    return hist, tree
+
+
+def hist_pack(data: BinnedData, hist, tree, n_nodes: int, out=None, launch=None):
+    """``sa_boost_hist_pack``: the level's exchange payload (int64 device vector,
+    :meth:`ExchangeLayout.words` long) of the dense ``hist [n_nodes, F, 256, 2]`` and, at level 0,
+    the root totals of the device node table ``tree``."""
+    import torch
+    lay, table = _exchange(data)
+    if out is None:
+        out = torch.empty(max(lay.words(n_nodes), 2), dtype=torch.int64, device=data.device)
+    (launch or _run)('pack', _native.lib().sa_boost_hist_pack, hist.data_ptr(), tree.data_ptr(), table.data_ptr(),
+                     lay.n_bool, lay.n_num, _level(n_nodes), n_nodes, data.n_features, out.data_ptr(), _stream())
+    return out[:lay.words(n_nodes)]
+
+
+def hist_unpack(data: BinnedData, payload, hist, tree, n_nodes: int, bit_feat=None, n_bool: Optional[int] = None,
+                launch=None) -> None:
+    """``sa_boost_hist_unpack``: the (summed) ``payload`` scattered into ``hist`` in place, at level 0
+    its first pair stored as the root totals of ``tree``, then bin 0 of the listed bool features
+    (device int32 list ``bit_feat`` with ``n_bool`` entries; default every bool feature) rebuilt
+    from the node totals."""
+    lay, table = _exchange(data)
+    if bit_feat is None:
+        bit_feat, n_bool = data.dev['bit_feat'], len(data.bit_feat)
+    (launch or _run)('unpack', _native.lib().sa_boost_hist_unpack, payload.data_ptr(), table.data_ptr(), lay.n_bool,
+                     lay.n_num, bit_feat.data_ptr() if n_bool else None, int(n_bool), _level(n_nodes), n_nodes,
+                     data.n_features, hist.data_ptr(), tree.data_ptr(), _stream())
 
 
 def best_splits(hist, totals, cuts: Sequence[np.ndarray], reg_lambda: float = 1.0, min_child_weight: float = 1.0,
@@ -861,9 +1063,11 @@ def make_classifier(params: Dict[str, Any], **kw) -> 'DeviceGBTClassifier':
 
 # The evaluation state of a fit (DeviceGBTClassifier._eval_setup fills it) and the state of one
 # fit_binned between its parts (._prepare fills it: `tu` / `columns` None: plain; `ev` None: no evaluation rows)
-_Eval = make_dataclass('_Eval', 'idx n n_pos minority m y margin p table P keys cursor'.split())
-_Fit = make_dataclass('_Fit', 'data y mask tu columns T D stream params margin gq hq node p P Mrec trees hist bg bc ev'
-                      .split())
+_Eval = make_dataclass('_Eval', 'idx n n_pos minority m y margin p table P keys cursor total total_pos'.split())
+_Fit = make_dataclass('_Fit', 'data y mask tu columns T D stream params margin gq hq node p P Mrec trees hist bg bc ev '
+                              'group pay'.split())
+# (`total` / `total_pos`: the evaluation rows and their positives over all ranks -- without a process
+# group `n` / `n_pos`; `group` / `pay`: the process group of a sharded fit and its level payload buffer)
 
 
 class DeviceGBTClassifier:
@@ -948,9 +1152,29 @@ class DeviceGBTClassifier:
             raise ValueError('eval_rows must be inside the table')
         if n_pos == 0 or n_pos == k:
             raise ValueError('Only one class present in y. The AUROC is not defined in that case.')
+        return self._eval_state(data, y, idx, int(n_pos), T, k, int(n_pos))
+
+    def _eval_local(self, data: BinnedData, y, eval_rows):
+        """A rank's part of the evaluation rows in a sharded fit (contract item 21): ``(idx, n_pos)``
+        after the rank's one host read; the class and size checks are made on the ranks' sums."""
+        import torch
+        n = data.n
+        idx = _row_list(eval_rows, n, data.device)
+        if not idx.numel():
+            return idx, 0
+        inside = idx.clamp(0, max(n - 1, 0))
+        lo, hi, n_pos = torch.stack([idx.min(), idx.max(), (y[inside] != 0).sum()]).cpu().tolist()
+        if lo < 0 or hi >= n:
+            raise ValueError('eval_rows must be inside the table')
+        return idx, int(n_pos)
+
+    def _eval_state(self, data: BinnedData, y, idx, n_pos: int, T: int, total: int, total_pos: int) -> '_Eval':
+        import torch
+        dev, k = data.device, int(idx.numel())
         minority, auc = int(n_pos <= k - n_pos), self.eval_metric == 'auc'
         m = int(n_pos) if minority else k - int(n_pos)
         return _Eval(idx=idx, n=k, n_pos=int(n_pos), minority=minority, m=m, y=y[idx].contiguous(),
+                     total=total, total_pos=total_pos,
                      margin=torch.full((k,), float(base_margin(self.base_score)), dtype=torch.float32, device=dev),
                      p=torch.empty(k, dtype=torch.float32, device=dev),
                      table=torch.zeros((max(T, 1), 10), dtype=torch.int64, device=dev),
@@ -964,6 +1188,8 @@ class DeviceGBTClassifier:
         import torch
         lib, run = _native.lib(), self._launch
         k, y = ev.n, ev.y
+        if k == 0:  # a rank of a sharded fit without evaluation rows: its sums stay zero
+            return
         p = ev.P[t] if ev.P is not None else ev.p
         _apply(data, tree, int(self.max_depth), ev.idx, k, ev.margin, p, run)
         row = ev.table[t]
@@ -978,12 +1204,17 @@ class DeviceGBTClassifier:
         run('metric', lib.sa_auc_count, y.data_ptr(), p.data_ptr(), 1, k, keys.data_ptr(), m, mino,
             row[9:10].data_ptr(), st)
 
-    def _eval_series(self, ev: '_Eval', rounds: int) -> List[int]:
-        """One host read of the metric table's first ``rounds`` rows: the integer series."""
+    def _eval_series(self, ev: '_Eval', rounds: int, group=None) -> List[int]:
+        """One host read of the metric table's first ``rounds`` rows: the integer series.  With a
+        process group the rows are first summed over the ranks (``shard.allreduce_boost_eval``)."""
         if rounds <= 0:
             return []
         from .ops import BinaryMetrics
-        h = ev.table[:rounds].cpu().tolist()
+        table = ev.table[:rounds]
+        if group is not None:
+            from . import shard
+            table = self._timed('allreduce', lambda: shard.allreduce_boost_eval(table, group))
+        h = table.cpu().tolist()
         err = 0
         for r in h:
             err |= r[8] & 0xFFFFFFFF
@@ -1007,13 +1238,96 @@ class DeviceGBTClassifier:
         mx, mn, fin = torch.stack([we.max(), we.min(), torch.isfinite(we).all().to(torch.float32)]).cpu().tolist()
         return _check_weight_range(mx, mn, bool(fin))
 
-    def _prepare(self, data: BinnedData, y_dev, rows, eval_rows, sample_weight, row_keys) -> '_Fit':
-        """A fit's state before round 0, in this order: labels, row mask, weights and their shift
-        (a weighted fit's one host read), row keys, column samples, buffers, evaluation state (one
-        host read).  Every validation error is raised here, before the first training launch."""
+    def _weight_stats(self, wd, y, mask, n: int):
+        """A rank's part of :meth:`_weight_shift` in a sharded fit (contract item 20): ``(max, min,
+        finite, count)`` of its training rows' effective weights (one host read); a rank without
+        training rows gives ``(-inf, inf, 1, 0)``."""
         import torch
-        dev, n, ld, F = data.device, data.n, data.ld, data.n_features
-        T, D = int(self.n_estimators), int(self.max_depth)
+        one = torch.ones((), dtype=torch.float32, device=y.device)
+        we = torch.where(y[:n] != 0, one * float(np.float32(float(self.scale_pos_weight))), one)
+        if wd is not None:
+            we = wd[:n] * we
+        if mask is not None:
+            we = we[mask[:n] != 0]
+        if not we.numel():
+            return -math.inf, math.inf, 1.0, 0.0
+        mx, mn, fin = torch.stack([we.max(), we.min(), torch.isfinite(we).all().to(torch.float32)]).cpu().tolist()
+        return mx, mn, fin, float(we.numel())
+
+    def _prepare_sharded(self, data: BinnedData, y_dev, rows, eval_rows, sample_weight, row_keys, group,
+                         pending: Optional[Exception]) -> '_Fit':
+        """:meth:`_prepare` for a rank of a sharded fit (contract items 20-22).  What can be checked
+        on the rank alone is checked first and a failure is kept, not raised; ONE all-gather of a
+        small record per rank -- that error flag, the table's rows, the effective weights' range,
+        the evaluation rows and their positives, a checksum of the cuts and parameters -- then
+        gives every rank the same global figures, and every remaining check is made on those: all
+        ranks raise together or none does, before any training launch or level collective."""
+        import zlib
+
+        import torch
+        import torch.distributed as dist
+        dev = data.device if data is not None else y_dev.device if y_dev is not None else _group_device(group)
+        n = data.n if data is not None else 0
+        err = pending
+        y = mask = wd = keys = idx = None
+        wstat, weighted, n_pos = (-math.inf, math.inf, 1.0, 0.0), False, 0
+        spw, thr = float(self.scale_pos_weight), row_threshold(self.subsample)
+        try:
+            if err is not None:
+                raise err
+            if self.eval_metric == 'auc' and (eval_rows is not None or self.early_stopping_rounds is not None):
+                raise ValueError("eval_metric='auc' is not available with a process group: the exact pair count "
+                                 "needs every rank's minority keys (use 'logloss')")
+            y, mask = self._labels_mask(data, y_dev, rows)
+            wd = self._device_weights(data, sample_weight, check_host=False)
+            weighted = wd is not None or spw != 1.0
+            if weighted:
+                wstat = self._weight_stats(wd, y, mask, n)
+            if row_keys is not None and thr != THR_ALL:
+                keys = self._device_keys(data, row_keys)
+            if eval_rows is not None:
+                idx, n_pos = self._eval_local(data, y, eval_rows)
+        except ValueError as e:
+            err = e
+        cfg = repr((sorted(self.get_params().items()), self.early_stopping_rounds, self.eval_metric, weighted,
+                    keys is not None, eval_rows is not None, int(self.record))).encode()
+        cuts = data.cuts if data is not None else []
+        crc = zlib.crc32(b''.join(np.asarray(c, np.float32).tobytes() + b'|' for c in cuts), zlib.crc32(cfg))
+        rec = _gather_records(group, dev, [0.0 if err is None else 1.0, float(n), *wstat,
+                                           float(0 if idx is None else idx.numel()), float(n_pos), float(crc)])
+        if err is not None:
+            raise err
+        rank = dist.get_rank(group)
+        if rec[:, 0].any():
+            raise ValueError(f'sharded fit: rank {int(np.flatnonzero(rec[:, 0])[0])} of the process group refused '
+                             f'its arguments (this is rank {rank})')
+        if (rec[:, 8] != rec[0, 8]).any():
+            raise ValueError('sharded fit: the cuts, the parameters or the kinds of arguments differ between the ranks')
+        e = 0
+        if weighted:
+            if not rec[:, 5].sum():
+                raise ValueError('no training rows')
+            e = _check_weight_range(float(rec[:, 2].max()), float(rec[:, 3].min()), bool(rec[:, 4].all()))
+        ev = None
+        if eval_rows is not None:
+            total, total_pos = int(rec[:, 6].sum()), int(rec[:, 7].sum())
+            if total == 0:
+                raise ValueError('binary scores need at least one row')
+            if total >= 2 ** 30:
+                raise ValueError('binary scores take fewer than 2**30 rows')
+            if total_pos == 0 or total_pos == total:
+                raise ValueError('Only one class present in y. The AUROC is not defined in that case.')
+            ev = self._eval_state(data, y, idx, n_pos, int(self.n_estimators), total, total_pos)
+        if keys is None and thr != THR_ALL:  # the default key: the row's index in the concatenated table
+            keys = torch.arange(n, dtype=torch.int64, device=dev) + int(rec[:rank, 1].sum())
+        f = self._buffers(data, y, mask, wd, e, keys, ev)
+        f.group = group
+        f.pay = torch.empty(max(_exchange(data)[0].words(2 ** (f.D - 1)), 2), dtype=torch.int64, device=dev)
+        return f
+
+    def _labels_mask(self, data: BinnedData, y_dev, rows):
+        import torch
+        dev, n, ld = data.device, data.n, data.ld
         y = y_dev.view(torch.uint8) if y_dev.dtype == torch.bool else y_dev
         if y.dtype != torch.uint8 or y.numel() < n or y.device != dev:
             raise ValueError('y_dev must be a uint8 / bool device column of at least n rows')
@@ -1026,28 +1340,58 @@ class DeviceGBTClassifier:
                 mask[:n] = rows[:n].to(torch.uint8)
             else:
                 mask[rows.to(torch.int64)] = 1
+        return y, mask
+
+    def _device_weights(self, data: BinnedData, sample_weight, check_host: bool):
+        """``sample_weight`` as the float32 device column (None: none given); ``check_host``: a host
+        column is validated by :func:`check_weights` before the upload."""
+        import torch
+        dev, n = data.device, data.n
+        if sample_weight is None:
+            return None
+        if isinstance(sample_weight, torch.Tensor) and sample_weight.device == dev:
+            if sample_weight.numel() < n:
+                raise ValueError(f'sample_weight has {sample_weight.numel()} entries for {n} rows')
+            return sample_weight.reshape(-1).to(torch.float32).contiguous()
+        host = sample_weight.numpy() if isinstance(sample_weight, torch.Tensor) else sample_weight
+        if check_host:
+            host, _ = check_weights(host, n)
+        elif len(np.asarray(host).ravel()) != n:
+            raise ValueError(f'sample_weight has {len(np.asarray(host).ravel())} entries for {n} rows')
+        return weights_to_device(host, dev)
+
+    def _device_keys(self, data: BinnedData, row_keys):
+        import torch
+        keys = torch.as_tensor(row_keys).reshape(-1).to(data.device).to(torch.int64).contiguous()
+        if keys.numel() < data.n:
+            raise ValueError(f'row_keys has {keys.numel()} entries for {data.n} rows')
+        return keys
+
+    def _prepare(self, data: BinnedData, y_dev, rows, eval_rows, sample_weight, row_keys) -> '_Fit':
+        """A fit's state before round 0, in this order: labels, row mask, weights and their shift
+        (a weighted fit's one host read), row keys, column samples, buffers, evaluation state (one
+        host read).  Every validation error is raised here, before the first training launch."""
+        n = data.n
+        y, mask = self._labels_mask(data, y_dev, rows)
+        spw, thr = float(self.scale_pos_weight), row_threshold(self.subsample)
+        wd = self._device_weights(data, sample_weight, check_host=rows is None)
+        e = self._weight_shift(wd, y, mask, n) if wd is not None or spw != 1.0 else 0
+        keys = self._device_keys(data, row_keys) if row_keys is not None and thr != THR_ALL else None
+        f = self._buffers(data, y, mask, wd, e, keys, None)
+        if eval_rows is not None:  # before any training launch
+            f.ev = self._eval_setup(data, y, eval_rows, f.T)
+        return f
+
+    def _buffers(self, data: BinnedData, y, mask, wd, e: int, keys, ev) -> '_Fit':
+        """The validated inputs as a fit's state: the :class:`Tuning` and the column samples (both
+        None for a plain fit) and every device buffer of the rounds."""
+        import torch
+        dev, ld, F = data.device, data.ld, data.n_features
+        T, D = int(self.n_estimators), int(self.max_depth)
         alpha, spw, seed = float(self.reg_alpha), float(self.scale_pos_weight), int(self.random_state)
         thr, colsample = row_threshold(self.subsample), float(self.colsample_bytree)
         tu = columns = None
-        if not (sample_weight is None and spw == 1.0 and thr == THR_ALL and colsample == 1.0 and alpha == 0.0):
-            e, wd, keys = 0, None, None
-            if isinstance(sample_weight, torch.Tensor) and sample_weight.device == dev:
-                if sample_weight.numel() < n:
-                    raise ValueError(f'sample_weight has {sample_weight.numel()} entries for {n} rows')
-                wd = sample_weight.reshape(-1).to(torch.float32).contiguous()
-            elif sample_weight is not None:
-                host = sample_weight.numpy() if isinstance(sample_weight, torch.Tensor) else sample_weight
-                if rows is None:
-                    host, _ = check_weights(host, n)
-                elif len(np.asarray(host).ravel()) != n:
-                    raise ValueError(f'sample_weight has {len(np.asarray(host).ravel())} entries for {n} rows')
-                wd = weights_to_device(host, dev)
-            if wd is not None or spw != 1.0:
-                e = self._weight_shift(wd, y, mask, n)
-            if row_keys is not None and thr != THR_ALL:
-                keys = torch.as_tensor(row_keys).reshape(-1).to(dev).to(torch.int64).contiguous()
-                if keys.numel() < n:
-                    raise ValueError(f'row_keys has {keys.numel()} entries for {n} rows')
+        if not (wd is None and spw == 1.0 and thr == THR_ALL and colsample == 1.0 and alpha == 0.0):
             if colsample != 1.0:
                 columns = ColumnSamples(data, seed, T, colsample)
             tu = Tuning(wd, spw, e, keys, seed, thr, alpha)
@@ -1063,8 +1407,7 @@ class DeviceGBTClassifier:
             trees=torch.zeros((max(T, 1), 2 ** (D + 1) - 1, NODE_DTYPE.itemsize), dtype=torch.uint8, device=dev),
             hist=torch.empty((top, F, 256, 2), dtype=torch.int64, device=dev),
             bg=torch.empty(top * F, dtype=torch.float64, device=dev),
-            bc=torch.empty(top * F, dtype=torch.int32, device=dev),
-            ev=None if eval_rows is None else self._eval_setup(data, y, eval_rows, T))  # before any training launch
+            bc=torch.empty(top * F, dtype=torch.int32, device=dev), ev=ev, group=None, pay=None)
 
     def _finish(self, f: '_Fit', R: int) -> 'DeviceGBTClassifier':
         """After ``R`` rounds: the evaluation series and the best round, ``margin_`` / ``p_`` of
@@ -1074,11 +1417,11 @@ class DeviceGBTClassifier:
         for k in ('evals_result_', 'eval_sums_', 'best_iteration', 'best_score'):
             self.__dict__.pop(k, None)
         if ev is not None:
-            series = self._eval_series(ev, R)
+            series = self._eval_series(ev, R, f.group)
             best, stop = stop_decision(series, esr, self.eval_metric == 'auc')
             assert stop == R, (stop, R)  # every round launched was needed
             self.eval_sums_ = series
-            scores = [metric_score(v, self.eval_metric, ev.n, ev.n_pos) for v in series]
+            scores = [metric_score(v, self.eval_metric, ev.total, ev.total_pos) for v in series]
             self.evals_result_ = {'validation_0': {self.eval_metric: scores}}
             if series:
                 self.best_iteration, self.best_score = best, scores[best]
@@ -1109,7 +1452,7 @@ class DeviceGBTClassifier:
         return self
 
     def fit_binned(self, data: BinnedData, y_dev, rows=None, eval_rows=None, sample_weight=None,
-                   row_keys=None) -> 'DeviceGBTClassifier':
+                   row_keys=None, process_group=None, _pending=None) -> 'DeviceGBTClassifier':
         """Fit on binned data and a device label column (uint8 / bool, at least n rows).  The
         whole fit is enqueued on the current stream -- fixed launch sequences per level and per
         round, no host synchronisation -- and the node tables of all trees are read back once.
@@ -1127,9 +1470,28 @@ class DeviceGBTClassifier:
         rows; with it a sampled fit is also the same for any row order.  The default key is the
         row index, which gives run-to-run identity only: permuting the rows then changes the
         sample.  With every one of these at its neutral value the launches are the unweighted
-        fit's and nothing is read from the device before the first round."""
-        esr = self._check_eval_rows(eval_rows)
-        f = self._prepare(data, y_dev, rows, eval_rows, sample_weight, row_keys)
+        fit's and nothing is read from the device before the first round.
+
+        ``process_group`` (a ``torch.distributed`` group; contract items 18-22): every rank passes
+        its own shard of the rows -- ``data`` binned with the same cuts (``bin_blocks(...,
+        process_group=)``), ``rows`` / ``eval_rows`` / ``sample_weight`` / ``row_keys`` of its own
+        table, possibly an empty one -- and the ranks join each level's histogram with ONE int64
+        SUM all-reduce of its packed used entries (``sa_boost_hist_pack`` / ``_unpack``).  Every
+        rank ends with the same ``trees_``, byte for byte the single-device fit of the ranks' rows
+        concatenated in rank order; ``margin_`` / ``p_`` / ``record_`` describe the rank's own rows.
+        The evaluation metric is 'logloss' ('auc' raises), summed over the ranks at every look.  A
+        ``ValueError`` on one rank is raised on every rank before the first level collective."""
+        group = process_group
+        if group is None:
+            esr = self._check_eval_rows(eval_rows)
+            f = self._prepare(data, y_dev, rows, eval_rows, sample_weight, row_keys)
+        else:
+            try:
+                self._check_eval_rows(eval_rows)
+            except ValueError as e:
+                _pending = _pending or e
+            esr = self.early_stopping_rounds
+            f = self._prepare_sharded(data, y_dev, rows, eval_rows, sample_weight, row_keys, group, _pending)
         lib, run, st, d, nb = _native.lib(), self._launch, f.stream, data.dev, len(data.bit_feat)
         n, ld, F = data.n, data.ld, data.n_features
         look, R, self.n_polls_ = esr, f.T, 0
@@ -1143,6 +1505,8 @@ class DeviceGBTClassifier:
                 h = f.hist[:nn]
                 h.zero_()
                 _hist(run, st, data, f.gq, f.hq, f.node, nn, h, tree, level == 0, cols=cols)
+                if group is not None:
+                    self._exchange_level(f, h, tree, nn, cols)
                 _split(run, st, h, d['cut_start'], d['cuts'], F, nn, f.params, f.bg, f.bc, tree, tu=f.tu, fmask=fmask)
                 run('advance', lib.sa_boost_advance, tree.data_ptr(), nn - 1, nn, d['fmap'].data_ptr(),
                     data.bits.data_ptr() if nb else None, data.bits.shape[1] * 8 if nb else 0, data.bins.data_ptr(),
@@ -1157,68 +1521,129 @@ class DeviceGBTClassifier:
             self._eval_round(data, f.ev, tree, t, st)
             if esr is not None and t == look and t + 1 < f.T:  # the rule could first fire here
                 self.n_polls_ += 1
-                fired, look = stop_look(self._eval_series(f.ev, t + 1), esr, self.eval_metric == 'auc')
+                fired, look = stop_look(self._eval_series(f.ev, t + 1, group), esr, self.eval_metric == 'auc')
                 if fired:
                     R = t + 1
                     break
         return self._finish(f, R)
 
+    def _exchange_level(self, f: '_Fit', hist, tree, n_nodes: int, cols) -> None:
+        """Contract item 18: the level's local histogram (and at level 0 the local root totals)
+        packed, summed over the ranks with one int64 all-reduce and unpacked in place -- after it
+        every rank holds the global level histogram.  ``cols``: the round's column sample, whose
+        bool features are the ones ``sa_boost_hist_bits`` derived a bin 0 for."""
+        from . import shard
+        pay = hist_pack(f.data, hist, tree, n_nodes, out=f.pay, launch=self._launch)
+        self._timed('allreduce', lambda: shard.allreduce_boost_level(pay, f.group))
+        bit_feat, nb = (None, None) if cols is None else (cols[1], cols[2])
+        hist_unpack(f.data, pay, hist, tree, n_nodes, bit_feat, nb, launch=self._launch)
+
+    def _sharded_bin(self, group, dev, check, bin_fn):
+        """The front of a sharded :meth:`fit_blocks` / :meth:`fit`: ``check()`` (the rank's own
+        validation) agreed over the ranks, then ``bin_fn()``, whose own ``ValueError`` is kept for
+        :meth:`fit_binned`'s agreement.  Returns ``(check's result, data or None, pending error)``."""
+        err = out = data = None
+        try:
+            out = check()
+        except ValueError as e:
+            err = e
+        agree(group, dev, err)
+        try:
+            data = bin_fn(out)
+        except ValueError as e:
+            err = e
+        return out, data, err
+
     def fit_blocks(self, blocks, y_dev, rows=None, cuts=None, eval_rows=None, sample_weight=None,
-                   row_keys=None) -> 'DeviceGBTClassifier':
+                   row_keys=None, process_group=None) -> 'DeviceGBTClassifier':
         """Fit on device feature blocks (``ops.features(..., bool_bits=True)``) and a device label
         column.  ``rows``: the training rows (indices or a bool mask), default all; ``cuts``:
         explicit cut lists, default :func:`make_cuts` on the training rows; ``eval_rows``: the
         evaluation rows (indices or a bool mask), default none; ``sample_weight`` / ``row_keys``: as
-        in :meth:`fit_binned`."""
-        self._check_eval_rows(eval_rows)
-        rows = None if rows is None else _row_list(rows, blocks.n, blocks.device)
+        in :meth:`fit_binned`.  ``process_group``: every rank passes its own blocks (contract items
+        18-22); with ``cuts=None`` the cuts come from the ranks' global sample."""
+        def check():
+            self._check_eval_rows(eval_rows)
+            return None if rows is None else _row_list(rows, blocks.n, blocks.device)
+        if process_group is not None:
+            rows, data, err = self._sharded_bin(process_group, blocks.device, check,
+                                                lambda r: bin_blocks(blocks, cuts, r, process_group))
+            return self.fit_binned(data, y_dev, rows, eval_rows, sample_weight, row_keys, process_group, err)
+        rows = check()
         return self.fit_binned(bin_blocks(blocks, cuts, rows), y_dev, rows, eval_rows, sample_weight, row_keys)
 
-    def fit(self, X, y, cuts=None, eval_set=None, sample_weight=None, row_keys=None) -> 'DeviceGBTClassifier':
+    def fit(self, X, y, cuts=None, eval_set=None, sample_weight=None, row_keys=None,
+            process_group=None) -> 'DeviceGBTClassifier':
         """Fit on a host frame or 2-D array: uploaded, binned and trained by the same kernels.
         ``eval_set=[(X_val, y_val)]``: exactly one pair with the same columns; the two frames
         are uploaded as one table whose first ``len(X)`` rows train and whose other rows are the
         evaluation rows (the cuts come from the training rows only).  ``sample_weight`` /
-        ``row_keys``: one entry per row of ``X`` (host), validated before anything is uploaded."""
-        self._check_eval_rows(eval_set)
-        yh = np.asarray(y).astype(bool).astype(np.uint8).ravel()
-        n_train = len(yh)
-        if sample_weight is not None:
-            sample_weight, _ = check_weights(sample_weight, n_train, yh, self.scale_pos_weight)
-        if row_keys is not None:
-            row_keys = check_row_keys(row_keys, n_train)
-        rows = eval_rows = None
-        if eval_set is not None:
-            if len(eval_set) != 1 or len(eval_set[0]) != 2:
-                raise ValueError('eval_set takes exactly one (X_val, y_val) pair')
-            names, cols = _host_columns(X)
-            vnames, vcols = _host_columns(eval_set[0][0])
-            if vnames != names or [_kind(c) for c in vcols] != [_kind(c) for c in cols]:
-                raise ValueError('the evaluation frame must have the training frame\'s columns')
-            if cols and len(cols[0]) != n_train:
+        ``row_keys``: one entry per row of ``X`` (host), validated before anything is uploaded.
+        ``process_group``: every rank passes its own frames (contract items 18-22; the weights'
+        range is then checked over all ranks, on the device)."""
+        group = process_group
+
+        def front():
+            self._check_eval_rows(eval_set)
+            Xa, w, keys = X, sample_weight, row_keys
+            yh = np.asarray(y).astype(bool).astype(np.uint8).ravel()
+            n_train = len(yh)
+            if w is not None and group is None:
+                w, _ = check_weights(w, n_train, yh, self.scale_pos_weight)
+            elif w is not None:
+                w = np.asarray(w, np.float64).ravel()
+                if len(w) != n_train:
+                    raise ValueError(f'sample_weight has {len(w)} entries for {n_train} rows')
+            if keys is not None:
+                keys = check_row_keys(keys, n_train)
+            rows = eval_rows = None
+            names, cols = _host_columns(Xa)
+            if eval_set is not None:
+                if len(eval_set) != 1 or len(eval_set[0]) != 2:
+                    raise ValueError('eval_set takes exactly one (X_val, y_val) pair')
+                vnames, vcols = _host_columns(eval_set[0][0])
+                if vnames != names or [_kind(c) for c in vcols] != [_kind(c) for c in cols]:
+                    raise ValueError('the evaluation frame must have the training frame\'s columns')
+                if cols and len(cols[0]) != n_train:
+                    raise ValueError('X and y have different lengths')
+                yv = np.asarray(eval_set[0][1]).astype(bool).astype(np.uint8).ravel()
+                if vcols and len(vcols[0]) != len(yv):
+                    raise ValueError('X_val and y_val have different lengths')
+                import pandas as pd
+                Xa = pd.DataFrame({c: np.concatenate([a, b]) for c, a, b in zip(names, cols, vcols)}, columns=names)
+                yh = np.concatenate([yh, yv])
+                rows = np.arange(n_train, dtype=np.int64)
+                eval_rows = np.arange(n_train, len(yh), dtype=np.int64)
+                if w is not None:  # the evaluation rows are scored unweighted
+                    w = np.concatenate([w, np.zeros(len(yv), w.dtype)])
+                if keys is not None:
+                    keys = np.concatenate([keys, np.zeros(len(yv), np.int64)])
+            elif group is not None and cols and len(cols[0]) != n_train:
                 raise ValueError('X and y have different lengths')
-            yv = np.asarray(eval_set[0][1]).astype(bool).astype(np.uint8).ravel()
-            if vcols and len(vcols[0]) != len(yv):
-                raise ValueError('X_val and y_val have different lengths')
-            import pandas as pd
-            X = pd.DataFrame({c: np.concatenate([a, b]) for c, a, b in zip(names, cols, vcols)}, columns=names)
-            yh = np.concatenate([yh, yv])
-            rows = np.arange(n_train, dtype=np.int64)
-            eval_rows = np.arange(n_train, len(yh), dtype=np.int64)
-            if sample_weight is not None:  # the evaluation rows are scored unweighted
-                sample_weight = np.concatenate([sample_weight, np.zeros(len(yv), np.float32)])
-            if row_keys is not None:
-                row_keys = np.concatenate([row_keys, np.zeros(len(yv), np.int64)])
+            return Xa, np.ascontiguousarray(yh), rows, eval_rows, w, keys, n_train
+
         import torch
-        data = bin_host(X, cuts, rows)
-        yh = np.ascontiguousarray(yh)
-        if len(yh) != data.n:
+        err = None
+        if group is None:
+            Xa, yh, rows, eval_rows, w, keys, n_train = front()
+            data = bin_host(Xa, cuts, rows)
+        else:
+            dev = torch.device('cuda', torch.cuda.current_device())
+            front_out, data, err = self._sharded_bin(group, dev, front,
+                                                     lambda v: bin_host(v[0], cuts, v[2], process_group=group))
+            Xa, yh, rows, eval_rows, w, keys, n_train = front_out
+        if data is not None and len(yh) != data.n:
             raise ValueError('X and y have different lengths')
-        yd = torch.zeros(data.ld, dtype=torch.uint8, device=data.device)
-        yd[:data.n] = torch.from_numpy(yh).to(data.device)
-        if sample_weight is not None:
-            sample_weight = weights_to_device(sample_weight, data.device)
-        self.fit_binned(data, yd, rows, eval_rows, sample_weight, row_keys)
+        yd = None
+        if data is not None:
+            yd = torch.zeros(data.ld, dtype=torch.uint8, device=data.device)
+            yd[:data.n] = torch.from_numpy(yh).to(data.device)
+            if w is not None:
+                w = weights_to_device(w, data.device)
+        if group is None:
+            self.fit_binned(data, yd, rows, eval_rows, w, keys)
+        else:
+            self.fit_binned(data, yd, rows, eval_rows, w, keys, group, err)
         if eval_set is not None:  # the fitted columns are the training frame's
             self.margin_, self.p_ = self.margin_[:n_train], self.p_[:n_train]
             if self.record_ is not None:
@@ -1314,5 +1739,6 @@ __all__ = ['DeviceGBTClassifier', 'BinnedData', 'NODE_DTYPE', 'make_cuts', 'cuts
            'trees_to_xgboost_json', 'predict_tables', 'base_margin', 'check_params', 'apply_tree',
            'stop_decision', 'stop_look', 'check_stop_params', 'metric_integer', 'metric_score', 'EVAL_METRICS',
            'fmix64', 'draw', 'row_threshold', 'column_sample', 'weight_shift', 'check_weights', 'importances',
-           'IMPORTANCE_TYPES', 'THR_ALL', 'row_keys',
+           'IMPORTANCE_TYPES', 'THR_ALL', 'row_keys', 'exchange_layout', 'ExchangeLayout', 'shard_sample_rows',
+           'level_histogram', 'hist_pack', 'hist_unpack', 'agree',
            'TunedGBTClassifier', 'TUNING_DEFAULTS', 'ALL_DEFAULTS', 'is_tuned', 'make_classifier']

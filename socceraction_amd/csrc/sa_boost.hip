@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 
 #include "sa_common.h"
 #include "sa_internal.h"
@@ -573,6 +574,60 @@ __global__ __launch_bounds__(AP_THREADS) void boost_apply_kernel(const sa_boost_
   if (p) p[i] = 1.0f / (1.0f + expf(-m));
 }
 
+// ---------------------------------------------------------------------------------------- exchange
+// The level histogram's used entries as one contiguous buffer of (G, H) pairs, for the ranks' one
+// integer all-reduce per level.  pairs [n_bool + n_num]: a node's payload
+// pairs as dense pair offsets feature * 256 + bin -- every bool feature's bin 1, then every numeric
+// feature's bins 0 .. m and 255.  Payload: `head` pairs (the root's totals at level 0), the bool
+// pairs of every node, the numeric pairs of every node.  Payload pair i of the body is dense pair
+// exchange_dense(i); one thread per pair, one 16-B load and one 16-B store, no atomics.
+typedef long long pair64 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ int64_t exchange_dense(int64_t i, const int32_t* __restrict__ pairs, int n_bool, int n_num,
+                                                  int n_nodes, int F) {
+  const int64_t nb = (int64_t)n_nodes * n_bool;
+  int k, j;
+  if (i < nb) {
+    k = (int)(i / n_bool);
+    j = (int)(i - (int64_t)k * n_bool);
+  } else {
+    k = (int)((i - nb) / n_num);
+    j = n_bool + (int)((i - nb) - (int64_t)k * n_num);
+  }
+  return (int64_t)k * F * BINS + pairs[j];
+}
+
+__global__ __launch_bounds__(256) void boost_hist_pack_kernel(const pair64* __restrict__ hist,
+                                                               const sa_boost_node* __restrict__ tree,
+                                                               const int32_t* __restrict__ pairs, int n_bool, int n_num,
+                                                               int n_nodes, int F, int head, pair64* __restrict__ payload) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x - head;
+  if (i >= (int64_t)n_nodes * (n_bool + n_num)) return;
+  if (i < 0) {  // level 0: this rank's root totals
+    payload[0] = pair64{(long long)tree[0].G, (long long)tree[0].H};
+    return;
+  }
+  const int64_t d = exchange_dense(i, pairs, n_bool, n_num, n_nodes, F);
+  SA_DGUARD(d >= 0 && d < (int64_t)n_nodes * F * BINS, d, return);
+  payload[head + i] = hist[d];
+}
+
+__global__ __launch_bounds__(256) void boost_hist_unpack_kernel(const pair64* __restrict__ payload,
+                                                                 const int32_t* __restrict__ pairs, int n_bool,
+                                                                 int n_num, int n_nodes, int F, int head,
+                                                                 pair64* __restrict__ hist,
+                                                                 sa_boost_node* __restrict__ tree) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x - head;
+  if (i >= (int64_t)n_nodes * (n_bool + n_num)) return;
+  if (i < 0) {  // level 0: the summed root totals (G, H: the record's first 16 bytes)
+    *reinterpret_cast<pair64*>(&tree[0].G) = payload[0];
+    return;
+  }
+  const int64_t d = exchange_dense(i, pairs, n_bool, n_num, n_nodes, F);
+  SA_DGUARD(d >= 0 && d < (int64_t)n_nodes * F * BINS, d, return);
+  hist[d] = payload[head + i];
+}
+
 // level-local node range [node0, node0 + n_nodes): one whole level of the heap, at most 32 nodes
 bool level_ok(int node0, int n_nodes) {
   return n_nodes >= 1 && n_nodes <= SA_BOOST_MAX_LEVEL_NODES && (n_nodes & (n_nodes - 1)) == 0 &&
@@ -781,4 +836,61 @@ extern "C" int sa_boost_apply(const sa_boost_node* tree, int32_t max_depth, cons
                      (hipStream_t)stream, tree, (int)max_depth, fmap, (const u64*)bits, bits_stride / 8, bins, ld, rows,
                      n_rows, n, margin, p);
   return check_launch("boost_apply_kernel");
+}
+
+namespace {
+static_assert(offsetof(sa_boost_node, G) == 0 && offsetof(sa_boost_node, H) == 8, "the totals are one 16-byte pair");
+
+// what pack and unpack share: the level, the pair table's sizes and the 16-byte alignment of the pair accesses
+int exchange_args(const char* name, const void* hist, const void* tree, const int32_t* pairs, int32_t n_pair_bool,
+                  int32_t n_pair_num, int32_t node0, int32_t n_nodes, int32_t n_features, const void* payload) {
+  if (n_pair_bool < 0 || n_pair_num < 0 || n_features < 1 || !level_ok(node0, n_nodes) || n_pair_bool > n_features ||
+      (int64_t)n_pair_bool + n_pair_num > (int64_t)n_features * BINS)
+    return fail(SA_EINVAL, "%s: bad sizes", name);
+  if (!hist || !tree || !payload || (n_pair_bool + n_pair_num > 0 && !pairs))
+    return fail(SA_EINVAL, "%s: null pointer", name);
+  if (((uintptr_t)hist | (uintptr_t)tree | (uintptr_t)payload) & 15u)
+    return fail(SA_EINVAL, "%s: hist, tree and payload must be 16-byte aligned", name);
+  return SA_OK;
+}
+}  // namespace
+
+extern "C" int sa_boost_hist_pack(const int64_t* hist, const sa_boost_node* tree, const int32_t* pairs,
+                                  int32_t n_pair_bool, int32_t n_pair_num, int32_t node0, int32_t n_nodes,
+                                  int32_t n_features, int64_t* payload, void* stream) {
+  if (int rc = exchange_args("sa_boost_hist_pack", hist, tree, pairs, n_pair_bool, n_pair_num, node0, n_nodes,
+                             n_features, payload))
+    return rc;
+  const int head = node0 == 0;
+  const int64_t items = head + (int64_t)n_nodes * (n_pair_bool + n_pair_num);
+  if (items == 0) return SA_OK;
+  hipLaunchKernelGGL(boost_hist_pack_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const pair64*)hist, tree, pairs, n_pair_bool, n_pair_num, n_nodes, n_features, head,
+                     (pair64*)payload);
+  return check_launch("boost_hist_pack_kernel");
+}
+
+extern "C" int sa_boost_hist_unpack(const int64_t* payload, const int32_t* pairs, int32_t n_pair_bool,
+                                    int32_t n_pair_num, const int32_t* bit_feat, int32_t n_bool, int32_t node0,
+                                    int32_t n_nodes, int32_t n_features, int64_t* hist, sa_boost_node* tree,
+                                    void* stream) {
+  if (int rc = exchange_args("sa_boost_hist_unpack", hist, tree, pairs, n_pair_bool, n_pair_num, node0, n_nodes,
+                             n_features, payload))
+    return rc;
+  if (n_bool < 0 || n_bool > n_pair_bool || (n_bool > 0 && !bit_feat))
+    return fail(SA_EINVAL, "sa_boost_hist_unpack: bad bool feature list");
+  const int head = node0 == 0;
+  const int64_t items = head + (int64_t)n_nodes * (n_pair_bool + n_pair_num);
+  if (items > 0) {
+    hipLaunchKernelGGL(boost_hist_unpack_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, (const pair64*)payload, pairs, n_pair_bool, n_pair_num, n_nodes, n_features,
+                       head, (pair64*)hist, tree);
+    if (int rc = check_launch("boost_hist_unpack_kernel")) return rc;
+  }
+  if (n_bool == 0) return SA_OK;
+  // every listed bool feature's bin 0 from the global totals and the summed bin 1 (the fill of sa_boost_hist_bits)
+  const int fill = n_bool * n_nodes;
+  hipLaunchKernelGGL(boost_bits_fill_kernel, dim3((unsigned)((fill + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     bit_feat, n_bool, node0, n_nodes, n_features, hist, tree);
+  return check_launch("boost_bits_fill_kernel");
 }

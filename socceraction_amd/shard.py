@@ -113,6 +113,37 @@ def allreduce_group_sums(acc, group=None) -> None:
                          'takes fewer than 2**30')
 
 
+def allreduce_boost_level(payload: torch.Tensor, group=None) -> None:
+    """Sum one tree level's exchange payload (``boost.hist_pack``: the used entries of the level
+    histogram and, at level 0, the root totals, int64) over the ranks of ``group`` in place with
+    ONE integer SUM all-reduce.  Integer addition commutes across ranks as it does across rows,
+    so every rank then holds the histogram a single rank would have summed over all rows, bit
+    for bit, and takes the same split decisions.  On RCCL the reduction is
+    ordered on the current stream: no host synchronisation."""
+    _all_reduce(payload, group=group)
+
+
+def allreduce_boost_eval(table: torch.Tensor, group=None) -> torch.Tensor:
+    """The learner's metric table rows ``[rounds, 10]`` (``ops.BinaryMetrics`` layout) summed over
+    the ranks of ``group`` -- a new tensor, the rank's own table stays -- with ONE integer SUM
+    all-reduce: the counts and log-loss limbs (words 0..7) add; the error word's three bits
+    travel as 16-bit lanes, as in :func:`allreduce_group_sums`, and come back as bits, so any
+    rank's flag raises on every rank.  Word 9 (the AUROC pair count) is not defined across ranks
+    and comes back 0."""
+    import torch.distributed as dist
+    if dist.get_world_size(group) > 65535:
+        raise ValueError('the metric all-reduce sums one 16-bit lane per error flag: at most 65535 ranks')
+    t = table.clone()
+    e = t[:, 8] & 0xFFFFFFFF
+    t[:, 8] = (e & 1) | ((e & 2) << 15) | ((e & 4) << 30)
+    t[:, 9] = 0
+    _all_reduce(t, group=group)
+    s = t[:, 8].clone()
+    t[:, 8] = ((s & 0xFFFF) != 0).to(torch.int64) | (((s >> 16) & 0xFFFF) != 0).to(torch.int64) * 2 | \
+        (((s >> 32) & 0xFFFF) != 0).to(torch.int64) * 4
+    return t
+
+
 def _flag_count_range(acc, group) -> None:
     """The int32-word sum is exact while every summed count stays below 2**31: each rank's shot
     and move counts below 2**31 // world guarantee it (a transition count never exceeds its

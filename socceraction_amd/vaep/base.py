@@ -298,7 +298,7 @@ class VAEP:
                   val_size: float = 0.0, nr_actions: int = 10,
                   tree_params: Optional[Dict[str, Any]] = None,
                   early_stopping_rounds: Optional[int] = None, eval_metric: str = 'auc',
-                  sample_weight=None) -> 'VAEP':
+                  sample_weight=None, process_group=None) -> 'VAEP':
         """Fit both learners on many games (contiguous per game) without the feature frame: one
         ``ActionBatch``, the features as bitmaps plus numeric blocks and the labels all on the
         device; only the cut sample and the finished trees cross the link.  ``val_size``: the
@@ -309,22 +309,55 @@ class VAEP:
         (every entry finite and not negative).  With ``subsample`` in ``tree_params`` a round's
         row sample is keyed by ``fm(game_id) + action_id``, built on the device, so it belongs to
         the action, not to its position: the model is the same for any game order or batch
-        split (as long as the cuts agree).  Built-in transformers only."""
+        split (as long as the cuts agree).  Built-in transformers only.
+
+        ``process_group`` (a ``torch.distributed`` group, one process per GPU): every rank passes
+        its OWN games and their actions -- for example one range of ``shard.partition_games`` --
+        builds its features, labels and bins locally, and both learners are fitted through the
+        sharded path (``boost.DeviceGBTClassifier.fit_binned(process_group=)``: the cuts from the
+        ranks' global sample, one integer all-reduce per tree level).  Every rank ends with the
+        same two models, byte for byte those of one GPU fitted on the ranks' actions in rank
+        order, and can ``rate`` its own games.  ``val_size`` splits each rank's own rows, and
+        ``device_eval_`` then scores the rank's OWN held-out rows with the common model.
+        ``early_stopping_rounds`` needs ``eval_metric='logloss'`` there (the exact AUROC is not
+        built across ranks).  A ``ValueError`` on one rank -- an empty ``actions`` frame is one --
+        is raised on every rank."""
         from .. import boost, metrics
         from ..trees import TreeEnsemble
         import torch
-        if learner != 'device':
-            raise ValueError(f'A {learner} learner is not supported by fit_batch')
-        params = boost.check_params(dict(tree_params or {}))  # before any device call
-        stop = self._device_stop_params(early_stopping_rounds, eval_metric, val_size > 0)
-        if sample_weight is not None:
-            sample_weight, _ = boost.check_weights(sample_weight, len(actions), None, params['scale_pos_weight'])
-        sampled = boost.row_threshold(params['subsample']) != boost.THR_ALL
-        if sampled and not {'game_id', 'action_id'} <= set(actions.columns):
-            raise ValueError('subsample needs the game_id and action_id columns (they key the row sample)')
-        known, unknown = self._split_xfns()
-        if unknown:
-            raise ValueError('fit_batch needs built-in feature transformers')
+        group = process_group
+
+        def check():
+            if learner != 'device':
+                raise ValueError(f'A {learner} learner is not supported by fit_batch')
+            params = boost.check_params(dict(tree_params or {}))  # before any device call
+            stop = self._device_stop_params(early_stopping_rounds, eval_metric, val_size > 0)
+            if group is not None and stop['early_stopping_rounds'] is not None and stop['eval_metric'] != 'logloss':
+                raise ValueError("early_stopping_rounds with a process group needs eval_metric='logloss': the "
+                                 "exact AUROC is not built across ranks")
+            if group is not None and len(actions) == 0:
+                raise ValueError('fit_batch with a process group needs actions on every rank')
+            weight = sample_weight
+            if weight is not None:
+                weight, _ = boost.check_weights(weight, len(actions), None, params['scale_pos_weight'])
+            sampled = boost.row_threshold(params['subsample']) != boost.THR_ALL
+            if sampled and not {'game_id', 'action_id'} <= set(actions.columns):
+                raise ValueError('subsample needs the game_id and action_id columns (they key the row sample)')
+            known, unknown = self._split_xfns()
+            if unknown:
+                raise ValueError('fit_batch needs built-in feature transformers')
+            return params, stop, weight, sampled, known
+
+        if group is None:
+            params, stop, sample_weight, sampled, known = check()
+        else:
+            err = out = None
+            try:
+                out = check()
+            except ValueError as e:
+                err = e
+            boost.agree(group, torch.device('cuda', torch.cuda.current_device()), err, 'fit_batch')
+            params, stop, sample_weight, sampled, known = out
         home_of = games.set_index('game_id')['home_team_id']
         ab = ActionBatch.from_frame(actions, atomic=self._atomic, home_team_id=home_of, segments='game')
         fb = ops.features(ab, known, self.nb_prev_actions, bool_bits=True)
@@ -335,14 +368,14 @@ class VAEP:
             cut = math.floor(ab.n * (1 - val_size))
             rows = torch.from_numpy(np.sort(idx[:cut])).to(ab.device)
             val_rows = torch.from_numpy(np.sort(idx[cut + 1:])).to(ab.device)
-        data = boost.bin_blocks(fb, rows=rows)
+        data = boost.bin_blocks(fb, rows=rows, process_group=group)
         keys = boost.row_keys(actions['game_id'].to_numpy(), actions['action_id'].to_numpy(), ab.device) \
             if sampled else None
         if sample_weight is not None:
             sample_weight = boost.weights_to_device(sample_weight, ab.device)
         labels = {col: getattr(lb, col) for col in ('scores', 'concedes')}
         eval_rows = val_rows if stop['early_stopping_rounds'] is not None else None
-        for col, ycol, clf in self._fit_labels(labels, params, stop, data, rows, eval_rows, sample_weight, keys):
+        for col, ycol, clf in self._fit_labels(labels, params, stop, data, rows, eval_rows, sample_weight, keys, group):
             if val_rows is not None and val_rows.numel():
                 p = TreeEnsemble.from_model(clf).predict_blocks(fb)
                 self.device_eval_[col] = metrics.binary_scores(ycol[:ab.n][val_rows].contiguous(),
