@@ -81,12 +81,12 @@ def _goal_flags(cols: Dict[str, np.ndarray], atomic: bool):
     return shot & (r == 1), shot & (r == 3)
 
 
-def features(cols: Dict[str, np.ndarray], k: int, xfns: Sequence[str], atomic: bool = False,
-             seg_off=None, home=None) -> List[Tuple[str, str, np.ndarray]]:
-    """Feature columns ``(name, kind, values)`` in reference order (vaep/base.py:113-116).
+def windows(cols: Dict[str, np.ndarray], k: int, atomic: bool = False, seg_off=None,
+            home=None) -> List[Dict[str, np.ndarray]]:
+    """The k game-state frames of a batch: window i of row j is row max(j - i, segment start),
+    flipped where row j's team is away (vaep/features.py:62-116 / atomic/vaep/features.py:86-111).
 
-    ``home`` = per-segment home team id (None: no flip). Windows and the flip follow
-    vaep/features.py:62-116 / atomic/vaep/features.py:86-111.
+    ``home`` = per-segment home team id (None: no flip).
     """
     n = len(cols['type_id'])
     so = segments_of(n, seg_off)
@@ -106,9 +106,18 @@ def features(cols: Dict[str, np.ndarray], k: int, xfns: Sequence[str], atomic: b
                            ('end_y', FIELD_W)):
                 w[c] = np.where(away, ext - w[c], w[c])
         W.append(w)
-    return features_frames(W, xfns, atomic, seg_off=so)
+    return W
 
 
+def features(cols: Dict[str, np.ndarray], k: int, xfns: Sequence[str], atomic: bool = False,
+             seg_off=None, home=None) -> List[Tuple[str, str, np.ndarray]]:
+    """Feature columns ``(name, kind, values)`` in reference order (vaep/base.py:113-116) of the
+    frames :func:`windows` builds."""
+    so = segments_of(len(cols['type_id']), seg_off)
+    return features_frames(windows(cols, k, atomic, so, home), xfns, atomic, seg_off=so)
+
+
+@np.errstate(over='ignore', invalid='ignore')  # coordinates may be NaN, inf or huge: no warnings
 def features_frames(frames: Sequence[Dict[str, np.ndarray]], xfns: Sequence[str],
                     atomic: bool = False, seg_off=None) -> List[Tuple[str, str, np.ndarray]]:
     """Feature columns of an explicit list of k game-state frames (equal-length column dicts),

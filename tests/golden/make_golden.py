@@ -14,7 +14,9 @@ Inputs are the reference's own fixtures (``tests/datasets/spadl/*.json``) plus s
 synthetic games from :mod:`socceraction_amd.synthetic` (edge sizes n = 1..40, forced
 goals/owngoals at the segment tail, full-size games). Every output is stored as plain
 arrays in ``tests/golden/*.npz`` (no pickles): inputs, feature blocks split by dtype,
-labels, formula values (f64 and f32 probabilities), and xT matrices/surfaces/rates.
+labels, formula values (f64 and f32 probabilities), and xT matrices/surfaces/rates.  The
+``values`` cases are the game of ``tests/value_cases.py`` (coordinates on, next to and beyond
+the goal point and line, NaN, inf, subnormals), which the schema stand-in is not asked about.
 """
 from __future__ import annotations
 
@@ -34,6 +36,7 @@ sys.dont_write_bytecode = True
 sys.path.insert(0, os.path.join(HERE, '_shims'))
 sys.path.insert(0, REF)
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, 'tests'))
 
 np.NaN = np.nan  # noqa: N816  (reference uses the removed alias)
 
@@ -117,9 +120,12 @@ def _inputs(df: pd.DataFrame, cols) -> dict:
     return {'in_' + c: df[c].to_numpy() for c in cols}
 
 
-def spadl_case(name: str, df: pd.DataFrame, home: int, ks=(3,), probs_seed: int = 1) -> None:
-    """Per-game VAEP features/labels/formula of one frame (= one segment)."""
-    _check_spadl(df, atomic=False)
+def spadl_case(name: str, df: pd.DataFrame, home: int, ks=(3,), probs_seed: int = 1,
+               in_schema: bool = True) -> None:
+    """Per-game VAEP features/labels/formula of one frame (= one segment).  ``in_schema=False``:
+    the frame holds coordinates the schema would refuse on purpose (the ``values`` cases)."""
+    if in_schema:
+        _check_spadl(df, atomic=False)
     out = _inputs(df, SPADL_IN)
     out['home_team_id'] = np.array([home], np.int64)
     game = _Game(home)
@@ -147,8 +153,10 @@ def spadl_case(name: str, df: pd.DataFrame, home: int, ks=(3,), probs_seed: int 
     print('spadl', name, len(df), 'rows')
 
 
-def atomic_case(name: str, df: pd.DataFrame, home: int, ks=(3,), probs_seed: int = 2) -> None:
-    _check_spadl(df, atomic=True)
+def atomic_case(name: str, df: pd.DataFrame, home: int, ks=(3,), probs_seed: int = 2,
+                in_schema: bool = True) -> None:
+    if in_schema:
+        _check_spadl(df, atomic=True)
     out = _inputs(df, ATOMIC_IN)
     out['home_team_id'] = np.array([home], np.int64)
     game = _Game(home)
@@ -255,6 +263,12 @@ def main() -> None:
 
     da = synthetic.atomic_games(1, seed=41)
     atomic_case('full0', synthetic.to_frame(da, atomic=True), int(da['home_team_id'][0]))
+
+    # --- value games (tests/value_cases.py): every special coordinate, NaN and inf included, in
+    # windows 0, 1 and 2 under both flip states, plus ordinary rows
+    import value_cases
+    spadl_case('values', value_cases.golden_game(False), value_cases.GOLDEN_HOME, in_schema=False)
+    atomic_case('values', value_cases.golden_game(True), value_cases.GOLDEN_HOME, in_schema=False)
 
     # --- xT ---
     xt_case('fixture', sp, grids=[(16, 12), (8, 6), (1, 1), (2, 2)], interp_grids=[(16, 12)])

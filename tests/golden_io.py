@@ -2,6 +2,7 @@
 import glob
 import os
 
+import mpmath
 import numpy as np
 import pandas as pd
 
@@ -55,6 +56,119 @@ def assert_close(a, b, name=''):
     tol = 1e-6 * np.abs(b[ok]) + 1e-12
     bad = err > tol
     assert not bad.any(), f'{name}: {bad.sum()} mismatches, max err {err.max()}'
+
+
+def _bits(a):
+    return a.view(np.int64 if a.dtype == np.float64 else np.int32)
+
+
+def assert_same_floats(got, ref, name=''):
+    """Bit-for-bit float parity: equal shape and dtype, NaN in the same places (payloads do not
+    count), equal bit patterns elsewhere, so 0.0 is not -0.0."""
+    got, ref = np.ascontiguousarray(got), np.ascontiguousarray(ref)
+    assert got.dtype == ref.dtype and got.dtype in (np.float64, np.float32), (name, got.dtype, ref.dtype)
+    assert got.shape == ref.shape, (name, got.shape, ref.shape)
+    ng, nr = np.isnan(got), np.isnan(ref)
+    assert (ng == nr).all(), f'{name}: NaN pattern differs at {np.argwhere(ng != nr)[:5].tolist()}'
+    bad = (_bits(got) != _bits(ref)) & ~nr
+    if bad.any():
+        at = np.argwhere(bad)
+        first = tuple(at[0])
+        raise AssertionError(f'{name}: {len(at)} values differ in their bits, first at {first}: '
+                             f'got {got[first]!r}, reference {ref[first]!r}')
+
+
+_PARTS = {}  # mpf value -> (nearest double, exact - nearest)
+_SPLIT = {}  # id(mpf array) -> (the array, nearest double, residual, ulp, sign)
+
+
+def _parts(e):
+    t = _PARTS.get(e)
+    if t is None:
+        near = float(e)
+        with mpmath.workprec(200):
+            t = (near, float('nan') if near != near else float(e - mpmath.mpf(near)))
+        _PARTS[e] = t
+    return t
+
+
+def _split_exact(exact):
+    """An array of mpmath.mpf as (nearest double, exact - nearest, spacing(|exact|), sign bit),
+    once per array and once per value: the callers compute a reference once and share it."""
+    key = id(exact)
+    if key not in _SPLIT:
+        parts = np.array([_parts(e) for e in exact.reshape(-1).tolist()], np.float64).reshape(-1, 2)
+        near, res = parts[:, 0].reshape(exact.shape), parts[:, 1].reshape(exact.shape)
+        # spacing at |exact|: of the double at or below it in magnitude
+        inward = np.where((res != 0) & (np.signbit(res) != np.signbit(near)), np.nextafter(near, 0.0), near)
+        with np.errstate(invalid='ignore'):
+            ulp = np.spacing(np.abs(inward))
+        _SPLIT[key] = (exact, near, res, ulp, np.signbit(near))   # float() keeps the sign of a tiny value
+    return _SPLIT[key][1:]
+
+
+def assert_within_ulps(got, exact, bound, name=''):
+    """``got`` within ``bound`` float64 ulps of a high-precision value; returns the largest
+    distance seen, in ulps.
+
+    ``exact`` is an array of ``mpmath.mpf`` (distances are exact; an exact zero is +0.0, mpf has
+    no signed zero), or a pair ``(lo, hi)`` of float64 arrays with lo <= value <= hi (``got`` must
+    lie in [hi - bound ulp, lo + bound ulp], which implies the bound; the distance returned is the
+    larger of the distances to lo and hi, an upper estimate).
+
+    NaN in the same places and the same sign; |got - exact| <= bound * spacing(|exact|); an
+    exact zero is matched exactly.  A float32 ``got`` must lie in
+    [float32(exact - bound ulp), float32(exact + bound ulp)] (ulp of float64), which does not
+    charge a float32 rounding midpoint to the code under test; the distance returned is then 0
+    inside float32(exact)'s own bracket, else the excess in float64 ulps.
+    """
+    got = np.ascontiguousarray(got)
+    assert got.dtype in (np.float64, np.float32), (name, got.dtype)
+    if isinstance(exact, tuple):
+        lo, hi = (np.ascontiguousarray(v, dtype=np.float64) for v in exact)
+        assert lo.shape == hi.shape and (np.isnan(lo) == np.isnan(hi)).all(), name
+        with np.errstate(invalid='ignore'):
+            assert (lo[~np.isnan(lo)] <= hi[~np.isnan(lo)]).all(), name
+            ulp = np.spacing(np.minimum(np.abs(lo), np.abs(hi)))
+        sign, zero, nan = np.signbit(lo), (lo == 0) & (hi == 0), np.isnan(lo)
+        res_lo = res_hi = 0.0
+    else:
+        assert exact.dtype == object, name
+        near, res, ulp, sign = _split_exact(exact)
+        nan = np.isnan(near)
+        zero = (near == 0) & (res == 0)
+        lo = hi = near
+        res_lo = res_hi = res
+    assert got.shape == lo.shape, (name, got.shape, lo.shape)
+    ng = np.isnan(got)
+    assert (ng == nan).all(), f'{name}: NaN pattern differs at {np.argwhere(ng != nan)[:5].tolist()}'
+    ok = ~nan
+    wrong = (np.signbit(got) != sign) & ok
+    assert not wrong.any(), (f'{name}: sign differs at {np.argwhere(wrong)[:5].tolist()}, '
+                             f'got {got[wrong][:5].tolist()}')
+    wrong = zero & (got != 0)
+    assert not wrong.any(), f'{name}: exact zero missed at {np.argwhere(wrong)[:5].tolist()}'
+    L = np.longdouble
+    with np.errstate(invalid='ignore', over='ignore'):
+        if got.dtype == np.float32:
+            # bounds rounded to float32 through the nearest float64: a double rounding can move a
+            # bound by one float32 step only when it lands on a float32 midpoint to within 2^-53
+            lo32 = ((lo.astype(L) + res_lo) - bound * ulp.astype(L)).astype(np.float64).astype(np.float32)
+            hi32 = ((hi.astype(L) + res_hi) + bound * ulp.astype(L)).astype(np.float64).astype(np.float32)
+            g = got.astype(L)
+            d = np.maximum(np.maximum(lo32.astype(L) - g, g - hi32.astype(L)), 0) / ulp.astype(L)
+        else:
+            g = got.astype(L)
+            d = np.maximum(np.abs((g - lo.astype(L)) - res_lo), np.abs((g - hi.astype(L)) - res_hi)) \
+                / ulp.astype(L)
+    d = np.where(ok, d, 0).astype(np.float64)
+    bad = d > (0 if got.dtype == np.float32 else bound)
+    if bad.any():
+        at = np.argwhere(bad)
+        first = tuple(at[0])
+        raise AssertionError(f'{name}: {len(at)} values beyond {bound} ulps, largest {d.max():.3f}, '
+                             f'first at {first}: got {got[first]!r}, exact ~ {lo[first]!r}')
+    return float(d.max()) if d.size else 0.0
 
 
 CONVERT_IN = ['game_id', 'original_event_id', 'action_id', 'period_id', 'time_seconds', 'team_id',

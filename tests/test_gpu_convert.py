@@ -194,8 +194,9 @@ def test_convert_scan_tiles(conv, tile_base, n, n_blocks):
 
 def test_convert_then_atomic_vaep(conv):
     """Chained drop-ins: convert_to_atomic on the GPU, then AtomicVAEP features / labels, vs
-    the oracle chain (convert restatement -> atomic VAEP restatement)."""
-    from golden_io import assert_close
+    the oracle chain (convert restatement -> atomic VAEP restatement): non-angle f64 columns bit
+    for bit, angles within ANGLE_ULPS + 1 ulps of numpy's (itself within 1 ulp of exact)."""
+    import value_cases as vc
     from oracle import atomic_convert_oracle as co
     from oracle import vaep_oracle as vo
     from socceraction_amd.atomic import vaep as avaep
@@ -209,11 +210,12 @@ def test_convert_then_atomic_vaep(conv):
     ref = vo.features(cols, 3, vo.ATOMIC_DEFAULT, atomic=True, home=[home])
     assert list(X.columns) == [c[0] for c in ref]
     for name, kind, v in ref:
-        if kind == 'f':
-            assert_close(X[name].to_numpy(), v, name)
-        else:
+        if kind != 'f':
             np.testing.assert_array_equal(X[name].to_numpy().astype(np.int64),
                                           np.asarray(v).astype(np.int64), err_msg=name)
+    fnames = [name for name, kind, _ in ref if kind == 'f']
+    vc.golden_angle_columns(fnames, np.stack([X[name].to_numpy() for name in fnames]),
+                            np.stack([v for _, kind, v in ref if kind == 'f']), 'convert -> features')
     Y = avaep.AtomicVAEP().compute_labels(pd.Series({'home_team_id': home}), atomic)
     lab = vo.labels(cols, atomic=True)
     np.testing.assert_array_equal(Y['scores'].to_numpy(), lab['scores'])
@@ -247,8 +249,9 @@ def test_convert_device_full_size(conv):
 
 def test_device_pipeline_convert_to_atomic_features(conv):
     """SPADL columns -> device conversion -> atomic ActionBatch (no host round trip) ->
-    Atomic-VAEP features + labels for 20 games, vs the oracle chain with per-game segments."""
-    from golden_io import assert_close
+    Atomic-VAEP features + labels for 20 games, vs the oracle chain with per-game segments:
+    non-angle f64 columns bit for bit, angles within ANGLE_ULPS + 1 ulps of numpy's."""
+    import value_cases as vc
     from oracle import atomic_convert_oracle as co
     from oracle import vaep_oracle as vo
     from socceraction_amd import ops, synthetic
@@ -272,13 +275,17 @@ def test_device_pipeline_convert_to_atomic_features(conv):
                      home=list(d['home_team_id']))
     blocks = dict(zip('bfi', fb.to_numpy()))
     assert fb.plan.names == [c[0] for c in rf]
+    fnames, fgot, fref = [], [], []
     for (name, kind, col), (_, _, rv) in zip(fb.plan.order, rf):
         got = blocks[kind][col, :ab.n]
         if kind == 'f':
-            assert_close(got, rv, name)
+            fnames.append(name)
+            fgot.append(got)
+            fref.append(rv)
         else:
             np.testing.assert_array_equal(got.astype(np.int64), np.asarray(rv).astype(np.int64),
                                           err_msg=name)
+    vc.golden_angle_columns(fnames, np.stack(fgot), np.stack(fref), 'device convert -> features')
     lab = vo.labels(cols, atomic=True, seg_off=so)
     np.testing.assert_array_equal(lb.scores[:ab.n].cpu().numpy().astype(bool), lab['scores'])
     np.testing.assert_array_equal(lb.concedes[:ab.n].cpu().numpy().astype(bool), lab['concedes'])

@@ -5,7 +5,8 @@ import numpy as np
 import pandas as pd
 import pytest
 
-from golden_io import assert_close, cases, frame, ks, load
+import value_cases as vc
+from golden_io import assert_close, assert_same_floats, cases, frame, ks, load
 
 pytestmark = pytest.mark.gpu
 
@@ -36,8 +37,8 @@ def _frame_equal(df, g, k):
             continue
         assert all(df[c].dtype == dt for c in cols), kind
         got = df[cols].to_numpy()
-        if kind == 'f':
-            assert_close(got, ref, 'features')
+        if kind == 'f':  # non-angle columns bit for bit, angles within ANGLE_ULPS + 1 of the golden
+            vc.golden_angle_columns(cols, got.T, ref.T, 'features')
         else:
             np.testing.assert_array_equal(got.astype(ref.dtype), ref)
     assert isinstance(df.index, pd.RangeIndex)
@@ -76,10 +77,8 @@ def test_compute_features_labels_rate(atomic):
             for c in v.columns:
                 ref = g[f'{c}_{tag}']
                 assert v[c].dtype == ref.dtype, (c, v[c].dtype)
-                if tag == '64':
-                    assert_close(v[c].to_numpy(), ref, c)
-                else:  # float32: bit-exact (the reference's f32 operations in its order)
-                    np.testing.assert_array_equal(v[c].to_numpy(), ref, err_msg=c)
+                # bit-exact, f64 and f32 (the reference's IEEE operations in its order)
+                assert_same_floats(v[c].to_numpy(), ref, c)
 
 
 def test_rate_errors():
@@ -136,12 +135,12 @@ def test_labels_and_formula_modules_single_segment():
                                   g['goal_from_shot'].astype(bool))
     v = formula.value(df, pd.Series(g['ps']), pd.Series(g['pc']))
     for c in v.columns:
-        assert_close(v[c].to_numpy(), g[f'{c}_64'], c)
+        assert_same_floats(v[c].to_numpy(), g[f'{c}_64'], c)
     v32 = formula.value(df, pd.Series(g['ps'].astype(np.float32)),
                         pd.Series(g['pc'].astype(np.float32)))
     assert v32.dtypes.eq(np.float32).all()
     off = formula.offensive_value(df, pd.Series(g['ps']), pd.Series(g['pc']))
-    assert_close(off.to_numpy(), g['offensive_value_64'], 'offensive')
+    assert_same_floats(off.to_numpy(), g['offensive_value_64'], 'offensive')
 
 
 def test_atomic_goal_from_shot_label():
@@ -182,7 +181,7 @@ def test_batched_api_equals_per_game(atomic):
     model._VAEP__models = {'scores': _FixedModel(np.concatenate([g['ps'] for g in gs])),
                            'concedes': _FixedModel(np.concatenate([g['pc'] for g in gs]))}
     v = model.rate_batch(games, actions, X)
-    assert_close(v['vaep_value'].to_numpy(), np.concatenate([g['vaep_value_64'] for g in gs]), 'vaep')
+    assert_same_floats(v['vaep_value'].to_numpy(), np.concatenate([g['vaep_value_64'] for g in gs]), 'vaep')
 
 
 @pytest.mark.parametrize('atomic', [False, True])

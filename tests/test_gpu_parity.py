@@ -1,12 +1,17 @@
 """GPU parity: the HIP kernels (through the C ABI) against the reference goldens and the oracle.
 
-Bar: bit-exact for ids, one-hots, labels, goal scores and counts; floats within
-|a-b| <= 1e-6*|ref| + 1e-12 (see golden_io.assert_close).
+Bar: bit-exact for ids, one-hots, labels, goal scores and counts, and for every f64 feature
+column that is not an angle and the f64 / f32 formula values (golden_io.assert_same_floats: the
+sign of zero counts).  The four angle families (atan / atan2) lie within value_cases.ANGLE_ULPS = 3
+ulps of the 200-bit value (measured on the MI355X: 1.38 / 1.42 ulp), or ANGLE_ULPS + 1 ulps of a
+golden of the reference.  The xT interpolated rates and grids keep golden_io.assert_close
+(|a-b| <= 1e-6*|ref| + 1e-12).
 """
 import numpy as np
 import pytest
 
-from golden_io import assert_close, cases, frame, inputs, ks, load
+import value_cases as vc
+from golden_io import assert_close, assert_same_floats, cases, frame, inputs, ks, load
 from oracle import vaep_oracle as vo
 from oracle import xt_oracle as xo
 
@@ -20,6 +25,24 @@ def sa():
     from socceraction_amd import _native, batch, catalog, ops, synthetic
     _native.load_library()
     return dict(batch=batch, catalog=catalog, ops=ops, synthetic=synthetic)
+
+
+def _columns_match(fb, ref, exact, rows, tag):
+    """Rows ``rows`` of the blocks against oracle columns ``ref`` with their 200-bit angles
+    ``exact``: integers and bools exact, non-angle floats bit for bit, angles within ANGLE_ULPS."""
+    assert fb.plan.names == [c[0] for c in ref], tag
+    blocks = {kk: fb.block(kk)[:, rows].cpu().numpy() for kk in 'bfi'}
+    fnames, fgot, fref = [], [], []
+    for (name, kind, col), (_, _, rv) in zip(fb.plan.order, ref):
+        got = blocks[kind][col]
+        if kind == 'f':
+            fnames.append(name)
+            fgot.append(got)
+            fref.append(rv)
+        else:
+            np.testing.assert_array_equal(got.astype(np.int64), np.asarray(rv).astype(np.int64),
+                                          err_msg=f'{name} {tag}')
+    vc.check_float_columns(fnames, np.stack(fgot), np.stack(fref), exact, tag)
 
 
 def _blocks_match(fb, g, k, n):
@@ -37,7 +60,7 @@ def _blocks_match(fb, g, k, n):
             continue
         M = np.stack(got[kind], axis=1)
         if kind == 'f':
-            assert_close(M, ref, f'k{k} f64 block')
+            vc.golden_angle_columns(list(g[f'k{k}_names_f']), M.T, ref.T, f'k{k} f64 block')
         else:
             np.testing.assert_array_equal(M.astype(ref.dtype), ref, err_msg=f'k{k} {kind} block')
 
@@ -65,10 +88,8 @@ def test_features_labels_formula_goldens(sa, atomic):
             pc = torch.tensor(g['pc'], dtype=dt, device=ab.device)
             v = ops.formula(ab, ps, pc).cpu().numpy()[:, :n]
             for r, c in enumerate(('offensive_value', 'defensive_value', 'vaep_value')):
-                if dt == torch.float32:  # a few IEEE f32 ops in the reference's order: bit-exact
-                    np.testing.assert_array_equal(v[r], g[f'{c}_{tag}'], err_msg=f'{name} {c}')
-                else:
-                    assert_close(v[r], g[f'{c}_{tag}'], f'{name} {c}')
+                # a few IEEE operations in the reference's order, f32 and f64 alike: bit-exact
+                assert_same_floats(v[r], g[f'{c}_{tag}'], f'{name} {c}')
 
 
 @pytest.mark.parametrize('atomic', [False, True])
@@ -106,14 +127,14 @@ def test_batched_segments_match_per_game(sa, atomic):
             M = np.stack(cols, axis=1)
             ref = g[f'k3_feat_{kind}']
             if kind == 'f':
-                assert_close(M, ref, 'batched f64')
+                vc.golden_angle_columns(list(g['k3_names_f']), M.T, ref.T, 'batched f64')
             else:
                 np.testing.assert_array_equal(M.astype(ref.dtype), ref)
         np.testing.assert_array_equal(lb.scores[sl].cpu().numpy(), g['scores'])
         np.testing.assert_array_equal(lb.concedes[sl].cpu().numpy(), g['concedes'])
         np.testing.assert_array_equal(lb.goal_from_shot[sl].cpu().numpy(), g['goal_from_shot'])
         for r, c in enumerate(('offensive_value', 'defensive_value', 'vaep_value')):
-            assert_close(v[r, sl], g[f'{c}_64'], c)
+            assert_same_floats(v[r, sl], g[f'{c}_64'], c)
         o += n
 
 
@@ -206,18 +227,12 @@ def test_many_small_segments_vs_oracle(sa, atomic):
               'type_id', 'result_id', 'bodypart_id'))
     cols = {c: d[c] for c in names}
     for k in (1, 3, 5):
-        ref = vo.features(cols, k, default, atomic=atomic, seg_off=so, home=d['home_team_id'])
+        W = vo.windows(cols, k, atomic, so, d['home_team_id'])
+        ref = vo.features_frames(W, default, atomic, seg_off=so)
+        exact = vc.exact_angles_frames(W, atomic)
         for Rb, Rn in ((1024, 128), (None, None)):
             fb = ops.features(ab, default, k, bool_tile=Rb, num_tile=Rn)
-            assert fb.plan.names == [c[0] for c in ref]
-            blocks = {kk: fb.block(kk)[:, :n].cpu().numpy() for kk in 'bfi'}
-            for (name, kind, col), (_, _, rv) in zip(fb.plan.order, ref):
-                got = blocks[kind][col]
-                if kind == 'f':
-                    assert_close(got, rv, f'{name} k={k}')
-                else:
-                    np.testing.assert_array_equal(got.astype(np.int64), rv.astype(np.int64),
-                                                  err_msg=f'{name} k={k} {Rb}')
+            _columns_match(fb, ref, exact, slice(0, n), f'k={k} {Rb}')
     for nr in (10, 20):
         lb = ops.labels(ab, nr_actions=nr)
         lab = vo.labels(cols, atomic=atomic, nr_actions=nr, seg_off=so)
@@ -237,10 +252,8 @@ def test_many_small_segments_vs_oracle(sa, atomic):
             np.testing.assert_array_equal(vf.cpu().numpy()[:, :n], v)
         fo = vo.formula(cols, ps, pc, atomic=atomic, seg_off=so)
         for r, c in enumerate(('offensive_value', 'defensive_value', 'vaep_value')):
-            if dt == np.float32:  # bit-exact (the reference's f32 operations in its order)
-                np.testing.assert_array_equal(v[r], fo[c], err_msg=c)
-            else:
-                assert_close(v[r], fo[c], c)
+            # bit-exact (the reference's IEEE operations in its order), f32 and f64 alike
+            assert_same_floats(v[r], fo[c], c)
 
 
 def test_explicit_frames_match_windowed(sa):
@@ -478,21 +491,16 @@ def test_full_size_sampled_games_vs_oracle(sa):
         cols = {c: d[c][s:e] for c in ('period_id', 'time_seconds', 'team_id', 'start_x',
                                        'start_y', 'end_x', 'end_y', 'type_id', 'result_id',
                                        'bodypart_id')}
-        ref = vo.features(cols, 3, vo.SPADL_DEFAULT, home=[d['home_team_id'][g]])
+        W = vo.windows(cols, 3, False, None, [d['home_team_id'][g]])
+        ref = vo.features_frames(W, vo.SPADL_DEFAULT)
         assert [c[0] for c in ref] == names
-        blocks = {k: fb.block(k)[:, s:e].cpu().numpy() for k in 'bfi'}
-        for (name, kind, col), (_, _, rv) in zip(plan.order, ref):
-            got = blocks[kind][col]
-            if kind == 'f':
-                assert_close(got, rv, name)
-            else:
-                np.testing.assert_array_equal(got.astype(np.int64), rv.astype(np.int64), err_msg=name)
+        _columns_match(fb, ref, vc.exact_angles_frames(W, False), slice(s, e), f'game {g}')
         lab = vo.labels(cols)
         np.testing.assert_array_equal(lb.scores[s:e].cpu().numpy().astype(bool), lab['scores'])
         np.testing.assert_array_equal(lb.concedes[s:e].cpu().numpy().astype(bool), lab['concedes'])
         fo = vo.formula(cols, p['scores'][s:e], p['concedes'][s:e])
         for r, c in enumerate(('offensive_value', 'defensive_value', 'vaep_value')):
-            assert_close(val[r, s:e].cpu().numpy(), fo[c], c)
+            assert_same_floats(val[r, s:e].cpu().numpy(), fo[c], c)
 
 
 @pytest.mark.parametrize('l,w,games', [(16, 12, 300), (30, 20, 60), (64, 64, 40), (1, 1, 5)])
@@ -562,15 +570,10 @@ def test_atomic_cfg3_slice_sampled_games_vs_oracle(sa):
     for g in rng.choice(len(off) - 1, 12, replace=False):
         s, e = int(off[g]), int(off[g + 1])
         cols = {c: d[c][s:e] for c in names}
-        ref = vo.features(cols, 3, vo.ATOMIC_DEFAULT, atomic=True, home=[d['home_team_id'][g]])
+        W = vo.windows(cols, 3, True, None, [d['home_team_id'][g]])
+        ref = vo.features_frames(W, vo.ATOMIC_DEFAULT, True)
         assert [c[0] for c in ref] == plan.names
-        blocks = {k: fb.block(k)[:, s:e].cpu().numpy() for k in 'bfi'}
-        for (name, kind, col), (_, _, rv) in zip(plan.order, ref):
-            got = blocks[kind][col]
-            if kind == 'f':
-                assert_close(got, rv, name)
-            else:
-                np.testing.assert_array_equal(got.astype(np.int64), rv.astype(np.int64), err_msg=name)
+        _columns_match(fb, ref, vc.exact_angles_frames(W, True), slice(s, e), f'game {g}')
         lab = vo.labels(cols, atomic=True)
         for c in ('scores', 'concedes', 'goal_from_shot'):
             np.testing.assert_array_equal(getattr(lb, c)[s:e].cpu().numpy().astype(bool), lab[c])

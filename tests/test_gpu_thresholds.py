@@ -15,8 +15,9 @@ inputs of tests/threshold_cases.py sit ON them:
 Every device result is compared with ``oracle/`` and with the reference's own outputs
 (tests/golden/make_golden_thresholds.py), never with another device path.  Bars: ids, counts,
 cells, rows and dtypes bit-exact; xT rates bit-exact (surfaces of small integers: every rate is
-an exact integer difference that names the cell pair); formula values float32 bit-exact, float64
-within golden_io.assert_close (one wrong decision moves a value by at least 0.1).  The unmarked
+an exact integer difference that names the cell pair); formula values bit-exact, float32 and
+float64 (golden_io.assert_same_floats; one wrong decision moves a value by at least 0.1); the
+interpolated xT rates within golden_io.assert_close.  The unmarked
 tests hold the inputs to a coverage floor, so a later edit of the value sets cannot hollow the
 device tests out, and the oracle to the goldens.
 
@@ -34,7 +35,7 @@ import pandas as pd
 import pytest
 
 import threshold_cases as tc
-from golden_io import GOLDEN, assert_close, assert_frame_same, dribbles_frame, load
+from golden_io import GOLDEN, assert_close, assert_frame_same, assert_same_floats, dribbles_frame, load
 from oracle import atomic_convert_oracle as co
 from oracle import vaep_oracle as vo
 from oracle import xt_oracle as xo
@@ -195,10 +196,7 @@ def test_formula_oracle_reproduces_the_samephase_golden():
         v = vo.formula(cols, g['ps'].astype(dt), g['pc'].astype(dt), seg_off=g['game_off'])
         for c in VALUES:
             assert v[c].dtype == dt
-            if dt == np.float32:
-                np.testing.assert_array_equal(v[c], g[f'{c}_{tag}'], err_msg=c)
-            else:
-                assert_close(v[c], g[f'{c}_{tag}'], c)
+            assert_same_floats(v[c], g[f'{c}_{tag}'], c)
     # the rule took both branches on the threshold pairs
     t = g['in_time_seconds']
     assert (np.abs(np.diff(t)) == 10.0).any() and (np.abs(np.diff(t)) > 10.0).any()
@@ -536,10 +534,8 @@ def _same_values(v, ref, n, dt, what):
     v = v.cpu().numpy()[:, :n]
     for r, c in enumerate(VALUES):
         assert v[r].dtype == dt
-        if dt == np.float32:   # a few IEEE f32 operations in the reference's order: bit-exact
-            np.testing.assert_array_equal(v[r], ref[c], err_msg=f'{what} {c}')
-        else:
-            assert_close(v[r], ref[c], f'{what} {c}')
+        # a few IEEE operations in the reference's order, f32 and f64 alike: bit-exact
+        assert_same_floats(v[r], ref[c], f'{what} {c}')
 
 
 @gpu

@@ -1,0 +1,332 @@
+"""The float outputs of csrc/sa_vaep.hip held to the reference bit for bit: every f64 feature
+column that is not an angle, its float32 form and the f64 / f32 formula values must equal the
+oracle (numpy) in every bit, the sign of zero included; the four angle families must lie within
+``value_cases.ANGLE_ULPS`` ulps of the 200-bit value.  The inputs are the value batch of
+tests/value_cases.py (coordinates on, next to and beyond the goal point and line, NaN, inf,
+subnormals, signed zeros, every one in windows 0, 1 and 2 under both flip states);
+tests/test_values_host.py holds the conditions on those inputs, and shows that the assertions used
+here reject a float32 arctan, a float32 sqrt, a contracted sum of squares and four wrong special
+cases.
+
+Every test prints the largest angle distance it saw (run with ``-s``)."""
+import copy
+
+import numpy as np
+import pytest
+
+import value_cases as vc
+from golden_io import assert_same_floats, load
+from oracle import vaep_oracle as vo
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip('torch')
+
+PACKAGES = [False, True]
+KS = (1, 2, 3)
+LAYOUTS = ((None, None), (1024, 128))   # plain, tiled
+LABELS = ('scores', 'concedes', 'goal_from_shot')
+_DTYPES = {'b': np.bool_, 'f': np.float64, 'i': np.int64}
+
+
+@pytest.fixture(scope='module')
+def sa():
+    from socceraction_amd import _native, batch, ops
+    _native.load_library()
+    return dict(batch=batch, ops=ops)
+
+
+def _xfns(atomic):
+    return vo.ATOMIC_DEFAULT if atomic else vo.SPADL_DEFAULT
+
+
+_BATCHES, _REFS, _FORMULAS = {}, {}, {}
+
+
+def _batch(sa, atomic, contiguous=False):
+    if (atomic, contiguous) not in _BATCHES:
+        d = vc.batch(atomic)
+        ab = sa['batch'].ActionBatch.from_columns({c: v.copy() for c, v in d.items()}, atomic=atomic,
+                                                  contiguous=contiguous)
+        assert ab.n == vc.N_ROWS and ab.n_segments == len(d['game_off']) - 1
+        _BATCHES[atomic, contiguous] = ab
+    return _BATCHES[atomic, contiguous]
+
+
+def _stack(cols, exact):
+    """Oracle columns -> (names, kinds, {kind: [n_cols, n] matrix}, exact angles), never modified."""
+    mats = {}
+    for kind in 'bfi':
+        sel = [v for _, kk, v in cols if kk == kind]
+        mats[kind] = np.stack(sel).astype(_DTYPES[kind]) if sel else None
+    return [c[0] for c in cols], [c[1] for c in cols], mats, exact
+
+
+def _ref(atomic, k):
+    """The oracle's features of the value batch at depth k and the 200-bit angles: once."""
+    if (atomic, k) not in _REFS:
+        d = vc.batch(atomic)
+        W = vo.windows(vc.cols_of(d, atomic), k, atomic, d['game_off'], d['home_team_id'])
+        _REFS[atomic, k] = _stack(vo.features_frames(W, _xfns(atomic), atomic, d['game_off']),
+                                  vc.exact_angles_frames(W, atomic))
+    return _REFS[atomic, k]
+
+
+def _formula(sa, atomic, dtype):
+    """(the oracle's formula, device ps, pc) of the value batch with the edge probabilities."""
+    if (atomic, dtype) not in _FORMULAS:
+        d = vc.batch(atomic)
+        ps, pc = vc.probabilities(vc.N_ROWS, dtype)
+        fo = vo.formula(vc.cols_of(d, atomic), ps, pc, atomic=atomic, seg_off=d['game_off'])
+        dev = _batch(sa, atomic).device
+        _FORMULAS[atomic, dtype] = fo, torch.from_numpy(ps).to(dev), torch.from_numpy(pc).to(dev)
+    return _FORMULAS[atomic, dtype]
+
+
+def _check_blocks(fb, ref, tag, bools=True):
+    """Every column, every row: bools and integers exact, floats by value_cases.check_float_columns.
+    Returns the largest angle distance."""
+    names, rkinds, mats, exact = ref
+    assert fb.plan.names == names, tag
+    assert [kk for _, kk, _ in fb.plan.order] == rkinds, tag
+    worst = 0.0
+    for kind in ('bfi' if bools else 'fi'):
+        idx = [col for _, kk, col in fb.plan.order if kk == kind]
+        got = fb.block(kind)[idx].cpu().numpy()
+        assert got.shape == mats[kind].shape, (tag, kind)
+        if kind == 'f':
+            assert got.dtype == np.float64
+            fnames = [nm for nm, kk in zip(names, rkinds) if kk == 'f']
+            worst = vc.check_float_columns(fnames, got, mats['f'], exact, f'{tag} f64 block')
+        else:
+            np.testing.assert_array_equal(got.astype(np.int64), mats[kind].astype(np.int64),
+                                          err_msg=f'{tag} {kind} block')
+    return worst
+
+
+def _check_labels(lab, atomic, nr, n, tag):
+    d = vc.batch(atomic)
+    ref = vo.labels(vc.cols_of(d, atomic), atomic=atomic, nr_actions=nr, seg_off=d['game_off'])
+    for c in LABELS:
+        got = getattr(lab, c)[:n].cpu().numpy()
+        assert set(np.unique(got).tolist()) <= {0, 1}, (tag, c)
+        np.testing.assert_array_equal(got.astype(bool), ref[c], err_msg=f'{tag} {c}')
+
+
+def _check_values(v, fo, n, dtype, tag):
+    v = v.cpu().numpy()[:, :n]
+    for r, c in enumerate(vc.VALUES):
+        assert fo[c].dtype == dtype and v[r].dtype == dtype
+        assert_same_floats(v[r], fo[c], f'{tag} {c}')
+
+
+# ------------------------------------------------------------------------------- feature forms
+@pytest.mark.parametrize('k', KS)
+@pytest.mark.parametrize('atomic', PACKAGES)
+def test_feature_forms_vs_oracle(sa, atomic, k):
+    """ops.features at k = 1, 2, 3, plain and tiled, from the pooled and from the physically
+    contiguous action batch, and the bitmap form's numeric blocks."""
+    ops = sa['ops']
+    ref = _ref(atomic, k)
+    worst = 0.0
+    for contiguous in (False, True):
+        ab = _batch(sa, atomic, contiguous)
+        for Rb, Rn in LAYOUTS:
+            fb = ops.features(ab, _xfns(atomic), k, bool_tile=Rb, num_tile=Rn)
+            if Rn is not None:
+                assert fb.f64_block.shape[0] == -(-ab.n // Rn) > 1
+            worst = max(worst, _check_blocks(
+                fb, ref, f'atomic={atomic} k={k} contiguous={contiguous} tiles={Rb}/{Rn}'))
+    fb = ops.features(_batch(sa, atomic), _xfns(atomic), k, num_tile=128, bool_bits=True)
+    worst = max(worst, _check_blocks(fb, ref, f'atomic={atomic} k={k} bitmap form', bools=False))
+    print(f'features atomic={atomic} k={k}: largest angle distance {worst:.3f} ulps')
+    assert worst <= vc.ANGLE_ULPS
+
+
+@pytest.mark.parametrize('k', KS)
+@pytest.mark.parametrize('atomic', PACKAGES)
+def test_float32_numeric_block_vs_oracle(sa, atomic, k):
+    """features_bits_f32: every non-angle column == the ORACLE's f64 column rounded to float32,
+    every integer column == its exact cast, angles inside the float32 bracket of the 200-bit value
+    +- ANGLE_ULPS float64 ulps.  Nothing here reads the device's own f64 block."""
+    ops = sa['ops']
+    names, kinds, mats, exact = _ref(atomic, k)
+    ab = _batch(sa, atomic)
+    for Rn in (None, 128):
+        tag = f'float32 atomic={atomic} k={k} tile={Rn}'
+        fb = ops.features(ab, _xfns(atomic), k, num_tile=Rn, bool_bits=True, num32=True)
+        assert fb.num32 and fb.plan.names == names
+        fidx = [col for _, kk, col in fb.plan.order if kk == 'f']
+        got = fb.block('f')[fidx].cpu().numpy()
+        assert got.dtype == np.float32
+        with np.errstate(over='ignore'):
+            want = mats['f'].astype(np.float32)   # round to nearest even; 1e200 -> inf
+        fnames = [nm for nm, kk in zip(names, kinds) if kk == 'f']
+        worst = vc.check_float_columns(fnames, got, want, exact, tag)
+        iidx = [col for _, kk, col in fb.plan.order if kk == 'i']
+        goti = fb.block('i')[iidx].cpu().numpy()
+        assert goti.dtype == np.float32
+        assert_same_floats(goti, mats['i'].astype(np.float32), tag + ' integer columns')
+    assert (np.isinf(want) & ~np.isinf(mats['f'])).any()   # the overflow to inf is among them
+    print(f'{tag}: angles outside their float32 bracket by {worst:.3f} ulps')
+
+
+# ------------------------------------------------------------------------------- fused step
+@pytest.mark.parametrize('k', KS)
+@pytest.mark.parametrize('atomic', PACKAGES)
+def test_step_vs_oracle(sa, atomic, k):
+    """sa_vaep_step_f64: features as above, labels exact, the f64 offensive / defensive / vaep
+    values == the oracle's formula bit for bit (-0.0 on every segment's first row)."""
+    ops = sa['ops']
+    ab = _batch(sa, atomic)
+    n = ab.n
+    fo, tps, tpc = _formula(sa, atomic, np.float64)
+    plan = ops.build_plan(_xfns(atomic), k, atomic)
+    ld = -(-n // 16) * 16
+    worst = 0.0
+    for Rb, Rn in LAYOUTS:
+        for nr in (10, 3):
+            tag = f'step atomic={atomic} k={k} nr={nr} tiles={Rb}/{Rn}'
+            out = ops.alloc_feature_blocks(plan, n, ab.device, Rb, Rn)
+            buf = torch.full((3, ld), 7, dtype=torch.uint8, device=ab.device)
+            lab = ops.LabelBlocks(n, buf[0], buf[1], buf[2])
+            val = torch.full((3, ld), float('nan'), dtype=torch.float64, device=ab.device)
+            ops.step_into(ab.struct(), out, tps, tpc, nr, lab, val)
+            worst = max(worst, _check_blocks(out, _ref(atomic, k), tag))
+            _check_labels(lab, atomic, nr, n, tag)
+            _check_values(val, fo, n, np.float64, tag)
+    print(f'step atomic={atomic} k={k}: largest angle distance {worst:.3f} ulps')
+    assert worst <= vc.ANGLE_ULPS
+
+
+@pytest.mark.parametrize('chunk', [512, 1024])
+def test_chunked_step_vs_oracle(sa, chunk):
+    """sa_vaep_step_f64_chunked (SPADL, the numeric pass in launches of ``chunk`` rows): numeric
+    blocks, labels and f64 values as above."""
+    ops = sa['ops']
+    ab = _batch(sa, False)
+    n = ab.n
+    fo, tps, tpc = _formula(sa, False, np.float64)
+    plan = ops.build_plan(vo.SPADL_DEFAULT, 3, False)
+    num = copy.copy(plan)   # the chunked step is the numeric pass only
+    num.struct = copy.deepcopy(plan.struct)
+    for x in range(len(num.struct.bool_col)):
+        num.struct.bool_col[x] = -1
+    blk = ops.alloc_feature_blocks(plan, n, ab.device, 1024, 128)
+    blk.f64_block.fill_(float('nan'))
+    blk.i64_block.fill_(-7)
+    view = ops.FeatureBlocks(num, n, blk.Rb, blk.Rn, blk.bool_block, blk.f64_block, blk.i64_block)
+    ld = -(-n // 16) * 16
+    buf = torch.full((3, ld), 7, dtype=torch.uint8, device=ab.device)
+    lab = ops.LabelBlocks(n, buf[0], buf[1], buf[2])
+    val = torch.full((3, ld), float('nan'), dtype=torch.float64, device=ab.device)
+    ops.step_into(ab.struct(), view, tps, tpc, 10, lab, val, chunk_rows=chunk)
+    tag = f'chunked step {chunk}'
+    worst = _check_blocks(blk, _ref(False, 3), tag, bools=False)
+    _check_labels(lab, False, 10, n, tag)
+    _check_values(val, fo, n, np.float64, tag)
+    print(f'{tag}: largest angle distance {worst:.3f} ulps')
+
+
+# ------------------------------------------------------------------------------- formula alone
+@pytest.mark.parametrize('dtype', [np.float64, np.float32])
+@pytest.mark.parametrize('atomic', PACKAGES)
+def test_formula_vs_oracle(sa, atomic, dtype):
+    """ops.formula and ops.labels_formula, f64 and f32, with probabilities of 0, 1, the smallest
+    subnormal and 1 - 2^-53 among full-precision draws: bit for bit."""
+    ops = sa['ops']
+    ab = _batch(sa, atomic)
+    fo, tps, tpc = _formula(sa, atomic, dtype)
+    assert tps.dtype == (torch.float64 if dtype == np.float64 else torch.float32)
+    tag = f'atomic={atomic} {np.dtype(dtype).name}'
+    _check_values(ops.formula(ab, tps, tpc), fo, ab.n, dtype, f'formula {tag}')
+    lab, val = ops.labels_formula(ab, tps, tpc)
+    _check_values(val, fo, ab.n, dtype, f'labels_formula {tag}')
+    _check_labels(lab, atomic, 10, ab.n, f'labels_formula {tag}')
+    neg0 = np.signbit(fo['defensive_value']) & (fo['defensive_value'] == 0)
+    assert neg0[vc.batch(atomic)['game_off'][:-1]].any()   # -0.0 is among the values
+
+
+# ------------------------------------------------------------------------------- explicit frames
+@pytest.mark.parametrize('k', (2, 3))
+@pytest.mark.parametrize('atomic', PACKAGES)
+def test_explicit_frames_vs_oracle(sa, atomic, k):
+    """Explicit-frame mode on host-built game states of the value batch: frame 0 = the batch's
+    rows, frame i the same rows under a seeded permutation (no shifts of one another), so every
+    special row meets ordinary rows in the other frames."""
+    B, ops = sa['batch'], sa['ops']
+    frames = vc.permuted_frames(k, atomic)
+    cols = [{c: f[c].to_numpy() for c in (vc.ATOMIC_COLS if atomic else vc.SPADL_COLS)} for f in frames]
+    ref = _stack(vo.features_frames(cols, _xfns(atomic), atomic), vc.exact_angles_frames(cols, atomic))
+    fb = ops.features_explicit(B.frames_batches(frames, atomic=atomic), _xfns(atomic))
+    assert fb.n == vc.N_ROWS
+    worst = _check_blocks(fb, ref, f'explicit atomic={atomic} k={k}')
+    print(f'explicit atomic={atomic} k={k}: largest angle distance {worst:.3f} ulps')
+    assert worst <= vc.ANGLE_ULPS
+
+
+# ------------------------------------------------------------------------------- public path, goldens
+class _Game:
+    home_team_id = vc.GOLDEN_HOME
+
+
+def _model(atomic):
+    if atomic:
+        from socceraction_amd.atomic.vaep import AtomicVAEP as Model
+    else:
+        from socceraction_amd.vaep import VAEP as Model
+    return Model
+
+
+@pytest.mark.parametrize('atomic', PACKAGES)
+def test_public_compute_features_vs_oracle(sa, atomic):
+    """VAEP.compute_features / AtomicVAEP.compute_features on one game holding the special rows:
+    the frame's f64 columns at the same bars."""
+    df = vc.golden_game(atomic)
+    X = _model(atomic)(nb_prev_actions=3).compute_features(_Game(), df)
+    cols = {c: df[c].to_numpy() for c in (vc.ATOMIC_COLS if atomic else vc.SPADL_COLS)}
+    W = vo.windows(cols, 3, atomic, None, [vc.GOLDEN_HOME])
+    ref = vo.features_frames(W, _xfns(atomic), atomic)
+    assert list(X.columns) == [c[0] for c in ref] and len(X) == len(df)
+    fnames = [nm for nm, kind, _ in ref if kind == 'f']
+    for nm, kind, v in ref:
+        assert X[nm].dtype == _DTYPES[kind], nm
+        if kind != 'f':
+            np.testing.assert_array_equal(X[nm].to_numpy(), v.astype(_DTYPES[kind]), err_msg=nm)
+    worst = vc.check_float_columns(fnames, np.stack([X[nm].to_numpy() for nm in fnames]),
+                                   np.stack([v for _, kind, v in ref if kind == 'f']),
+                                   vc.exact_angles_frames(W, atomic), f'compute_features atomic={atomic}')
+    print(f'compute_features atomic={atomic}: largest angle distance {worst:.3f} ulps')
+    assert worst <= vc.ANGLE_ULPS
+
+
+@pytest.mark.parametrize('atomic', PACKAGES)
+def test_values_goldens(sa, atomic):
+    """The device against the reference's own outputs on the special rows
+    (tests/golden/{spadl,atomic}_values.npz): non-angle f64 columns bit for bit, angles within
+    ANGLE_ULPS + 1 ulps of the golden (itself within 1 ulp of exact, tests/test_values_host.py),
+    integers, bools and labels exact, the f64 and f32 formula bit for bit."""
+    B, ops = sa['batch'], sa['ops']
+    prefix = 'atomic' if atomic else 'spadl'
+    g = load(prefix, 'values')
+    df = vc.golden_game(atomic)
+    n = len(df)
+    ab = B.ActionBatch.from_frame(df, atomic=atomic, home_team_id=vc.GOLDEN_HOME)
+    fb = ops.features(ab, _xfns(atomic), 3)
+    assert fb.plan.names == list(g['k3_names_all'])
+    for kind in 'bi':
+        idx = [col for _, kk, col in fb.plan.order if kk == kind]
+        np.testing.assert_array_equal(fb.block(kind)[idx].cpu().numpy().T.astype(g[f'k3_feat_{kind}'].dtype),
+                                      g[f'k3_feat_{kind}'], err_msg=kind)
+    fidx = [col for _, kk, col in fb.plan.order if kk == 'f']
+    worst = vc.golden_angle_columns(list(g['k3_names_f']), fb.block('f')[fidx].cpu().numpy(),
+                                    np.ascontiguousarray(g['k3_feat_f'].T), f'{prefix} values golden')
+    lb = ops.labels(ab)
+    for c in LABELS:
+        np.testing.assert_array_equal(getattr(lb, c)[:n].cpu().numpy(), g[c], err_msg=c)
+    for tag, dt in (('64', np.float64), ('32', np.float32)):
+        ps = torch.from_numpy(g['ps'].astype(dt)).to(ab.device)
+        pc = torch.from_numpy(g['pc'].astype(dt)).to(ab.device)
+        _check_values(ops.formula(ab, ps, pc), {c: g[f'{c}_{tag}'] for c in vc.VALUES}, n, dt,
+                      f'{prefix} values golden {tag}')
+    print(f'{prefix} values golden: largest angle distance from the golden {worst:.3f} ulps')

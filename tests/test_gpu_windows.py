@@ -5,7 +5,9 @@ segments shorter than, equal to and longer than every window depth and look-ahea
 tests/test_windows_host.py asserts those conditions on the inputs.
 
 No row and no column is left out.  Ids, one-hots, bitmaps, labels and goal scores are bit-exact;
-f64 features and the f64 formula meet golden_io.assert_close; the f32 formula is bit-exact.
+so are the f64 feature columns that are not angles and the f64 and f32 formula
+(golden_io.assert_same_floats); the angle columns lie within value_cases.ANGLE_ULPS ulps of the
+200-bit value (one more against a golden of the reference).
 
 The instantiations ``launch_features`` picks from, SPADL and atomic each, and the test here that
 checks them against the oracle or the reference:
@@ -39,8 +41,9 @@ test_step_vs_oracle checks through the same call.
 import numpy as np
 import pytest
 
+import value_cases as vc
 import window_cases as wc
-from golden_io import assert_close
+from golden_io import assert_same_floats
 from oracle import vaep_oracle as vo
 
 pytestmark = pytest.mark.gpu
@@ -87,21 +90,28 @@ def _batch(sa, atomic, strings=False):
     return _BATCHES[key]
 
 
-def _stack(cols):
-    """Oracle columns -> (names, kinds, {kind: [n_cols, n] matrix}) in the oracle's order."""
+def _stack(cols, exact):
+    """Oracle columns -> (names, kinds, {kind: [n_cols, n] matrix}, exact angles) in the oracle's
+    order; ``exact`` = the 200-bit angle columns by name, or None when the columns are a golden."""
     mats = {}
     for kind in 'bfi':
         sel = [v for _, kk, v in cols if kk == kind]
         mats[kind] = np.stack(sel).astype(_DTYPES[kind]) if sel else None
-    return [c[0] for c in cols], [c[1] for c in cols], mats
+    return [c[0] for c in cols], [c[1] for c in cols], mats, exact
+
+
+def _frames_ref(frames, atomic, seg_off=None):
+    """The oracle's features of a list of game-state frames and their 200-bit angles."""
+    return _stack(vo.features_frames(frames, _xfns(atomic), atomic, seg_off=seg_off),
+                  vc.exact_angles_frames(frames, atomic))
 
 
 def _ref(atomic, k):
     """The oracle's features of the edge batch at depth k: computed once, never modified."""
     if (atomic, k) not in _REFS:
         d = wc.batch(atomic)
-        _REFS[atomic, k] = _stack(vo.features(wc.cols_of(d, atomic), k, _xfns(atomic), atomic=atomic,
-                                              seg_off=d['game_off'], home=d['home_team_id']))
+        W = vo.windows(wc.cols_of(d, atomic), k, atomic, d['game_off'], d['home_team_id'])
+        _REFS[atomic, k] = _frames_ref(W, atomic, d['game_off'])
     return _REFS[atomic, k]
 
 
@@ -115,7 +125,7 @@ def _ref_labels(atomic, nr):
 
 def _check_blocks(fb, ref, tag, kinds='bfi'):
     """Every column of the blocks ``kinds`` of ``fb``, every row, against stacked oracle columns."""
-    names, rkinds, mats = ref
+    names, rkinds, mats, exact = ref
     assert fb.plan.names == names, tag
     assert [kk for _, kk, _ in fb.plan.order] == rkinds, tag
     for kind in kinds:
@@ -126,7 +136,11 @@ def _check_blocks(fb, ref, tag, kinds='bfi'):
         got = fb.block(kind)[idx].cpu().numpy()
         assert got.shape == mats[kind].shape, (tag, kind)
         if kind == 'f':
-            assert_close(got, mats[kind], f'{tag} f64 block')
+            fnames = [nm for nm, kk in zip(names, rkinds) if kk == 'f']
+            if exact is None:
+                vc.golden_angle_columns(fnames, got, mats[kind], f'{tag} f64 block')
+            else:
+                vc.check_float_columns(fnames, got, mats[kind], exact, f'{tag} f64 block')
         else:
             np.testing.assert_array_equal(got.astype(np.int64), mats[kind].astype(np.int64),
                                           err_msg=f'{tag} {kind} block')
@@ -152,10 +166,8 @@ def _check_values(v, ref, n, dtype, tag):
     v = v.cpu().numpy()[:, :n]
     for r, c in enumerate(VALUES):
         assert ref[c].dtype == dtype
-        if dtype == np.float32:  # the reference's f32 operations in its order: bit-exact
-            np.testing.assert_array_equal(v[r], ref[c], err_msg=f'{tag} {c}')
-        else:
-            assert_close(v[r], ref[c], f'{tag} {c}')
+        # the reference's IEEE operations in its order, f32 and f64 alike: bit-exact, -0.0 included
+        assert_same_floats(v[r], ref[c], f'{tag} {c}')
 
 
 def _probs(sa, atomic, dtype):
@@ -211,8 +223,10 @@ def test_bool_bitmaps_vs_oracle(sa, atomic, k):
 # ------------------------------------------------------------------ float32 and condition forms
 @pytest.mark.parametrize('atomic', PACKAGES)
 def test_float32_and_condition_forms(sa, atomic):
-    """k = 3 on the edge batch: the bitmap form's blocks == the oracle; ``num32=True`` == those
-    f64 / i64 blocks cast to float32, with the same bitmaps; and trees.predict_pair_conditions
+    """k = 3 on the edge batch: the bitmap form's blocks == the oracle; ``num32=True`` == the
+    ORACLE's f64 / i64 columns cast to float32 (angles: the float32 bracket of the 200-bit value
+    +- ANGLE_ULPS float64 ulps) and, second, the device's own f64 / i64 blocks cast down, with the
+    same bitmaps; and trees.predict_pair_conditions
     (the COND numeric pass + the staged walk over condition bitmaps) of two small xgboost-shaped
     learners == each learner's staged walk over the checked blocks, bit for bit."""
     ops, trees = sa['ops'], sa['trees']
@@ -224,8 +238,17 @@ def test_float32_and_condition_forms(sa, atomic):
     got = ops.features(ab, _xfns(atomic), 3, num_tile=wc.SEG_BLOCK, bool_bits=True, num32=True)
     assert got.num32 and not chk.num32
     assert torch.equal(got.bool_bits, chk.bool_bits)
+    names, rkinds, mats, exact = ref
     for kind in 'fi':
         assert got.block(kind).dtype == torch.float32
+        idx = [col for _, kk, col in got.plan.order if kk == kind]
+        g32 = got.block(kind)[idx].cpu().numpy()
+        want = mats[kind].astype(np.float32)
+        if kind == 'f':
+            vc.check_float_columns([nm for nm, kk in zip(names, rkinds) if kk == 'f'], g32, want,
+                                   exact, f'atomic={atomic} float32 block')
+        else:
+            assert_same_floats(g32, want, f'atomic={atomic} float32 integer columns')
         assert torch.equal(got.block(kind), chk.block(kind).to(torch.float32)), kind
     kinds = [kk for _, kk, _ in chk.plan.order]
     models = [trees.TreeEnsemble.from_model(trees.synthetic_xgboost_json(
@@ -361,12 +384,12 @@ def test_explicit_frames_goldens(sa, atomic):
         mats = {}
         for kind in 'bfi':
             m = g[f'{tag}_feat_{kind}']
-            mats[kind] = m.T.astype(_DTYPES[kind]) if m.shape[1] else None
+            mats[kind] = np.ascontiguousarray(m.T.astype(_DTYPES[kind])) if m.shape[1] else None
         # the golden's blocks hold each kind's columns in frame order: so does _stack
         order = {kind: [nm for nm, kk in zip(names, kinds) if kk == kind] for kind in 'bfi'}
         for kind in 'bfi':
             assert order[kind] == list(g[f'{tag}_names_{kind}'])
-        _check_blocks(fb, (names, kinds, mats), f'explicit golden atomic={atomic} {tag}')
+        _check_blocks(fb, (names, kinds, mats, None), f'explicit golden atomic={atomic} {tag}')
 
 
 @pytest.mark.parametrize('k', wc.EXPLICIT_KS)
@@ -378,7 +401,7 @@ def test_explicit_frames_vs_oracle(sa, atomic, k):
     B, ops = sa['batch'], sa['ops']
     for n in wc.EXPLICIT_NS:
         frames = wc.permuted_frames(n, k, atomic)
-        ref = _stack(vo.features_frames(wc.frame_cols(frames, atomic), _xfns(atomic), atomic))
+        ref = _frames_ref(wc.frame_cols(frames, atomic), atomic)
         fb = ops.features_explicit(B.frames_batches(frames, atomic=atomic), _xfns(atomic))
         assert fb.n == n
         _check_blocks(fb, ref, f'explicit atomic={atomic} k={k} n={n}')
@@ -403,10 +426,13 @@ def test_public_transformers_on_long_frame_lists(sa, atomic, k, n):
     assert len(X) == n and X.index.equals(frames[0].index)
     for name, kind, v in ref:
         assert X[name].dtype == _DTYPES[kind], name
-        if kind == 'f':
-            assert_close(X[name].to_numpy(), v, name)
-        else:
+        if kind != 'f':
             np.testing.assert_array_equal(X[name].to_numpy(), v.astype(_DTYPES[kind]), err_msg=name)
+    fnames = [name for name, kind, _ in ref if kind == 'f']
+    vc.check_float_columns(fnames, np.stack([X[name].to_numpy() for name in fnames]),
+                           np.stack([v for _, kind, v in ref if kind == 'f']),
+                           vc.exact_angles_frames(wc.frame_cols(frames, atomic), atomic),
+                           f'public transformers atomic={atomic} k={k}')
     for name in ('time', 'team', 'goalscore'):  # one transformer alone keeps its own columns
         one = getattr(fs, name)(frames)
         assert list(one.columns) == [c[0] for c in vo.features_frames(
