@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SA_ABI_VERSION 3
+#define SA_ABI_VERSION 4
 #define SA_MAX_FRAMES 8 /* max frames n_frames == k of explicit-frame mode (windowed mode: any k) */
 #define SA_BOOL_TILE_QUANTUM 1024 /* bool block: rows per tile must be a multiple of this */
 #define SA_NUM_TILE_QUANTUM 128   /* f64 / i64 blocks: rows per tile must be a multiple of this */
@@ -822,19 +822,31 @@ int sa_auc_count(const uint8_t* y, const void* p, int32_t f32, int64_t n, const 
  * sa_boost_bin: the numeric features' bins from the f64 / i64 blocks (f32 != 0: both blocks hold
  *   float32); slots[r] = (1 << 24 | f64 column) or (2 << 24 | i64 column); x32 is the value the
  *   tree predictor compares ((float)x, for an i64 column (float)(double)x).
- * sa_boost_grad: p = 1 / (1 + expf(-margin)); with gq: g = p - y, h = p (1 - p) in float32,
- *   gq = (int32)rint(g 2^30), hq likewise.  p and node are optional; node is set to 0, or to
- *   SA_BOOST_NO_NODE where row_mask (optional) is 0.
+ * sa_boost_grad: p = 1 / (1 + expf(-margin)); with gq (contract items 13, 14 and 16): we =
+ *   weight[j] * (y[j] ? scale_pos_weight : 1.0f) (weight == NULL: 1.0f), g = (p - y) * we, h =
+ *   (p * (1 - p)) * we in float32, gq = (int32)rint(g * 2^(30 - shift)), hq likewise, every product
+ *   rounded on its own.  The caller guarantees 0 <= we <= 2^shift, shift in 0 ..
+ *   SA_BOOST_MAX_SHIFT.  Row j is in the round's sample iff (draw >> 32) < thr, thr in 0 .. 2^32
+ *   (2^32: every row, no hash), draw = fm(fm(fm(seed ^ SA_BOOST_SALT_ROWS) + round) + key), fm =
+ *   splitmix64's finaliser on wrapping uint64, key = row_keys[j] (NULL: j).  A row outside the
+ *   sample gets gq = hq = 0.  p and node are optional; node is set to 0, or to SA_BOOST_NO_NODE
+ *   where row_mask (optional) is 0, for a row inside the sample or outside it.
  * sa_boost_hist_bits: ADDS the set-bit sums of every bool feature into bin 1, then sets bin 0 to
  *   the node's total minus bin 1.  add_totals != 0: the nodes' totals are first added to
  *   tree[node0 + k].G / .H (level 0); otherwise they are read from there.
- * sa_boost_hist_bins: ADDS the numeric features' histograms.
+ * sa_boost_hist_bins: ADDS the numeric features' histograms: list entry r < n_num is row
+ *   num_rows[r] (NULL: r) of the n_bin_rows-row bin matrix and feature number num_feat[r], so a
+ *   round's column sample (contract item 17) reads only its own rows.
  * sa_boost_split: for every existing node of the level its leaf value (float)(eta * -(G / (H +
  *   lambda))) and, unless leaf_only, its best split -- over the cuts i with both children's
  *   hessian sums >= min_child_weight, gain = ((GL*GL)/(HL+lambda) + (GR*GR)/(HR+lambda)) -
  *   (G*G)/(H+lambda) in float64, the maximum with ties to the lowest feature then the lowest
  *   cut, taken iff > gamma -- with its children's totals written to their records.  best_gain /
- *   best_cut [n_nodes * n_features]: scratch.  leaf_only allows n_nodes up to 64.
+ *   best_cut [n_nodes * n_features]: scratch.  leaf_only allows n_nodes up to 64.  Contract items
+ *   13, 15 and 17: T(G) = G > a ? G - a : (G < -a ? G + a : 0), a = reg_alpha, stands in place of
+ *   G, GL and GR in the gain and the leaf value; every integer sum is scaled by 2^(shift - 30) (so
+ *   min_child_weight compares weighted hessians); and a feature whose byte of feature_mask
+ *   [n_features] (NULL: all) is 0 is no split candidate (best_cut = -1).
  * sa_boost_advance: margin == NULL: every row in a split node of the level moves to a child
  *   (bit set, or bin > cut: the right one); fmap[f] = bitmap row, or 1 << 24 | bin-matrix row.
  *   margin != NULL: margin[j] += tree[node[j]].value for every participating row.
@@ -850,22 +862,8 @@ int sa_auc_count(const uint8_t* y, const void* p, int32_t f32, int64_t n, const 
  *   thread per entry, 256 per workgroup; the records' walk fields are staged in LDS once per
  *   workgroup (12 bytes per node), the bitmap and bin reads are gathers by row.
  *
- * Sample weights, sampling and the L1 penalty (contract items 13-17).  The existing entries keep
- * their results; the _ex entries with neutral arguments (weight = row_keys = feature_mask = NULL,
- * scale_pos_weight = 1, shift = 0, thr = 2^32, reg_alpha = 0) compute the same.
- * sa_boost_grad_ex: we = weight[j] * (y[j] ? scale_pos_weight : 1.0f) (weight == NULL: 1.0f), g =
- *   (p - y) * we, h = (p * (1 - p)) * we, gq = (int32)rint(g * 2^(30 - shift)), hq likewise, every
- *   product rounded on its own.  The caller guarantees 0 <= we <= 2^shift, shift in 0 ..
- *   SA_BOOST_MAX_SHIFT.  Row j is in the round's sample iff (draw >> 32) < thr, thr in 0 .. 2^32
- *   (2^32: every row, no hash), draw = fm(fm(fm(seed ^ SA_BOOST_SALT_ROWS) + round) + key), fm =
- *   splitmix64's finaliser on wrapping uint64, key = row_keys[j] (NULL: j).  A row outside the
- *   sample gets gq = hq = 0; its node is set like any other row's.
- * sa_boost_hist_bins_ex: list entry r is row num_rows[r] (NULL: r) of the n_bin_rows-row bin
- *   matrix and feature number num_feat[r]: a round's column sample reads only its own rows.
- * sa_boost_split_ex: sa_boost_split with T(G) = G > a ? G - a : (G < -a ? G + a : 0), a =
- *   reg_alpha, in place of G, GL and GR in the gain and the leaf value; every integer sum scaled
- *   by 2^(shift - 30) (so min_child_weight compares weighted hessians); and feature_mask
- *   [n_features] (NULL: all): a feature whose byte is 0 is no split candidate (best_cut = -1).
+ * The neutral arguments -- weight = row_keys = num_rows = feature_mask = NULL, scale_pos_weight =
+ * 1, shift = 0, thr = 2^32, reg_alpha = 0 -- are the unweighted, unsampled learner, bit for bit.
  * sa_boost_row_keys: keys[j] = fm(game_id[j]) + action_id[j], wrapping.
  *
  * The level exchange of a fit whose rows are split over ranks (contract item 18): the used entries
@@ -920,19 +918,23 @@ int sa_boost_bin(const sa_block* f64_blk, const sa_block* i64_blk, int32_t f32, 
                  const int32_t* num_feat, const int32_t* cut_start, const float* cuts, int32_t n_num,
                  int64_t n, uint8_t* bins, int64_t ld, void* stream);
 int sa_boost_grad(const float* margin, const uint8_t* y, const uint8_t* row_mask, int64_t n,
-                  int32_t* gq, int32_t* hq, float* p, uint8_t* node, void* stream);
+                  const float* weight, float scale_pos_weight, int32_t shift, const int64_t* row_keys,
+                  uint64_t seed, int64_t round, uint64_t thr, int32_t* gq, int32_t* hq, float* p,
+                  uint8_t* node, void* stream);
 int sa_boost_hist_bits(const uint64_t* bits, int64_t bits_stride, const int32_t* bit_rows,
                        const int32_t* bit_feat, int32_t n_bool, const int32_t* gq, const int32_t* hq,
                        const uint8_t* node, int64_t n, int32_t node0, int32_t n_nodes,
                        int32_t n_features, int64_t* hist, sa_boost_node* tree, int32_t add_totals,
                        void* stream);
-int sa_boost_hist_bins(const uint8_t* bins, int64_t ld, const int32_t* num_feat, int32_t n_num,
-                       const int32_t* gq, const int32_t* hq, const uint8_t* node, int64_t n,
-                       int32_t node0, int32_t n_nodes, int32_t n_features, int64_t* hist, void* stream);
+int sa_boost_hist_bins(const uint8_t* bins, int64_t ld, const int32_t* num_feat,
+                       const int32_t* num_rows, int32_t n_bin_rows, int32_t n_num, const int32_t* gq,
+                       const int32_t* hq, const uint8_t* node, int64_t n, int32_t node0,
+                       int32_t n_nodes, int32_t n_features, int64_t* hist, void* stream);
 int sa_boost_split(const int64_t* hist, const int32_t* cut_start, const float* cuts, int32_t n_features,
                    int32_t node0, int32_t n_nodes, int32_t leaf_only, double reg_lambda,
-                   double min_child_weight, double gamma, double learning_rate, double* best_gain,
-                   int32_t* best_cut, sa_boost_node* tree, void* stream);
+                   double min_child_weight, double gamma, double learning_rate, double reg_alpha,
+                   int32_t shift, const uint8_t* feature_mask, double* best_gain, int32_t* best_cut,
+                   sa_boost_node* tree, void* stream);
 int sa_boost_advance(const sa_boost_node* tree, int32_t node0, int32_t n_nodes, const int32_t* fmap,
                      const uint64_t* bits, int64_t bits_stride, const uint8_t* bins, int64_t ld,
                      int64_t n, uint8_t* node, float* margin, void* stream);
@@ -941,19 +943,6 @@ int sa_boost_apply(const sa_boost_node* tree, int32_t max_depth, const int32_t* 
                    const int64_t* rows /* NULL: rows 0..n_rows-1 */, int64_t n_rows, int64_t n,
                    float* margin /* [n_rows], updated in place */, float* p /* [n_rows] or NULL */,
                    void* stream);
-int sa_boost_grad_ex(const float* margin, const uint8_t* y, const uint8_t* row_mask, int64_t n,
-                     const float* weight, float scale_pos_weight, int32_t shift,
-                     const int64_t* row_keys, uint64_t seed, int64_t round, uint64_t thr, int32_t* gq,
-                     int32_t* hq, float* p, uint8_t* node, void* stream);
-int sa_boost_hist_bins_ex(const uint8_t* bins, int64_t ld, const int32_t* num_feat,
-                          const int32_t* num_rows, int32_t n_bin_rows, int32_t n_num, const int32_t* gq,
-                          const int32_t* hq, const uint8_t* node, int64_t n, int32_t node0,
-                          int32_t n_nodes, int32_t n_features, int64_t* hist, void* stream);
-int sa_boost_split_ex(const int64_t* hist, const int32_t* cut_start, const float* cuts,
-                      int32_t n_features, int32_t node0, int32_t n_nodes, int32_t leaf_only,
-                      double reg_lambda, double min_child_weight, double gamma, double learning_rate,
-                      double reg_alpha, int32_t shift, const uint8_t* feature_mask, double* best_gain,
-                      int32_t* best_cut, sa_boost_node* tree, void* stream);
 int sa_boost_row_keys(const int64_t* game_id, const int64_t* action_id, int64_t n, int64_t* keys,
                       void* stream);
 int sa_boost_hist_pack(const int64_t* hist, const sa_boost_node* tree, const int32_t* pairs,

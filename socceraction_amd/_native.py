@@ -271,28 +271,21 @@ _SIGNATURES = {
                                     ctypes.c_int32, _p, _p]),
     'sa_boost_bin': (ctypes.c_int, [ctypes.POINTER(SaBlock), ctypes.POINTER(SaBlock), ctypes.c_int32, _p, _p, _p,
                                     _p, ctypes.c_int32, ctypes.c_int64, _p, ctypes.c_int64, _p]),
-    'sa_boost_grad': (ctypes.c_int, [_p, _p, _p, ctypes.c_int64, _p, _p, _p, _p, _p]),
+    'sa_boost_grad': (ctypes.c_int, [_p, _p, _p, ctypes.c_int64, _p, ctypes.c_float, ctypes.c_int32, _p,
+                                     ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint64, _p, _p, _p, _p, _p]),
     'sa_boost_hist_bits': (ctypes.c_int, [_p, ctypes.c_int64, _p, _p, ctypes.c_int32, _p, _p, _p,
                                           ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                           _p, _p, ctypes.c_int32, _p]),
-    'sa_boost_hist_bins': (ctypes.c_int, [_p, ctypes.c_int64, _p, ctypes.c_int32, _p, _p, _p,
+    'sa_boost_hist_bins': (ctypes.c_int, [_p, ctypes.c_int64, _p, _p, ctypes.c_int32, ctypes.c_int32, _p, _p, _p,
                                           ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                           _p, _p]),
     'sa_boost_split': (ctypes.c_int, [_p, _p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                       ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                      ctypes.c_double, _p, _p, _p, _p]),
+                                      ctypes.c_double, ctypes.c_double, ctypes.c_int32, _p, _p, _p, _p, _p]),
     'sa_boost_advance': (ctypes.c_int, [_p, ctypes.c_int32, ctypes.c_int32, _p, _p, ctypes.c_int64, _p,
                                         ctypes.c_int64, ctypes.c_int64, _p, _p, _p]),
     'sa_boost_apply': (ctypes.c_int, [_p, ctypes.c_int32, _p, _p, ctypes.c_int64, _p, ctypes.c_int64, _p,
                                       ctypes.c_int64, ctypes.c_int64, _p, _p, _p]),
-    'sa_boost_grad_ex': (ctypes.c_int, [_p, _p, _p, ctypes.c_int64, _p, ctypes.c_float, ctypes.c_int32, _p,
-                                        ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint64, _p, _p, _p, _p, _p]),
-    'sa_boost_hist_bins_ex': (ctypes.c_int, [_p, ctypes.c_int64, _p, _p, ctypes.c_int32, ctypes.c_int32, _p, _p, _p,
-                                             ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                             _p, _p]),
-    'sa_boost_split_ex': (ctypes.c_int, [_p, _p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                         ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                         ctypes.c_double, ctypes.c_double, ctypes.c_int32, _p, _p, _p, _p, _p]),
     'sa_boost_row_keys': (ctypes.c_int, [_p, _p, ctypes.c_int64, _p, _p]),
     'sa_boost_hist_pack': (ctypes.c_int, [_p, _p, _p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                           ctypes.c_int32, _p, _p]),
@@ -346,7 +339,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    if lib.sa_abi_version() != 3:
+    if lib.sa_abi_version() != 4:
         raise ImportError('libsocceraction_amd ABI version mismatch')
     _check_build_id(lib, path)
     if path == LIB_PATH:

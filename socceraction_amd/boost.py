@@ -23,10 +23,11 @@ reproducible as the full one.
 Sample weights, ``scale_pos_weight``, the L1 penalty and row / column subsampling (contract items
 13-17; ``tests/boost_sample_reference.py``): weights are folded in before the quantisation with an
 exact power-of-two rescale, a round's samples come from a counter hash of ``(random_state, round,
-row key or feature)``, so a tuned model is as reproducible as a plain one.  The tuning parameters
-are :class:`TunedGBTClassifier`'s; :class:`DeviceGBTClassifier` keeps its seven.  No weighted
-evaluation, bylevel / bynode column sampling, categorical splits or learned default directions
-(missing values always go right).
+row key or feature)``, so a tuned model is as reproducible as a plain one.  Every kernel has one
+entry point: a plain fit passes the neutral :class:`Tuning`, which is the unweighted arithmetic
+bit for bit.  The tuning parameters are :class:`TunedGBTClassifier`'s;
+:class:`DeviceGBTClassifier` keeps its seven.  No weighted evaluation, bylevel / bynode column
+sampling, categorical splits or learned default directions (missing values always go right).
 
 The sharded fit (contract items 18-22; ``tests/test_gpu_boost_shard.py``): with ``process_group=``
 every rank of a ``torch.distributed`` group holds a shard of the rows; the cuts come from the
@@ -551,10 +552,10 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-# What a fit (or one launch) has beyond the plain learner's (contract items 13-16): the float32 device
+# The tuning arguments of a fit's (or one launch's) kernels (contract items 13-16): the float32 device
 # weight column (None: every weight 1), scale_pos_weight, the quantisation shift e (the scale is
 # 2^(30 - e)), the int64 device key column (None: a row's key is its index), the seed, the row sample's
-# raw threshold, the L1 penalty.  Where a Tuning is expected, None means plain: the entry points without `_ex`.
+# raw threshold, the L1 penalty.  The defaults are the neutral values: the plain learner.
 Tuning = namedtuple('Tuning', 'weight scale_pos_weight shift keys seed thr reg_alpha',
                     defaults=(None, 1.0, 0, None, 0, THR_ALL, 0.0))
 
@@ -587,21 +588,16 @@ class ColumnSamples:
         self.mask = torch.from_numpy(mask).to(data.device)
 
 
-def _grad(run, st, margin, y, mask, n: int, gq, hq, p, node, tu: Optional[Tuning] = None, t: int = 0) -> None:
-    """Round ``t``'s gradient launch: ``sa_boost_grad``, with a :class:`Tuning` ``sa_boost_grad_ex``."""
-    lib, out = _native.lib(), (_ptr(gq), _ptr(hq), _ptr(p), _ptr(node), st)
-    if tu is None:
-        run('grad', lib.sa_boost_grad, margin.data_ptr(), _ptr(y), _ptr(mask), n, *out)
-    else:
-        run('grad', lib.sa_boost_grad_ex, margin.data_ptr(), _ptr(y), _ptr(mask), n, _ptr(tu.weight),
-            tu.scale_pos_weight, tu.shift, _ptr(tu.keys), tu.seed, t, tu.thr, *out)
+def _grad(run, st, margin, y, mask, n: int, gq, hq, p, node, tu: Tuning = Tuning(), t: int = 0) -> None:
+    """Round ``t``'s gradient launch (``sa_boost_grad``)."""
+    run('grad', _native.lib().sa_boost_grad, margin.data_ptr(), _ptr(y), _ptr(mask), n, _ptr(tu.weight),
+        tu.scale_pos_weight, tu.shift, _ptr(tu.keys), tu.seed, t, tu.thr, _ptr(gq), _ptr(hq), _ptr(p), _ptr(node), st)
 
 
 def _hist(run, st, data: BinnedData, gq, hq, node, n_nodes: int, hist, tree, add_totals: bool, cols=None) -> None:
-    """Both histogram kernels of the level of ``n_nodes`` nodes into the zeroed ``hist``.  This pair
-    is chosen by the column sample, not by the :class:`Tuning`: with ``cols`` (a round of
-    :class:`ColumnSamples`) the kernels visit its features only (``sa_boost_hist_bins_ex``), and the
-    bitmap kernel is launched even for none of them (it carries the level-0 node totals)."""
+    """Both histogram kernels of the level of ``n_nodes`` nodes into the zeroed ``hist``.  With
+    ``cols`` (a round of :class:`ColumnSamples`) the kernels visit its features only, else every
+    feature; the bitmap kernel is launched even for none (it carries the level-0 node totals)."""
     lib, d = _native.lib(), data.dev
     bit_rows, bit_feat, nb, num_feat, num_rows, nn = cols or (
         d['bit_rows'], d['bit_feat'], len(data.bit_feat), d['num_feat'], None, len(data.num_feat))
@@ -610,34 +606,27 @@ def _hist(run, st, data: BinnedData, gq, hq, node, n_nodes: int, hist, tree, add
     run('hist_bits', lib.sa_boost_hist_bits, data.bits.data_ptr() if nb else None,
         data.bits.shape[1] * 8 if nb else 0, bit_rows.data_ptr() if nb else None, bit_feat.data_ptr() if nb else None,
         nb, *level, tree.data_ptr(), int(add_totals), st)
-    if nn and cols is None:
-        run('hist_bins', lib.sa_boost_hist_bins, data.bins.data_ptr(), data.ld, num_feat.data_ptr(), nn, *level, st)
-    elif nn:
-        run('hist_bins', lib.sa_boost_hist_bins_ex, data.bins.data_ptr(), data.ld, num_feat.data_ptr(),
-            num_rows.data_ptr(), len(data.num_feat), nn, *level, st)
+    if nn:
+        run('hist_bins', lib.sa_boost_hist_bins, data.bins.data_ptr(), data.ld, num_feat.data_ptr(), _ptr(num_rows),
+            len(data.num_feat) if cols else 0, nn, *level, st)
 
 
-def _split(run, st, hist, cut_start, cuts, F: int, n_nodes: int, params, bg, bc, tree, tu: Optional[Tuning] = None,
+def _split(run, st, hist, cut_start, cuts, F: int, n_nodes: int, params, bg, bc, tree, tu: Tuning = Tuning(),
            fmask=None, leaf_only: bool = False) -> None:
     """The split search of the level of ``n_nodes`` nodes (``leaf_only``: its leaf values only);
-    ``params = (reg_lambda, min_child_weight, gamma, learning_rate)``.  With a :class:`Tuning`
-    ``sa_boost_split_ex``: its L1 penalty and shift, and the ``[F]`` uint8 device mask ``fmask``."""
-    lib = _native.lib()
-    head = (_ptr(hist), _ptr(cut_start), _ptr(cuts), F, n_nodes - 1, n_nodes, int(leaf_only), *params)
-    tail = (_ptr(bg), _ptr(bc), tree.data_ptr(), st)
-    if tu is None:
-        run('split', lib.sa_boost_split, *head, *tail)
-    else:
-        run('split', lib.sa_boost_split_ex, *head, tu.reg_alpha, tu.shift, _ptr(fmask), *tail)
+    ``params = (reg_lambda, min_child_weight, gamma, learning_rate)``, ``tu``'s L1 penalty and shift,
+    and the ``[F]`` uint8 device mask ``fmask`` (None: every feature is a candidate)."""
+    run('split', _native.lib().sa_boost_split, _ptr(hist), _ptr(cut_start), _ptr(cuts), F, n_nodes - 1, n_nodes,
+        int(leaf_only), *params, tu.reg_alpha, tu.shift, _ptr(fmask), _ptr(bg), _ptr(bc), tree.data_ptr(), st)
 
 
 def gradients(margin, y, row_mask=None, *, weight=None, scale_pos_weight: float = 1.0, shift: int = 0,
               row_keys=None, seed: int = 0, round: int = 0, thr: Optional[int] = None):
-    """``sa_boost_grad`` on device columns: ``(gq, hq, p)`` -- int32, int32, float32.  With any
-    keyword argument ``sa_boost_grad_ex``: ``weight`` (float32 device column), ``scale_pos_weight``,
-    the quantisation ``shift`` e (the caller keeps every effective weight ``<= 2^e``), and the
-    round's row sample -- ``row_keys`` (int64 device column, default the row index), ``seed``,
-    ``round`` and the raw threshold ``thr`` in ``0 .. 2^32`` (default ``2^32``: every row)."""
+    """``sa_boost_grad`` on device columns: ``(gq, hq, p)`` -- int32, int32, float32.  ``weight``
+    (float32 device column, default every weight 1), ``scale_pos_weight``, the quantisation
+    ``shift`` e (the caller keeps every effective weight ``<= 2^e``), and the round's row sample --
+    ``row_keys`` (int64 device column, default the row index), ``seed``, ``round`` and the raw
+    threshold ``thr`` in ``0 .. 2^32`` (default ``2^32``: every row)."""
     import torch
     n = margin.numel()
     margin = margin.to(torch.float32).contiguous()
@@ -645,18 +634,15 @@ def gradients(margin, y, row_mask=None, *, weight=None, scale_pos_weight: float 
     gq = torch.empty(max(n, 1), dtype=torch.int32, device=margin.device)
     hq = torch.empty_like(gq)
     p = torch.empty(max(n, 1), dtype=torch.float32, device=margin.device)
-    tu = None
-    if not (weight is None and scale_pos_weight == 1.0 and shift == 0 and row_keys is None and thr is None):
-        if weight is not None:
-            weight = weight.to(torch.float32).contiguous()
-            if weight.numel() < n:
-                raise ValueError('one weight per row')
-        if row_keys is not None:
-            row_keys = row_keys.to(torch.int64).contiguous()
-            if row_keys.numel() < n:
-                raise ValueError('one key per row')
-        tu = Tuning(weight, float(scale_pos_weight), int(shift), row_keys, int(seed),
-                    THR_ALL if thr is None else int(thr))
+    if weight is not None:
+        weight = weight.to(torch.float32).contiguous()
+        if weight.numel() < n:
+            raise ValueError('one weight per row')
+    if row_keys is not None:
+        row_keys = row_keys.to(torch.int64).contiguous()
+        if row_keys.numel() < n:
+            raise ValueError('one key per row')
+    tu = Tuning(weight, float(scale_pos_weight), int(shift), row_keys, int(seed), THR_ALL if thr is None else int(thr))
     _grad(_run, _stream(), margin, y.contiguous(), row_mask, n, gq, hq, p, None, tu=tu, t=int(round))
     return gq[:n], hq[:n], p[:n]
 
@@ -763,8 +749,8 @@ def best_splits(hist, totals, cuts: Sequence[np.ndarray], reg_lambda: float = 1.
     """``sa_boost_split`` on a level's histograms ``[n_nodes, F, 256, 2]`` and node totals
     ``[n_nodes, 2]``: the level's node records (:data:`NODE_DTYPE`) and, after them, their
     children's -- ``[3 * n_nodes]`` rows: the level, then the children level in heap order.
-    With ``reg_alpha``, the quantisation ``shift`` or a ``feature_mask`` (``[F]``, 0 = the feature
-    is no candidate) ``sa_boost_split_ex``."""
+    ``reg_alpha``, the quantisation ``shift`` and a ``feature_mask`` (``[F]``, 0 = the feature is no
+    candidate; default all) are the kernel's."""
     import torch
     n_nodes, F = hist.shape[0], hist.shape[1]
     node0 = _level(n_nodes)
@@ -780,14 +766,12 @@ def best_splits(hist, totals, cuts: Sequence[np.ndarray], reg_lambda: float = 1.
     cs, cf = torch.from_numpy(cut_start).to(dev), torch.from_numpy(flat).to(dev)
     bg = torch.empty(n_nodes * F, dtype=torch.float64, device=dev)
     bc = torch.empty(n_nodes * F, dtype=torch.int32, device=dev)
-    tu = fm = None
-    if not (reg_alpha == 0.0 and shift == 0 and feature_mask is None):
-        tu = Tuning(reg_alpha=float(reg_alpha), shift=int(shift))
-        if feature_mask is not None:
-            fm = np.ascontiguousarray(np.asarray(feature_mask).astype(bool).astype(np.uint8).ravel())
-            if len(fm) != F:
-                raise ValueError('one mask byte per feature')
-            fm = torch.from_numpy(fm).to(dev)
+    tu, fm = Tuning(reg_alpha=float(reg_alpha), shift=int(shift)), None
+    if feature_mask is not None:
+        fm = np.ascontiguousarray(np.asarray(feature_mask).astype(bool).astype(np.uint8).ravel())
+        if len(fm) != F:
+            raise ValueError('one mask byte per feature')
+        fm = torch.from_numpy(fm).to(dev)
     params = (float(reg_lambda), float(min_child_weight), float(gamma), float(learning_rate))
     _split(_run, _stream(), hist.contiguous(), cs, cf, F, n_nodes, params, bg, bc, tree, tu=tu, fmask=fm)
     return tree.cpu().numpy().view(NODE_DTYPE).reshape(-1)[node0:node0 + 3 * n_nodes]
@@ -1062,7 +1046,7 @@ def make_classifier(params: Dict[str, Any], **kw) -> 'DeviceGBTClassifier':
 
 
 # The evaluation state of a fit (DeviceGBTClassifier._eval_setup fills it) and the state of one
-# fit_binned between its parts (._prepare fills it: `tu` / `columns` None: plain; `ev` None: no evaluation rows)
+# fit_binned between its parts (._prepare fills it: `columns` None: every feature; `ev` None: no evaluation rows)
 _Eval = make_dataclass('_Eval', 'idx n n_pos minority m y margin p table P keys cursor total total_pos'.split())
 _Fit = make_dataclass('_Fit', 'data y mask tu columns T D stream params margin gq hq node p P Mrec trees hist bg bc ev '
                               'group pay'.split())
@@ -1221,27 +1205,10 @@ class DeviceGBTClassifier:
         BinaryMetrics.raise_errors(err)
         return [metric_integer(r, self.eval_metric) for r in h]
 
-    def _weight_shift(self, wd, y, mask, n: int) -> int:
-        """The quantisation shift e of a weighted fit (contract item 13) -- the fit's one host read
-        for it, before the first round: the training rows' effective weights, formed on the device
-        by the gradient kernel's own float32 product, reduced to their maximum, minimum and
-        finiteness."""
-        import torch
-        one = torch.ones((), dtype=torch.float32, device=y.device)
-        we = torch.where(y[:n] != 0, one * float(np.float32(float(self.scale_pos_weight))), one)
-        if wd is not None:
-            we = wd[:n] * we
-        if mask is not None:
-            we = we[mask[:n] != 0]
-        if not we.numel():
-            raise ValueError('no training rows')
-        mx, mn, fin = torch.stack([we.max(), we.min(), torch.isfinite(we).all().to(torch.float32)]).cpu().tolist()
-        return _check_weight_range(mx, mn, bool(fin))
-
     def _weight_stats(self, wd, y, mask, n: int):
-        """A rank's part of :meth:`_weight_shift` in a sharded fit (contract item 20): ``(max, min,
-        finite, count)`` of its training rows' effective weights (one host read); a rank without
-        training rows gives ``(-inf, inf, 1, 0)``."""
+        """``(max, min, finite, count)`` of the training rows' effective weights (one host read; no
+        training rows: ``(-inf, inf, 1, 0)`` and none), formed on the device by the gradient kernel's
+        own float32 product: a rank's part of the shift in a sharded fit (contract item 20)."""
         import torch
         one = torch.ones((), dtype=torch.float32, device=y.device)
         we = torch.where(y[:n] != 0, one * float(np.float32(float(self.scale_pos_weight))), one)
@@ -1253,6 +1220,14 @@ class DeviceGBTClassifier:
             return -math.inf, math.inf, 1.0, 0.0
         mx, mn, fin = torch.stack([we.max(), we.min(), torch.isfinite(we).all().to(torch.float32)]).cpu().tolist()
         return mx, mn, fin, float(we.numel())
+
+    def _weight_shift(self, wd, y, mask, n: int) -> int:
+        """The quantisation shift e of a weighted fit (contract item 13) -- the fit's one host read
+        for it, before the first round."""
+        mx, mn, fin, count = self._weight_stats(wd, y, mask, n)
+        if not count:
+            raise ValueError('no training rows')
+        return _check_weight_range(mx, mn, bool(fin))
 
     def _prepare_sharded(self, data: BinnedData, y_dev, rows, eval_rows, sample_weight, row_keys, group,
                          pending: Optional[Exception]) -> '_Fit':
@@ -1383,18 +1358,15 @@ class DeviceGBTClassifier:
         return f
 
     def _buffers(self, data: BinnedData, y, mask, wd, e: int, keys, ev) -> '_Fit':
-        """The validated inputs as a fit's state: the :class:`Tuning` and the column samples (both
-        None for a plain fit) and every device buffer of the rounds."""
+        """The validated inputs as a fit's state: the :class:`Tuning`, the column samples (None
+        unless ``colsample_bytree != 1``) and every device buffer of the rounds."""
         import torch
         dev, ld, F = data.device, data.ld, data.n_features
         T, D = int(self.n_estimators), int(self.max_depth)
         alpha, spw, seed = float(self.reg_alpha), float(self.scale_pos_weight), int(self.random_state)
         thr, colsample = row_threshold(self.subsample), float(self.colsample_bytree)
-        tu = columns = None
-        if not (wd is None and spw == 1.0 and thr == THR_ALL and colsample == 1.0 and alpha == 0.0):
-            if colsample != 1.0:
-                columns = ColumnSamples(data, seed, T, colsample)
-            tu = Tuning(wd, spw, e, keys, seed, thr, alpha)
+        columns = ColumnSamples(data, seed, T, colsample) if colsample != 1.0 else None
+        tu = Tuning(wd, spw, e, keys, seed, thr, alpha)
         params = (float(self.reg_lambda), float(self.min_child_weight), float(self.gamma), float(self.learning_rate))
         top = 2 ** (D - 1)  # nodes of the deepest level that splits
         rec = lambda: torch.empty((T, ld), dtype=torch.float32, device=dev) if self.record else None  # noqa: E731
@@ -1439,7 +1411,7 @@ class DeviceGBTClassifier:
         M = f.trees.shape[1]
         self.trees_ = f.trees[:keep].cpu().numpy().view(NODE_DTYPE).reshape(keep, M).copy()  # the one read-back
         self.cuts_ = data.cuts
-        self.quant_shift_ = 0 if f.tu is None else f.tu.shift
+        self.quant_shift_ = f.tu.shift
         self.column_samples_ = None if f.columns is None else f.columns.features[:keep]
         self.feature_names_in_ = np.array(data.names, dtype=object)
         self.n_features_in_ = data.n_features

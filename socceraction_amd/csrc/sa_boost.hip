@@ -110,7 +110,7 @@ __device__ __host__ __forceinline__ u64 fmix64(u64 z) {  // splitmix64's finalis
   return z;
 }
 
-struct grad_tuning {  // what sa_boost_grad_ex adds to sa_boost_grad: the TUNED kernel alone reads it
+struct grad_tuning {  // sa_boost_grad's weights and row sample: the TUNED kernel alone reads it
   const float* weight;
   float spw, scale;
   const int64_t* keys;
@@ -121,6 +121,8 @@ struct grad_tuning {  // what sa_boost_grad_ex adds to sa_boost_grad: the TUNED 
 // the quantisation at scale 2^(30 - e) (|g| <= we <= 2^e keeps |gq| <= 2^30), and the round's row
 // sample from a counter hash of (seed, round, row key): a row outside it gets gq = hq = 0 -- the
 // histogram kernels skip zero adds -- and still walks the tree.  Each product is its own statement.
+// With every tuning argument neutral the two instantiations compute the same bits (g * 1.0f is g, the
+// scale is 2^30, thr = 2^32 skips the hash); sa_boost_grad then launches the shorter one.
 template <bool TUNED>
 __global__ __launch_bounds__(256) void boost_grad_kernel(const float* __restrict__ margin, const uint8_t* __restrict__ y,
                                                           const uint8_t* __restrict__ mask, int64_t n,
@@ -639,17 +641,6 @@ bool bits_ok(const uint64_t* bits, int64_t bits_stride, int64_t n) {
   return bits_stride % 8 == 0 && bits_stride >= 8 * ((n + 63) / 64) && ((uintptr_t)bits & 7u) == 0;
 }
 
-// `name`: the entry point, for the error text; `tuning_ok`: its check of what it put into `tu`
-template <bool TUNED>
-int grad(const char* name, const float* margin, const uint8_t* y, const uint8_t* row_mask, int64_t n, bool tuning_ok,
-         grad_tuning tu, int32_t* gq, int32_t* hq, float* p, uint8_t* node, void* stream) {
-  if (n < 0 || !margin || (gq && (!hq || !y)) || (!gq && hq)) return fail(SA_EINVAL, "%s: bad arguments", name);
-  if (!tuning_ok) return fail(SA_EINVAL, "%s: bad parameters", name);
-  if (n == 0) return SA_OK;
-  hipLaunchKernelGGL((boost_grad_kernel<TUNED>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     margin, y, row_mask, n, gq, hq, p, node, tu);
-  return check_launch(TUNED ? "boost_grad_ex_kernel" : "boost_grad_kernel");
-}
 }  // namespace
 
 extern "C" int sa_boost_bin(const sa_block* f64_blk, const sa_block* i64_blk, int32_t f32, const int32_t* slots,
@@ -672,20 +663,25 @@ extern "C" int sa_boost_bin(const sa_block* f64_blk, const sa_block* i64_blk, in
   return check_launch("boost_bin_kernel");
 }
 
-extern "C" int sa_boost_grad(const float* margin, const uint8_t* y, const uint8_t* row_mask, int64_t n, int32_t* gq,
-                             int32_t* hq, float* p, uint8_t* node, void* stream) {
-  return grad<false>("sa_boost_grad", margin, y, row_mask, n, true, grad_tuning{}, gq, hq, p, node, stream);
-}
-
-extern "C" int sa_boost_grad_ex(const float* margin, const uint8_t* y, const uint8_t* row_mask, int64_t n,
-                                const float* weight, float scale_pos_weight, int32_t shift, const int64_t* row_keys,
-                                uint64_t seed, int64_t round, uint64_t thr, int32_t* gq, int32_t* hq, float* p,
-                                uint8_t* node, void* stream) {
-  const bool ok = shift >= 0 && shift <= SA_BOOST_MAX_SHIFT && scale_pos_weight > 0.0f &&
-                  !std::isinf(scale_pos_weight) && round >= 0 && thr <= (1ull << 32);
+extern "C" int sa_boost_grad(const float* margin, const uint8_t* y, const uint8_t* row_mask, int64_t n,
+                             const float* weight, float scale_pos_weight, int32_t shift, const int64_t* row_keys,
+                             uint64_t seed, int64_t round, uint64_t thr, int32_t* gq, int32_t* hq, float* p,
+                             uint8_t* node, void* stream) {
+  if (n < 0 || !margin || (gq && (!hq || !y)) || (!gq && hq)) return fail(SA_EINVAL, "sa_boost_grad: bad arguments");
+  if (shift < 0 || shift > SA_BOOST_MAX_SHIFT || !(scale_pos_weight > 0.0f) || std::isinf(scale_pos_weight) ||
+      round < 0 || thr > (1ull << 32))
+    return fail(SA_EINVAL, "sa_boost_grad: bad parameters");
+  if (n == 0) return SA_OK;
   const u64 round_base = fmix64(fmix64((u64)seed ^ SA_BOOST_SALT_ROWS) + (u64)round);
-  const grad_tuning tu{weight, scale_pos_weight, std::ldexp(1.0f, ok ? 30 - shift : 0), row_keys, round_base, (u64)thr};
-  return grad<true>("sa_boost_grad_ex", margin, y, row_mask, n, ok, tu, gq, hq, p, node, stream);
+  const grad_tuning tu{weight, scale_pos_weight, std::ldexp(1.0f, 30 - shift), row_keys, round_base, (u64)thr};
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (!weight && scale_pos_weight == 1.0f && shift == 0 && !row_keys && thr == (1ull << 32))
+    hipLaunchKernelGGL((boost_grad_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, margin, y, row_mask, n, gq,
+                       hq, p, node, tu);
+  else
+    hipLaunchKernelGGL((boost_grad_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, margin, y, row_mask, n, gq,
+                       hq, p, node, tu);
+  return check_launch("boost_grad_kernel");
 }
 
 extern "C" int sa_boost_row_keys(const int64_t* game_id, const int64_t* action_id, int64_t n, int64_t* keys,
@@ -722,10 +718,10 @@ extern "C" int sa_boost_hist_bits(const uint64_t* bits, int64_t bits_stride, con
   return check_launch("boost_bits_fill_kernel");
 }
 
-namespace {
-int hist_bins(const uint8_t* bins, int64_t ld, const int32_t* num_feat, const int32_t* num_rows, int32_t n_bin_rows,
-              int32_t n_num, const int32_t* gq, const int32_t* hq, const uint8_t* node, int64_t n, int32_t node0,
-              int32_t n_nodes, int32_t n_features, int64_t* hist, void* stream) {
+extern "C" int sa_boost_hist_bins(const uint8_t* bins, int64_t ld, const int32_t* num_feat, const int32_t* num_rows,
+                                  int32_t n_bin_rows, int32_t n_num, const int32_t* gq, const int32_t* hq,
+                                  const uint8_t* node, int64_t n, int32_t node0, int32_t n_nodes, int32_t n_features,
+                                  int64_t* hist, void* stream) {
   if (n < 0 || n_num < 0 || n_features < 1 || ld < n || ld % 4 != 0 || !level_ok(node0, n_nodes) ||
       (num_rows && n_bin_rows < 1))
     return fail(SA_EINVAL, "sa_boost_hist_bins: bad sizes");
@@ -752,27 +748,12 @@ int hist_bins(const uint8_t* bins, int64_t ld, const int32_t* num_feat, const in
                        n_nodes, n_features, fg, hist);
   return check_launch("boost_hist_bins_kernel");
 }
-}  // namespace
 
-extern "C" int sa_boost_hist_bins(const uint8_t* bins, int64_t ld, const int32_t* num_feat, int32_t n_num,
-                                  const int32_t* gq, const int32_t* hq, const uint8_t* node, int64_t n, int32_t node0,
-                                  int32_t n_nodes, int32_t n_features, int64_t* hist, void* stream) {
-  return hist_bins(bins, ld, num_feat, nullptr, 0, n_num, gq, hq, node, n, node0, n_nodes, n_features, hist, stream);
-}
-
-extern "C" int sa_boost_hist_bins_ex(const uint8_t* bins, int64_t ld, const int32_t* num_feat, const int32_t* num_rows,
-                                     int32_t n_bin_rows, int32_t n_num, const int32_t* gq, const int32_t* hq,
-                                     const uint8_t* node, int64_t n, int32_t node0, int32_t n_nodes,
-                                     int32_t n_features, int64_t* hist, void* stream) {
-  return hist_bins(bins, ld, num_feat, num_rows, n_bin_rows, n_num, gq, hq, node, n, node0, n_nodes, n_features, hist,
-                   stream);
-}
-
-extern "C" int sa_boost_split_ex(const int64_t* hist, const int32_t* cut_start, const float* cuts, int32_t n_features,
-                                 int32_t node0, int32_t n_nodes, int32_t leaf_only, double reg_lambda,
-                                 double min_child_weight, double gamma, double learning_rate, double reg_alpha,
-                                 int32_t shift, const uint8_t* feature_mask, double* best_gain, int32_t* best_cut,
-                                 sa_boost_node* tree, void* stream) {
+extern "C" int sa_boost_split(const int64_t* hist, const int32_t* cut_start, const float* cuts, int32_t n_features,
+                              int32_t node0, int32_t n_nodes, int32_t leaf_only, double reg_lambda,
+                              double min_child_weight, double gamma, double learning_rate, double reg_alpha,
+                              int32_t shift, const uint8_t* feature_mask, double* best_gain, int32_t* best_cut,
+                              sa_boost_node* tree, void* stream) {
   if (!(reg_alpha >= 0.0) || std::isinf(reg_alpha) || shift < 0 || shift > SA_BOOST_MAX_SHIFT)
     return fail(SA_EINVAL, "sa_boost_split: bad parameters");
   const bool leaf_level = n_nodes == 2 * SA_BOOST_MAX_LEVEL_NODES && node0 == n_nodes - 1;  // below the deepest level
@@ -793,14 +774,6 @@ extern "C" int sa_boost_split_ex(const int64_t* hist, const int32_t* cut_start, 
   hipLaunchKernelGGL(boost_decide_kernel, dim3((unsigned)n_nodes), dim3(256), 0, st, hist, cut_start, cuts, n_features,
                      node0, leaf_only, reg_lambda, gamma, learning_rate, reg_alpha, s, best_gain, best_cut, tree);
   return check_launch("boost_decide_kernel");
-}
-
-extern "C" int sa_boost_split(const int64_t* hist, const int32_t* cut_start, const float* cuts, int32_t n_features,
-                              int32_t node0, int32_t n_nodes, int32_t leaf_only, double reg_lambda,
-                              double min_child_weight, double gamma, double learning_rate, double* best_gain,
-                              int32_t* best_cut, sa_boost_node* tree, void* stream) {
-  return sa_boost_split_ex(hist, cut_start, cuts, n_features, node0, n_nodes, leaf_only, reg_lambda, min_child_weight,
-                           gamma, learning_rate, 0.0, 0, nullptr, best_gain, best_cut, tree, stream);
 }
 
 extern "C" int sa_boost_advance(const sa_boost_node* tree, int32_t node0, int32_t n_nodes, const int32_t* fmap,

@@ -208,9 +208,10 @@ def test_boost_entry_points_validate_without_a_gpu():
     assert lib.sa_boost_bin(ctypes.byref(z), ctypes.byref(z), 0, one, one, one, one, 1, -1, one, 16, None) == E
     assert lib.sa_boost_bin(ctypes.byref(z), ctypes.byref(z), 0, None, one, one, one, 1, 5, one, 16, None) == E
     assert lib.sa_boost_bin(ctypes.byref(z), ctypes.byref(z), 0, one, one, one, one, 1, 0, one, 16, None) == 0
-    assert lib.sa_boost_grad(None, one, None, 4, one, one, one, one, None) == E
-    assert lib.sa_boost_grad(one, None, None, 4, one, one, one, one, None) == E
-    assert lib.sa_boost_grad(one, one, None, 0, one, one, one, one, None) == 0
+    neutral = (None, 1.0, 0, None, 0, 0, 2 ** 32)  # weight, scale_pos_weight, shift, row_keys, seed, round, thr
+    assert lib.sa_boost_grad(None, one, None, 4, *neutral, one, one, one, one, None) == E
+    assert lib.sa_boost_grad(one, None, None, 4, *neutral, one, one, one, one, None) == E
+    assert lib.sa_boost_grad(one, one, None, 0, *neutral, one, one, one, one, None) == 0
     hb = lambda **k: lib.sa_boost_hist_bits(*[{**dict(  # noqa: E731
         bits=one, stride=8, rows=one, feat=one, nb=1, gq=one, hq=one, node=one, n=64, node0=0, nn=1, F=1,
         hist=one, tree=one, tot=1, st=None), **k}[a] for a in (
@@ -218,15 +219,16 @@ def test_boost_entry_points_validate_without_a_gpu():
             'tot', 'st')])
     assert hb(stride=4) == E and hb(n=65) == E and hb(nn=3) == E and hb(node0=1) == E and hb(nn=64, node0=63) == E
     assert hb(tree=None) == E and hb(bits=None) == E and hb(F=0) == E and hb(n=0) == 0
-    assert lib.sa_boost_hist_bins(one, 16, one, 1, one, one, one, 17, 0, 1, 1, one, None) == E
-    assert lib.sa_boost_hist_bins(one, 18, one, 1, one, one, one, 17, 0, 1, 1, one, None) == E
-    assert lib.sa_boost_hist_bins(one, 16, one, 1, one, one, one, 8, 1, 1, 1, one, None) == E
-    assert lib.sa_boost_hist_bins(None, 16, one, 1, one, one, one, 8, 0, 1, 1, one, None) == E
-    assert lib.sa_boost_hist_bins(one, 16, one, 1, one, one, one, 0, 0, 1, 1, one, None) == 0
+    assert lib.sa_boost_hist_bins(one, 16, one, None, 0, 1, one, one, one, 17, 0, 1, 1, one, None) == E
+    assert lib.sa_boost_hist_bins(one, 18, one, None, 0, 1, one, one, one, 17, 0, 1, 1, one, None) == E
+    assert lib.sa_boost_hist_bins(one, 16, one, None, 0, 1, one, one, one, 8, 1, 1, 1, one, None) == E
+    assert lib.sa_boost_hist_bins(None, 16, one, None, 0, 1, one, one, one, 8, 0, 1, 1, one, None) == E
+    assert lib.sa_boost_hist_bins(one, 16, one, None, 0, 1, one, one, one, 0, 0, 1, 1, one, None) == 0
     sp = lambda **k: lib.sa_boost_split(*[{**dict(  # noqa: E731
-        hist=one, cs=one, cuts=one, F=1, node0=0, nn=1, leaf=0, lam=1.0, mcw=1.0, gamma=0.0, eta=0.3, bg=one,
-        bc=one, tree=one, st=None), **k}[a] for a in (
-            'hist', 'cs', 'cuts', 'F', 'node0', 'nn', 'leaf', 'lam', 'mcw', 'gamma', 'eta', 'bg', 'bc', 'tree', 'st')])
+        hist=one, cs=one, cuts=one, F=1, node0=0, nn=1, leaf=0, lam=1.0, mcw=1.0, gamma=0.0, eta=0.3, alpha=0.0, e=0,
+        mask=None, bg=one, bc=one, tree=one, st=None), **k}[a] for a in (
+            'hist', 'cs', 'cuts', 'F', 'node0', 'nn', 'leaf', 'lam', 'mcw', 'gamma', 'eta', 'alpha', 'e', 'mask', 'bg',
+            'bc', 'tree', 'st')])
     assert sp(F=0) == E and sp(nn=3) == E and sp(node0=2) == E and sp(tree=None) == E and sp(hist=None) == E
     assert sp(lam=-1.0) == E and sp(mcw=float('nan')) == E and sp(nn=64, node0=63) == E
     assert sp(nn=128, node0=127, leaf=1) == E

@@ -224,7 +224,7 @@ def test_sample_entry_points_validate_without_a_gpu():
     one = ctypes.c_void_p(16)  # a non-null pointer that is never dereferenced
     E = _native.SA_EINVAL
     order = ('margin', 'y', 'mask', 'n', 'w', 'spw', 'e', 'keys', 'seed', 'round', 'thr', 'gq', 'hq', 'p', 'node', 'st')
-    gr = lambda **k: lib.sa_boost_grad_ex(*[{**dict(  # noqa: E731
+    gr = lambda **k: lib.sa_boost_grad(*[{**dict(  # noqa: E731
         margin=one, y=one, mask=None, n=0, w=None, spw=1.0, e=0, keys=None, seed=0, round=0, thr=2 ** 32, gq=one,
         hq=one, p=one, node=one, st=None), **k}[a] for a in order])
     assert gr() == 0 and gr(w=one, keys=one, e=20, spw=3.0, thr=0, seed=2 ** 63 - 1, round=10 ** 6) == 0
@@ -232,25 +232,26 @@ def test_sample_entry_points_validate_without_a_gpu():
     assert gr(e=-1) == E and gr(e=21) == E and gr(spw=0.0) == E and gr(spw=-1.0) == E and gr(spw=float('nan')) == E
     assert gr(spw=float('inf')) == E and gr(thr=2 ** 32 + 1) == E and gr(round=-1) == E
     assert gr(n=5, e=21) == E  # with rows, still before any launch
-    assert b'sa_boost_grad_ex' in lib.sa_last_error()
+    assert b'sa_boost_grad:' in lib.sa_last_error()
     order = ('hist', 'cs', 'cuts', 'F', 'node0', 'nn', 'leaf', 'lam', 'mcw', 'gamma', 'eta', 'alpha', 'e', 'mask',
              'bg', 'bc', 'tree', 'st')
-    sp = lambda **k: lib.sa_boost_split_ex(*[{**dict(  # noqa: E731
+    sp = lambda **k: lib.sa_boost_split(*[{**dict(  # noqa: E731
         hist=None, cs=one, cuts=one, F=1, node0=0, nn=1, leaf=0, lam=1.0, mcw=1.0, gamma=0.0, eta=0.3, alpha=0.0,
         e=0, mask=None, bg=one, bc=one, tree=one, st=None), **k}[a] for a in order])
     assert sp() == E  # hist is NULL: every case below fails before a launch whatever it changes
     assert sp(hist=one, alpha=-1.0) == E and sp(hist=one, alpha=float('nan')) == E
     assert sp(hist=one, alpha=float('inf')) == E and sp(hist=one, e=-1) == E and sp(hist=one, e=21) == E
     assert sp(hist=one, F=0) == E and sp(hist=one, nn=3) == E and sp(hist=one, lam=-1.0) == E
-    assert lib.sa_boost_hist_bins_ex(one, 16, one, one, 0, 1, one, one, one, 8, 0, 1, 1, one, None) == E
-    assert lib.sa_boost_hist_bins_ex(one, 16, one, one, 1, 1, one, one, one, 17, 0, 1, 1, one, None) == E
-    assert lib.sa_boost_hist_bins_ex(None, 16, one, one, 1, 1, one, one, one, 8, 0, 1, 1, one, None) == E
-    assert lib.sa_boost_hist_bins_ex(one, 16, one, one, 1, 1, one, one, one, 0, 0, 1, 1, one, None) == 0
-    assert lib.sa_boost_hist_bins_ex(one, 16, one, None, 0, 0, one, one, one, 8, 0, 1, 1, one, None) == 0
+    assert lib.sa_boost_hist_bins(one, 16, one, one, 0, 1, one, one, one, 8, 0, 1, 1, one, None) == E
+    assert lib.sa_boost_hist_bins(one, 16, one, one, 1, 1, one, one, one, 17, 0, 1, 1, one, None) == E
+    assert lib.sa_boost_hist_bins(None, 16, one, one, 1, 1, one, one, one, 8, 0, 1, 1, one, None) == E
+    assert lib.sa_boost_hist_bins(one, 16, one, one, 1, 1, one, one, one, 0, 0, 1, 1, one, None) == 0
+    assert lib.sa_boost_hist_bins(one, 16, one, None, 0, 0, one, one, one, 8, 0, 1, 1, one, None) == 0
     assert lib.sa_boost_row_keys(None, one, 4, one, None) == E and lib.sa_boost_row_keys(one, one, -1, one, None) == E
     assert lib.sa_boost_row_keys(one, one, 4, None, None) == E and lib.sa_boost_row_keys(None, None, 0, None, None) == 0
-    for name in ('sa_boost_grad_ex', 'sa_boost_split_ex', 'sa_boost_hist_bins_ex', 'sa_boost_row_keys'):
+    for name in ('sa_boost_grad', 'sa_boost_split', 'sa_boost_hist_bins', 'sa_boost_row_keys'):
         assert name in _native.EXPORTED_SYMBOLS
+    assert not [name for name in _native.EXPORTED_SYMBOLS if name.startswith('sa_boost_') and name.endswith('_ex')]
 
 
 # ----------------------------------------------------------------------------- importances

@@ -251,7 +251,7 @@ def test_histograms_over_more_row_steps_than_workgroups(sa, nodes, tail):
 
 
 def test_sampled_histograms_over_more_row_steps_than_workgroups(sa):
-    """sa_boost_hist_bins_ex at the first shape: a column list of 64 of the 128 matrix rows, out
+    """sa_boost_hist_bins with a row list at the first shape: a column list of 64 of the 128 matrix rows, out
     of order.  Only those features' histograms are filled, and they are the restatement's."""
     boost, nodes = sa['boost'], 32
     n, f_num, gx, steps = _trip_case(nodes, BINS_TILE + 3)

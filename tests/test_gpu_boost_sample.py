@@ -1,6 +1,6 @@
 """Sample weights, row / column subsampling and the L1 penalty of the device learner
-(``sa_boost_grad_ex``, ``sa_boost_split_ex``, ``sa_boost_hist_bins_ex``, ``sa_boost_row_keys``,
-socceraction_amd.boost) against the numpy restatement of contract items 13-17
+(the tuning arguments of ``sa_boost_grad``, ``sa_boost_split`` and ``sa_boost_hist_bins``,
+``sa_boost_row_keys``, socceraction_amd.boost) against the numpy restatement of contract items 13-17
 (tests/boost_sample_reference.py).  Integers, node records, margins and models are compared
 exactly; only ``expf`` against numpy's ``exp`` gets the 1e-6 relative bar of tests/test_gpu_boost.py."""
 import json
@@ -132,14 +132,21 @@ def test_grad_ex_equals_the_restatement(sa, n, e, spw):
     check(2 ** 31, _dev(big.view(np.int64)), big)
 
 
-def test_grad_ex_neutral_arguments_are_sa_boost_grad(sa):
+def test_grad_neutral_arguments_spelled_out_are_the_defaults(sa):
+    """One row, and one workgroup minus one, exactly, and plus one row: every neutral argument
+    written out -- a weight column of ones, the row index as the key, thr = 2^32, scale_pos_weight
+    = 1, shift = 0 -- gives the bytes of the call that leaves it out."""
     boost = sa['boost']
-    m = np.repeat(MARGINS, 2)
-    y = np.resize(np.array([0, 1], np.uint8), len(m))
-    plain = boost.gradients(_dev(m), _dev(y))
-    ex = boost.gradients(_dev(m), _dev(y), weight=_dev(np.ones(len(m), np.float32)), thr=2 ** 32)
-    for a, b in zip(plain, ex):
-        assert a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
+    for n in (1, 255, 256, 257):
+        m = np.resize(np.repeat(MARGINS, 2), n)
+        y = np.resize(np.array([0, 1], np.uint8), n)
+        plain = [a.cpu().numpy().tobytes() for a in boost.gradients(_dev(m), _dev(y))]
+        assert [len(b) for b in plain] == [4 * n] * 3
+        ones, index = _dev(np.ones(n, np.float32)), _dev(np.arange(n, dtype=np.int64))
+        for kw in (dict(weight=ones), dict(row_keys=index), dict(thr=2 ** 32), dict(scale_pos_weight=1.0, shift=0),
+                   dict(weight=ones, row_keys=index, thr=2 ** 32, scale_pos_weight=1.0, shift=0)):
+            got = [a.cpu().numpy().tobytes() for a in boost.gradients(_dev(m), _dev(y), **kw)]
+            assert got == plain, (n, sorted(kw))
 
 
 # ----------------------------------------------------------------------------- row keys
@@ -245,7 +252,7 @@ def test_split_ex_equals_the_restatement(sa, case, e):
     got = sa['boost'].best_splits(_dev(h), tot, cuts, **{k: v for k, v in kw.items()}, shift=e, feature_mask=mask)
     print(case, e, got, rec)
     _same_records(got, rec, case)
-    if e == 0 and not kw.get('reg_alpha') and features is None:  # neutral arguments: sa_boost_split itself
+    if e == 0 and not kw.get('reg_alpha') and features is None:  # the neutral arguments left out
         assert sa['boost'].best_splits(_dev(h), tot, cuts, **kw).tobytes() == got.tobytes()
 
 
@@ -348,7 +355,7 @@ WIDE_TUNED = dict(n_estimators=2, max_depth=6, subsample=0.5, colsample_bytree=0
 def test_tuned_fit_over_many_workgroups(sa):
     """The 40,000 x 388 table of tests/test_gpu_boost.py (more row steps than workgroups at every
     level, twenty bitmap tiles) under a row sample, a column sample -- the sampled bin histograms
-    (sa_boost_hist_bins_ex) past one trip -- and weights with shift 3."""
+    (sa_boost_hist_bins with a row list) past one trip -- and weights with shift 3."""
     from test_gpu_boost import bins_launch, wide_table
     t = wide_table()
     X, y, cuts, B = t['X'], t['y'], t['cuts'], t['B']
@@ -382,13 +389,25 @@ def test_tuned_fit_over_many_workgroups(sa):
     assert splits[:, 0].all() and splits[:, 31:63].any(axis=1).all()  # both rounds split, down to level 5
 
 
-def _families(sa, clf, fit):
-    """The (family, entry point) sequence of the launches of ``fit(clf)``."""
+# where the tuning arguments stand in each entry point's argument list (include/socceraction_amd.h):
+# grad: weight, scale_pos_weight, shift, row_keys, thr; hist_bins: num_rows; split: reg_alpha, shift, feature_mask
+TUNING_ARGS = {'grad': (4, 5, 6, 7, 10), 'hist_bins': (3,), 'split': (11, 12, 13)}
+NEUTRAL_ARGS = {'grad': (None, 1.0, 0, None, 2 ** 32), 'hist_bins': (None,), 'split': (0.0, 0, None)}
+GRAD_GQ = 11
+
+
+def _families(sa, clf, fit, tuning=None):
+    """The (family, entry point) sequence of the launches of ``fit(clf)``; ``tuning`` (a list)
+    receives, for every launch of a family in TUNING_ARGS, ``(family, its tuning arguments)`` --
+    for a gradient launch with its ``gq`` argument appended."""
     seq = []
     plain = clf._launch
 
     def launch(family, fn, *args):
         seq.append((family, fn.__name__))
+        if tuning is not None and family in TUNING_ARGS:
+            extra = (args[GRAD_GQ],) if family == 'grad' else ()
+            tuning.append((family, tuple(args[i] for i in TUNING_ARGS[family]) + extra))
         plain(family, fn, *args)
     clf._launch = launch
     fit(clf)
@@ -398,16 +417,23 @@ def _families(sa, clf, fit):
 def test_neutral_parameters_change_nothing(sa, game, monkeypatch):
     boost, fb = sa['boost'], game['fb']
     base = boost.DeviceGBTClassifier(n_estimators=4)
-    seq0 = _families(sa, base, lambda c: c.fit_blocks(fb, game['yd'], cuts=game['cuts']))
+    tun0, tun1 = [], []
+    seq0 = _families(sa, base, lambda c: c.fit_blocks(fb, game['yd'], cuts=game['cuts']), tun0)
     neutral = dict(subsample=1.0, colsample_bytree=1.0, reg_alpha=0.0, scale_pos_weight=1.0, random_state=9)
-    # explicit neutral values: today's entry points, launch for launch, and no host read for the weights
+    # explicit neutral values: the plain fit's launches, launch for launch, and no host read for the weights
     same = boost.TunedGBTClassifier(n_estimators=4, **neutral)
-    monkeypatch.setattr(boost.DeviceGBTClassifier, '_weight_shift',
-                        lambda *a: (_ for _ in ()).throw(AssertionError('a host read')))
+    for reader in ('_weight_shift', '_weight_stats'):
+        monkeypatch.setattr(boost.DeviceGBTClassifier, reader,
+                            lambda *a: (_ for _ in ()).throw(AssertionError('a host read')))
     seq1 = _families(sa, same, lambda c: c.fit_blocks(fb, game['yd'], cuts=game['cuts'],
-                                                      row_keys=np.arange(fb.n)[::-1].copy()))
+                                                      row_keys=np.arange(fb.n)[::-1].copy()), tun1)
     monkeypatch.undo()
-    assert seq1 == seq0 and not any(name.endswith('_ex') for _, name in seq0)
+    assert seq1 == seq0
+    # every launch of both fits carries the neutral constants (the last gradient launch no gq besides)
+    for tun in (tun0, tun1):
+        assert {f for f, _ in tun} == set(TUNING_ARGS) and tun[-1][0] == 'grad' and tun[-1][1][-1] is None
+        for family, args in tun:
+            assert args[:len(NEUTRAL_ARGS[family])] == NEUTRAL_ARGS[family], (family, args)
     assert same.trees_.tobytes() == base.trees_.tobytes() and same.quant_shift_ == 0
     # ... plus a weight column of ones: the same trees and the same families
     ones = boost.TunedGBTClassifier(n_estimators=4, **neutral)
@@ -419,31 +445,56 @@ def test_neutral_parameters_change_nothing(sa, game, monkeypatch):
     assert ones.column_samples_ is None
 
 
-def test_launch_sequence_of_a_tuned_fit(sa, game):
+def test_launch_sequence_of_a_tuned_fit(sa, game, monkeypatch):
     """The (family, entry point) sequence of a tuned fit, written out from the contract: per round
-    the tuned gradients; per level the bitmap histograms always, the sampled bin histograms exactly
-    when the round's sample holds a numeric feature, the tuned split search and the advance; then
-    the leaf values and the margin; after the last round the plain gradients for ``p_``."""
+    the gradients; per level the bitmap histograms always, the bin histograms exactly when the
+    round's sample holds a numeric feature, the split search and the advance; then the leaf values
+    and the margin; after the last round the gradients for ``p_``.  What tells a tuned launch is its
+    arguments: every round's gradients carry the weight column, the fit's shift and the row
+    threshold, the last launch (no ``gq``) the neutral ones; every bin histogram a row list; every
+    split launch the L1 penalty and the shift, and every level's search the round's mask (the leaf
+    values' launch searches nothing and gets none)."""
+    boost = sa['boost']
     D, T = 2, 5
+    F = len(game['fb'].plan.names)
+    uploaded = []
+    upload = boost.weights_to_device
+    monkeypatch.setattr(boost, 'weights_to_device', lambda w, dev: uploaded.append(upload(w, dev)) or uploaded[-1])
     for which in ('all_on', 'one_column'):
-        clf = sa['boost'].TunedGBTClassifier(**{**FITS[which], 'max_depth': D, 'n_estimators': T})
+        params = {**FITS[which], 'max_depth': D, 'n_estimators': T}
+        clf = boost.TunedGBTClassifier(**params)
+        tun = []
         seq = _families(sa, clf, lambda c: c.fit_blocks(game['fb'], game['yd'], cuts=game['cuts'],
-                                                        sample_weight=game['w']))
+                                                        sample_weight=game['w']), tun)
         assert len(clf.column_samples_) == T
         numeric = [bool((~game['is_bool'][S]).any()) for S in clf.column_samples_]
         if which == 'one_column':  # one feature a round: rounds with and without a numeric one occur
             assert True in numeric and False in numeric, numeric
         want = []
         for t in range(T):
-            want.append(('grad', 'sa_boost_grad_ex'))
+            want.append(('grad', 'sa_boost_grad'))
             for _ in range(D):
                 want.append(('hist_bits', 'sa_boost_hist_bits'))
                 if numeric[t]:
-                    want.append(('hist_bins', 'sa_boost_hist_bins_ex'))
-                want += [('split', 'sa_boost_split_ex'), ('advance', 'sa_boost_advance')]
-            want += [('split', 'sa_boost_split_ex'), ('advance', 'sa_boost_advance')]
+                    want.append(('hist_bins', 'sa_boost_hist_bins'))
+                want += [('split', 'sa_boost_split'), ('advance', 'sa_boost_advance')]
+            want += [('split', 'sa_boost_split'), ('advance', 'sa_boost_advance')]
         want.append(('grad', 'sa_boost_grad'))
         assert seq == want, which
+        e, wptr = clf.quant_shift_, uploaded[-1].data_ptr()
+        assert e == 4 and wptr
+        grads = [a for f, a in tun if f == 'grad']
+        assert len(grads) == T + 1
+        for a in grads[:T]:  # (the default key: a non-sharded fit passes no key column)
+            assert a[:5] == (wptr, params['scale_pos_weight'], e, None, bs.threshold(params['subsample'])) and a[5]
+        assert grads[T] == NEUTRAL_ARGS['grad'] + (None,)
+        bins = [a for f, a in tun if f == 'hist_bins']
+        assert len(bins) == D * sum(numeric) and all(a[0] for a in bins)
+        splits = [a for f, a in tun if f == 'split']
+        assert len(splits) == T * (D + 1) and splits[0][2]
+        for k, a in enumerate(splits):  # round t's mask is row t of the fit's [T, F] byte table
+            t, leaves = divmod(k, D + 1)[0], k % (D + 1) == D
+            assert a == (params['reg_alpha'], e, None if leaves else splits[0][2] + t * F), (k, a)
 
 
 def test_weight_duplication_on_the_device(sa, game):
