@@ -656,6 +656,24 @@ int sa_segment_offsets(const int32_t* key, int64_t n, int64_t n_segments, int64_
  * >= 2*ceil(n/16); the block's tile_rows a multiple of 16 and its data 16-byte aligned. */
 int sa_pack_bits(const sa_block* bool_blk, int64_t n, uint8_t* bits, int64_t col_stride, void* stream);
 
+/* ---- row selection -----------------------------------------------------------------
+ * The shot rows of the expected-goals notebook (EXTRA-build-expected-goals-model.ipynb:
+ * `Xi[shot_idx]`), or any other row list: rows[m] (device, int64 source row numbers in [0, n),
+ * any order, repeats allowed) of bitmap-form feature blocks of n rows, gathered in list order.
+ * Source: the numeric blocks f_blk / i_blk, tiled [tiles, C, R] (R a multiple of 16; f32 = 0:
+ * float64 + int64 elements, f32 = 1: both float32) and the bool bitmaps bits [n_bool][words_in]
+ * int64 (bit i of word w = row 64w + i; words_in * 64 >= n).
+ * Output: one-tile numeric blocks f_out / i_out [C][ld_out] of the same element types (ld_out a
+ * multiple of 16, >= m; element bits copied unchanged, elements m .. ld_out - 1 zero) and
+ * bitmaps bits_out [n_bool][words_out] (words_out >= ceil(m / 64)): bit i of word j of column c
+ * = the source bit of row rows[64j + i]; the bits at or beyond m of word ceil(m / 64) - 1 are
+ * zero, later words are not written.  A row number outside [0, n) is clamped into it (callers
+ * check the range first).  m = 0, or no column at all: SA_OK, nothing is launched. */
+int sa_select_rows(const sa_block* f_blk, const sa_block* i_blk, int32_t f32, const int64_t* bits,
+                   int64_t words_in, int32_t n_bool, int64_t n, const int64_t* rows, int64_t m,
+                   void* f_out, void* i_out, int64_t ld_out, int64_t* bits_out, int64_t words_out,
+                   void* stream);
+
 /* ---- gradient-boosted trees on the feature blocks --------------------------------
  * The learner call of VAEP.rate (`_estimate_probabilities`, vaep/base.py:284-294): P(class 1)
  * of a binary gradient-boosted tree ensemble for every row of the feature blocks.

@@ -496,19 +496,41 @@ def _bin(names, kinds_cols, bits, f_blk, i_blk, f32: bool, n: int, cuts) -> Binn
                       fmap, d)
 
 
-def bin_blocks(blocks, cuts: Optional[Sequence[np.ndarray]] = None, rows=None, process_group=None) -> BinnedData:
+def plan_columns(plan, columns: Sequence[str]) -> List[int]:
+    """The positions in ``plan.order`` of the feature names ``columns``; an unknown or repeated
+    name is a ``ValueError``."""
+    where = {name: j for j, name in enumerate(plan.names)}
+    names = [str(c) for c in columns]
+    unknown = [c for c in names if c not in where]
+    if unknown:
+        raise ValueError(f'{" and ".join(unknown)} are not available in the features')
+    if len(set(names)) != len(names):
+        raise ValueError(f'repeated feature names: {sorted({c for c in names if names.count(c) > 1})}')
+    return [where[c] for c in names]
+
+
+def bin_blocks(blocks, cuts: Optional[Sequence[np.ndarray]] = None, rows=None, process_group=None,
+               columns: Optional[Sequence[str]] = None) -> BinnedData:
     """Bin device feature blocks (``ops.features(..., bool_bits=True)``; float64 / int64 or
     float32 numeric blocks): ``sa_boost_bin`` for the numeric features, the bitmaps as they are.
     ``cuts``: explicit cut lists (model order), default :func:`make_cuts` on ``rows`` (with
-    ``process_group``: of all ranks' rows)."""
+    ``process_group``: of all ranks' rows).  ``columns``: the feature names of the plan the model
+    uses, in the model's feature order (default: every feature, in plan order); ``cuts`` then has
+    one entry per name of ``columns``."""
     plan = blocks.plan
     if plan.n_bool and blocks.bool_bits is None:
         raise ValueError('the bool features must come as bitmaps (ops.features(..., bool_bits=True))')
+    order = list(plan.order)
+    pick = None if columns is None else plan_columns(plan, columns)  # before the cut sample's device work
     if cuts is None:
         cuts = make_cuts(blocks, rows, process_group)
-    kc = [(kind, col) for _, kind, col in plan.order]
-    return _bin(list(plan.names), kc, blocks.bool_bits, blocks.f64_block, blocks.i64_block, blocks.num32,
-                blocks.n, cuts)
+        if pick is not None:
+            cuts = [cuts[j] for j in pick]
+    if pick is not None:
+        order = [order[j] for j in pick]
+    kc = [(kind, col) for _, kind, col in order]
+    return _bin([name for name, _, _ in order], kc, blocks.bool_bits, blocks.f64_block, blocks.i64_block,
+                blocks.num32, blocks.n, cuts)
 
 
 def bin_host(X, cuts: Optional[Sequence[np.ndarray]] = None, rows=None, device=None, process_group=None) -> BinnedData:

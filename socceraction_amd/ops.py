@@ -266,6 +266,39 @@ def features(batch: ActionBatch, xfns: Sequence[str], k: int, flip: bool = True,
     return out
 
 
+def select_rows(blocks: FeatureBlocks, rows) -> FeatureBlocks:
+    """The listed rows of bitmap-form feature blocks (``features(..., bool_bits=True)``, either
+    numeric dtype) as bitmap-form blocks of their own (``sa_select_rows``): the same plan,
+    ``n = len(rows)``, one tile, row ``q`` = source row ``rows[q]``.  ``rows``: a device int64
+    tensor or anything ``torch.as_tensor`` accepts, in any order, repeats allowed; a row outside
+    ``[0, blocks.n)`` is a ``ValueError`` before any launch (one ``aminmax`` read back).  Element
+    bits are copied unchanged, the padding of the numeric tile and the last bitmap word's bits at
+    or beyond ``n`` are zero: every consumer of feature blocks takes the result as it is."""
+    if blocks.bool_bits is None:
+        raise ValueError('select_rows takes the bitmap form (ops.features(..., bool_bits=True))')
+    dev = blocks.device
+    rows = torch.as_tensor(rows, device=dev).reshape(-1).to(torch.int64).contiguous()
+    m = int(rows.numel())
+    if m:
+        lo, hi = (int(v) for v in torch.aminmax(rows))
+        if lo < 0 or hi >= blocks.n:
+            raise ValueError(f'rows must be inside [0, {blocks.n}): got {lo} .. {hi}')
+    plan, ld, words = blocks.plan, _ld(m), max(1, (m + 63) // 64)
+    # m > 0: the kernels write every element, padding included
+    alloc = torch.empty if m else torch.zeros
+    out = FeatureBlocks(plan, m, 1024, ld, None,
+                        alloc((1, plan.n_f64, ld), dtype=blocks.f64_block.dtype, device=dev),
+                        alloc((1, plan.n_i64, ld), dtype=blocks.i64_block.dtype, device=dev),
+                        (alloc if plan.n_bool else torch.zeros)((max(plan.n_bool, 1), words), dtype=torch.int64,
+                                                                device=dev))
+    fb, ib = blocks.sa_blocks()[-2:]
+    _native.check(_native.lib().sa_select_rows(
+        ctypes.byref(fb), ctypes.byref(ib), int(blocks.num32), _ptr(blocks.bool_bits), blocks.bool_bits.shape[1],
+        plan.n_bool, blocks.n, _ptr(rows), m, _ptr(out.f64_block), _ptr(out.i64_block), ld, _ptr(out.bool_bits),
+        words, stream_handle()))
+    return out
+
+
 def features_explicit(frames: Sequence[ActionBatch], xfns: Sequence[str]) -> FeatureBlocks:
     """Features of a user-built list of game-state frames (module-level transformers)."""
     plan = build_plan(xfns, len(frames), frames[0].atomic)

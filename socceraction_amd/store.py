@@ -80,7 +80,8 @@ def features_to_arrow(blocks) -> 'pa.Table':
     _need_arrow()
     n = blocks.n
     plan = blocks.plan
-    bits = pack_bits(blocks.bool_block, blocks.Rb, n) if plan.n_bool else None
+    # (_blk('b'): a bitmap-form table, e.g. ops.select_rows' result, unpacks its bools first)
+    bits = pack_bits(blocks._blk('b'), blocks.Rb, n) if plan.n_bool else None
     hb = _to_pinned(bits) if bits is not None else None
     hosts = {}
     for k in 'fi':
