@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SA_ABI_VERSION 4
+#define SA_ABI_VERSION 5
 #define SA_MAX_FRAMES 8 /* max frames n_frames == k of explicit-frame mode (windowed mode: any k) */
 #define SA_BOOL_TILE_QUANTUM 1024 /* bool block: rows per tile must be a multiple of this */
 #define SA_NUM_TILE_QUANTUM 128   /* f64 / i64 blocks: rows per tile must be a multiple of this */
@@ -276,6 +276,21 @@ int sa_xt_count_codes(const sa_actions* a, int32_t l, int32_t w, int64_t* shot, 
                       int64_t* move, int32_t* trans, int32_t* err_flags, uint32_t* codes,
                       int32_t flags, void* stream);
 
+/* Which count pass sa_xt_count, sa_xt_count_codes and sa_xt_count_cells run for an (l, w) grid,
+ * n actions and `flags` (host only, no device call; the launcher itself asks this function):
+ * WIDE = every bin as u32 in one workgroup's LDS per CU (l * w <= 194, without
+ * SA_XT_COUNT_SHARED), SMALL = per-32768-action LDS histograms with the C x C bins packed two
+ * u16 per word (l * w <= 199), BANDS = the band-owned count below (200 <= l * w <= 12000 and
+ * n < 2^31), VEC = the three C-vectors in LDS and global atomics into the C x C table (only a
+ * band-sized grid with n >= 2^31), GLOBAL = global atomics for everything (l * w > 12000).
+ * Returns the mode, or SA_EINVAL for a bad grid or n < 0. */
+#define SA_XT_COUNT_MODE_GLOBAL 0
+#define SA_XT_COUNT_MODE_VEC 1
+#define SA_XT_COUNT_MODE_SMALL 2
+#define SA_XT_COUNT_MODE_WIDE 3
+#define SA_XT_COUNT_MODE_BANDS 4
+int sa_xt_count_mode(int32_t l, int32_t w, int64_t n, int32_t flags);
+
 /* xT cell codes: the binning of a fit + rate of the SAME actions on an (l, w) grid with
  * l * w <= SA_XT_CELLS_MAX_C, computed once per action where the coordinates are read anyway
  * (sa_vaep_features_xt, or sa_xt_cells alone) and consumed by sa_xt_count_cells and
@@ -301,8 +316,9 @@ int sa_xt_count_cells(const uint32_t* cells, int64_t n, int32_t l, int32_t w, in
 int sa_xt_rate_cells(const uint32_t* cells, int64_t n, int32_t l, int32_t w, const double* grid,
                      double* out, int32_t* err_flags, void* stream);
 
-/* Band-owned count of large grids (203 <= C <= ~12000 cells, e.g. 105 x 68; sa_xt_band_shape
- * says whether a grid takes it): the transition counts without global atomics.  sa_xt_count,
+/* Band-owned count of large grids (200 <= C <= 12000 cells, e.g. 105 x 68; sa_xt_count_mode
+ * says whether a grid takes it, sa_xt_band_shape its shape -- also of smaller grids, which the
+ * bucket calls below accept): the transition counts without global atomics.  sa_xt_count,
  * sa_xt_count_codes and sa_xt_count_cells use it internally for such grids; a fit over several
  * device batches calls, per batch, sa_xt_count_bucket -- one key per counted action, sorted by
  * start-cell band into buckets[n] (u16: the action's bin in its band's R x P histogram,

@@ -24,6 +24,9 @@ SA_SEG_BLOCK = 128  # rows per entry of sa_actions.seg_of_block
 SA_XT_SOLVE_MAX_C = 1024  # sa_xt_solve: larger grids may pass trans_t = NULL
 SA_XT_CELLS_MAX_C = 4096
 SA_XT_COUNT_SHARED, SA_XT_COUNT_OVERWRITE, SA_XT_COUNT_COMPACT_ONLY = 1, 2, 4
+# sa_xt_count_mode: the count pass a grid takes
+(SA_XT_COUNT_MODE_GLOBAL, SA_XT_COUNT_MODE_VEC, SA_XT_COUNT_MODE_SMALL, SA_XT_COUNT_MODE_WIDE,
+ SA_XT_COUNT_MODE_BANDS) = 0, 1, 2, 3, 4
 SA_XT_CELLS16_MAX_C = 202  # xT cell codes: 16 bits per action up to this many cells
 SA_XT_COMPACT_MAX_C = 9472  # sa_xt_compact_rows / sa_xt_iterate_compact
 SA_XT_SOLVE_EXACT = 1  # sa_xt_solve_ex / sa_xt_solve_compact: the reference's summation order
@@ -186,6 +189,7 @@ _SIGNATURES = {
     'sa_xt_probabilities': (ctypes.c_int, [_p, _p, _p, ctypes.c_int32, _p, _p, _p, _p]),
     'sa_xt_iterate_rows': (ctypes.c_int, [_p, _p, _p, _p, ctypes.c_int32, ctypes.c_int32,
                                           ctypes.c_int32, _p, ctypes.c_double, _p, _p, _p, _p]),
+    'sa_xt_count_mode': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
     'sa_xt_band_shape': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                         ctypes.POINTER(ctypes.c_int32)]),
     'sa_xt_count_bucket': (ctypes.c_int, [ctypes.POINTER(SaActions), _p, ctypes.c_int64, ctypes.c_int32,
@@ -342,7 +346,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    if lib.sa_abi_version() != 4:
+    if lib.sa_abi_version() != 5:
         raise ImportError('libsocceraction_amd ABI version mismatch')
     _check_build_id(lib, path)
     if path == LIB_PATH:

@@ -30,14 +30,18 @@ namespace sa {
 // ~10k, e.g. 105 x 68): only the three C-vectors in LDS -- every move hits move[start], so
 // global atomics there serialise on a few thousand hot addresses -- and the sparse C x C
 // transition counts as global atomics.  XC_GLOBAL: global atomics for everything.
-// XC_WIDE (C <= 197, e.g. 16 x 12): all 3C + C*C bins as u32 in one 1024-thread workgroup's LDS
+// XC_WIDE (C <= 194, e.g. 16 x 12): all 3C + C*C bins as u32 in one 1024-thread workgroup's LDS
 // (150 KB at C = 192, one workgroup per CU), each workgroup counting one contiguous chunk of
 // the actions -- 16 waves per CU keep the loads in flight, and the C*C flush happens once per
 // CU instead of once per 32k actions (16M actions: 472 -> see DESIGN.md).
 constexpr int XT_THREADS = 256;
 constexpr int XT_WIDE_THREADS = 1024;
 constexpr int XT_SMALL_ACTS = 32768;  // actions per workgroup in XC_SMALL / XC_VEC
-enum { XC_GLOBAL = 0, XC_VEC = 1, XC_SMALL = 2, XC_WIDE = 3 };
+enum { XC_GLOBAL = 0, XC_VEC = 1, XC_SMALL = 2, XC_WIDE = 3, XC_BANDS = 4 };
+static_assert(XC_GLOBAL == SA_XT_COUNT_MODE_GLOBAL && XC_VEC == SA_XT_COUNT_MODE_VEC &&
+                  XC_SMALL == SA_XT_COUNT_MODE_SMALL && XC_WIDE == SA_XT_COUNT_MODE_WIDE &&
+                  XC_BANDS == SA_XT_COUNT_MODE_BANDS,
+              "sa_xt_count_mode's values");
 
 template <int MODE>
 __device__ __forceinline__ void count_one(const XtAct& a, int C, uint32_t* hs, uint32_t* hg, uint32_t* hm,
@@ -976,6 +980,32 @@ extern "C" int sa_xt_count(const sa_actions* a, int32_t l, int32_t w, int64_t* s
   return sa_xt_count_codes(a, l, w, shot, goal, move, trans, err_flags, nullptr, 0, stream);
 }
 
+// Which count pass a grid of C cells and a batch of n actions take (host only; what
+// sa_xt_count_mode reports).  XC_WIDE while 3C + C*C u32 bins fit 150 KB of LDS (C <= 194), unless
+// SA_XT_COUNT_SHARED: the pass runs next to other kernels (bench.py's side stream), so use the
+// 80-KB-LDS workgroups that co-reside with them instead of one 150-KB workgroup per CU, which
+// waits for whole CUs to drain (in-process A/B: 3.35 vs 3.40 ms per step).  XC_SMALL while 3C u32
+// + C*C packed u16 bins fit 80 KB (C <= 199); the band-owned count (XC_BANDS, sa_xt_large.hip)
+// while it holds the grid (C <= 12000) and n fits its 32-bit positions; XC_VEC (only then: more
+// than 2^31 - 1 actions) while 3C u32 bins fit 120 KB; XC_GLOBAL for the rest.
+static int count_mode(int C, int64_t n, int32_t flags) {
+  const size_t c = (size_t)C;  // 3C + C*C passes 2^31 at the largest grid
+  const size_t wide_lds = (3 * c + c * c) * 4;
+  const size_t small_lds = (3 * c + (c * c + 1) / 2) * 4;
+  const size_t vec_lds = 3 * c * 4;
+  if (wide_lds <= 150 * 1024 && !(flags & SA_XT_COUNT_SHARED)) return XC_WIDE;
+  if (small_lds <= 80 * 1024) return XC_SMALL;
+  if (xt_band_ok(C) && n <= INT32_MAX) return XC_BANDS;
+  if (vec_lds <= 120 * 1024) return XC_VEC;
+  return XC_GLOBAL;
+}
+
+extern "C" int sa_xt_count_mode(int32_t l, int32_t w, int64_t n, int32_t flags) {
+  if (int rc = check_grid(l, w)) return rc;
+  if (n < 0) return fail(SA_EINVAL, "negative action count");
+  return count_mode(l * w, n, flags);
+}
+
 // Count-pass launcher shared by the coordinate path (cells == nullptr) and the cell-code path.
 static int launch_count(const sa_actions& A, const uint32_t* cells, int64_t n, int32_t l, int32_t w,
                         int64_t* shot, int64_t* goal, int64_t* move, int32_t* trans, int32_t* err_flags,
@@ -987,12 +1017,8 @@ static int launch_count(const sa_actions& A, const uint32_t* cells, int64_t n, i
   auto* um = reinterpret_cast<unsigned long long*>(move);
   const size_t vec_lds = (size_t)3 * C * 4;
   const unsigned wg_blocks = (unsigned)((n + XT_SMALL_ACTS - 1) / XT_SMALL_ACTS);
-  const size_t wide_lds = (size_t)(3 * C + C * C) * 4;
+  const size_t wide_lds = (3 * (size_t)C + (size_t)C * C) * 4;
   const bool cl = cells != nullptr;
-  // SA_XT_COUNT_SHARED: the pass runs next to other kernels (bench.py's side stream), so use the
-  // 80-KB-LDS workgroups that co-reside with them instead of one 150-KB workgroup per CU, which
-  // waits for whole CUs to drain (in-process A/B: 3.35 vs 3.40 ms per step)
-  const bool shared = (flags & SA_XT_COUNT_SHARED) != 0;
 #define SA_COUNT_LAUNCH(MODE, GRID, BLOCK, LDS, CHUNK)                                                   \
   do {                                                                                                  \
     if (cl)                                                                                             \
@@ -1002,24 +1028,30 @@ static int launch_count(const sa_actions& A, const uint32_t* cells, int64_t n, i
       hipLaunchKernelGGL((xt_count_kernel<MODE, false>), GRID, BLOCK, LDS, st, A, nullptr, n, l, w, us,   \
                          ug, um, trans, err_flags, (int64_t)(CHUNK), codes);                            \
   } while (0)
-  if (wide_lds <= 150 * 1024 && !shared) {
-    // one workgroup per CU (or fewer when there are few actions: >= 4096 actions each)
-    const int cus = device_cus(current_device());
-    int64_t blocks = (n + 4095) / 4096;
-    if (blocks > cus) blocks = cus;
-    const int64_t chunk = (n + blocks - 1) / blocks;
-    SA_COUNT_LAUNCH(XC_WIDE, dim3((unsigned)blocks), dim3(XT_WIDE_THREADS), wide_lds, chunk);
-  } else if (small_lds <= 80 * 1024) {
-    SA_COUNT_LAUNCH(XC_SMALL, dim3(wg_blocks), dim3(XT_THREADS), small_lds, XT_SMALL_ACTS);
-  } else if (xt_band_ok(C) && n <= INT32_MAX) {
-    // band-owned count (sa_xt_large.hip): no global atomics into the C x C table
-    return xt_count_bands(A, cells, n, l, w, shot, goal, move, trans, err_flags, codes, st);
-  } else if (vec_lds <= 120 * 1024) {
-    SA_COUNT_LAUNCH(XC_VEC, dim3(wg_blocks), dim3(XT_THREADS), vec_lds, XT_SMALL_ACTS);
-  } else {
-    int64_t blocks = (n + XT_THREADS - 1) / XT_THREADS;
-    if (blocks > 4096) blocks = 4096;
-    SA_COUNT_LAUNCH(XC_GLOBAL, dim3((unsigned)blocks), dim3(XT_THREADS), 0, 0);
+  switch (count_mode(C, n, flags)) {
+    case XC_WIDE: {
+      // one workgroup per CU (or fewer when there are few actions: >= 4096 actions each)
+      const int cus = device_cus(current_device());
+      int64_t blocks = (n + 4095) / 4096;
+      if (blocks > cus) blocks = cus;
+      const int64_t chunk = (n + blocks - 1) / blocks;
+      SA_COUNT_LAUNCH(XC_WIDE, dim3((unsigned)blocks), dim3(XT_WIDE_THREADS), wide_lds, chunk);
+      break;
+    }
+    case XC_SMALL:
+      SA_COUNT_LAUNCH(XC_SMALL, dim3(wg_blocks), dim3(XT_THREADS), small_lds, XT_SMALL_ACTS);
+      break;
+    case XC_BANDS:
+      // band-owned count (sa_xt_large.hip): no global atomics into the C x C table
+      return xt_count_bands(A, cells, n, l, w, shot, goal, move, trans, err_flags, codes, st);
+    case XC_VEC:
+      SA_COUNT_LAUNCH(XC_VEC, dim3(wg_blocks), dim3(XT_THREADS), vec_lds, XT_SMALL_ACTS);
+      break;
+    default: {
+      int64_t blocks = (n + XT_THREADS - 1) / XT_THREADS;
+      if (blocks > 4096) blocks = 4096;
+      SA_COUNT_LAUNCH(XC_GLOBAL, dim3((unsigned)blocks), dim3(XT_THREADS), 0, 0);
+    }
   }
 #undef SA_COUNT_LAUNCH
   return check_launch("xt_count_kernel");

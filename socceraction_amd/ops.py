@@ -496,10 +496,14 @@ def xt_count(batch: ActionBatch, l: int, w: int, acc: Optional[XTCounts] = None,
 
 
 def xt_band_shape(l: int, w: int) -> Optional[Tuple[int, int]]:
-    """(start cells per band, bands) of the band-owned count of an (l, w) grid, or None when
-    the grid takes the LDS-histogram (small) or global-atomic (very large) count instead."""
+    """(start cells per band, bands) of the bucketed, band-owned count of an (l, w) grid
+    (:func:`xt_bucket` + :func:`xt_count_buckets`, which :func:`xt_count_many` runs), or None
+    when such a fit counts batch by batch with :func:`xt_count` instead: grids of up to
+    ``SA_XT_CELLS16_MAX_C`` = 202 cells and grids above the band count's 12000."""
     C = l * w
-    if C <= 202 or C > 46340:  # the XC_WIDE / XC_SMALL LDS passes hold these whole
+    # <= 199 cells the XC_WIDE / XC_SMALL LDS passes hold whole; 200 - 202 sa_xt_count itself
+    # counts by bands (sa_xt_count_mode); the bucketed fit starts above the 16-bit cell codes
+    if C <= _native.SA_XT_CELLS16_MAX_C or C > 46340:
         return None
     r, nb = ctypes.c_int32(0), ctypes.c_int32(0)
     if _native.lib().sa_xt_band_shape(int(l), int(w), ctypes.byref(r), ctypes.byref(nb)) != 0:

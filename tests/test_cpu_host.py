@@ -30,7 +30,7 @@ def test_library_builds_and_exports_every_declared_symbol():
     for sym in declared:
         assert hasattr(lib, sym), sym
     assert set(declared) == set(_native.EXPORTED_SYMBOLS)
-    assert lib.sa_abi_version() == 4
+    assert lib.sa_abi_version() == 5
     assert lib.sa_debug_enabled() == 0
     assert lib.sa_debug_check() == 0  # default build: no device checks, no device call
 

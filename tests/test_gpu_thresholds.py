@@ -39,6 +39,7 @@ from golden_io import GOLDEN, assert_close, assert_frame_same, assert_same_float
 from oracle import atomic_convert_oracle as co
 from oracle import vaep_oracle as vo
 from oracle import xt_oracle as xo
+from xt_count_checks import ref_counts as _ref_counts, same_counts as _same_counts
 
 gpu = pytest.mark.gpu
 
@@ -158,16 +159,6 @@ def _xt_case(g, l, w):
     d = {c: g[tag + 'in_' + c] for c in ('game_id', 'period_id', 'time_seconds', 'team_id', 'bodypart_id') + XT_COLS}
     d['game_off'], d['home_team_id'] = g[tag + 'game_off'], g[tag + 'home_team_id']
     return tag, d
-
-
-def _sparse_trans(d, l, w):
-    """The successful-move transition counts as (sorted flat s * C + e, count), from the
-    oracle's binning."""
-    t, r = d['type_id'], d['result_id']
-    mv = ((t == 0) | (t == 21) | (t == 1)) & (r == 1)
-    s = xo.flat_indexes(d['start_x'][mv], d['start_y'][mv], l, w)
-    e = xo.flat_indexes(d['end_x'][mv], d['end_y'][mv], l, w)
-    return np.unique(s.astype(np.int64) * (l * w) + e, return_counts=True)
 
 
 @pytest.mark.parametrize('l,w', tc.GOLDEN_GRIDS)
@@ -332,34 +323,6 @@ def test_dribble_thresholds_device_frame(sa):
 # ------------------------------------------------------------------------------- B. binning
 def _batch(sa, d):
     return sa['batch'].ActionBatch.from_columns(d)
-
-
-def _ref_counts(d, l, w):
-    """The oracle's counts with the C x C transition counts as their non-zero entries (up to 1024
-    cells straight from xt_oracle.counts; above, from its binning without the dense table)."""
-    t, r = d['type_id'], d['result_id']
-    out = {}
-    for name, m in (('shot', t == 11), ('goal', (t == 11) & (r == 1)), ('move', (t == 0) | (t == 21) | (t == 1))):
-        out[name] = xo.count(d['start_x'][m], d['start_y'][m], l, w).astype(np.int64).reshape(-1)
-    out['trans'] = _sparse_trans(d, l, w)
-    if l * w <= 1024:
-        cnt = xo.counts(d, l, w)
-        for name in ('shot', 'goal', 'move'):
-            np.testing.assert_array_equal(cnt[name].reshape(-1), out[name])
-        nz = np.flatnonzero(cnt['trans'])
-        np.testing.assert_array_equal(nz, out['trans'][0])
-        np.testing.assert_array_equal(cnt['trans'].reshape(-1)[nz], out['trans'][1])
-    return out
-
-
-def _same_counts(sa, acc, ref, what):
-    torch = sa['torch']
-    for name in ('shot', 'goal', 'move'):
-        np.testing.assert_array_equal(getattr(acc, name).cpu().numpy(), ref[name], err_msg=f'{what} {name}')
-    nz = torch.nonzero(acc.trans).reshape(-1)
-    np.testing.assert_array_equal(nz.cpu().numpy(), ref['trans'][0], err_msg=f'{what} transition cells')
-    np.testing.assert_array_equal(acc.trans[nz].cpu().numpy(), ref['trans'][1], err_msg=f'{what} transitions')
-    assert int(acc.err.item()) == 0, what   # every coordinate is finite: the reference does not raise
 
 
 def _same_rate(got, ref, what):
