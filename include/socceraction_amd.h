@@ -831,6 +831,61 @@ int sa_auc_keys(const uint8_t* y, const void* p, int32_t f32, int64_t n, int32_t
 int sa_auc_count(const uint8_t* y, const void* p, int32_t f32, int64_t n, const void* sorted_keys,
                  int64_t m, int32_t minority, uint64_t* u2, void* stream);
 
+/* ---- filtered top-k of a column -------------------------------------------------- */
+/* The first k rows of one column values [n] (f32 != 0: float, else double) in rank order, as the
+ * last cell of the reference's public-notebooks/4-compute-vaep-values-and-top-players.ipynb takes
+ * them with sort_values(...)[mask].head(k):
+ *   - a row is eligible if its byte of keep [n] is non-zero (keep == NULL: every row) and its
+ *     value is not NaN (any payload, either sign); NaN rows are never selected;
+ *   - eligible rows are ranked by value, descending for largest != 0 and ascending otherwise,
+ *     then by ascending row number; -0.0 and +0.0 are equal, +-inf and subnormals order as numbers;
+ *   - m = min(k, #eligible) rows are selected; m = 0 is a valid, empty result.
+ * The selection is a function of the (row, value, keep) set only: every count below is an
+ * integer, so two runs, any grid and any chunking select the same rows.  1 <= k <= SA_TOP_MAX_K,
+ * 0 <= n < 2^31; n = 0 launches nothing.  Columns whose pointers are 16-byte (values) and 4-byte
+ * (keep) aligned are read with 16-byte and 4-byte loads per four rows; rows >= n are never read.
+ *
+ * Order key: the unsigned integer of the value's width whose order is the numeric order (the bit
+ * pattern with -0.0 folded onto +0.0; negative: complemented, else the sign bit set), complemented
+ * once more for largest == 0, so the select always looks for the highest keys.  The key is cut
+ * into digits of SA_TOP_DIGIT_BITS bits from the top (the last digit takes what is left):
+ * sa_top_passes(f32) of them, 3 for float and 6 for double.
+ *
+ * state [SA_TOP_STATE_WORDS] uint64 and hist [2^SA_TOP_DIGIT_BITS] uint32 are caller-zeroed
+ * device buffers of one selection.  For pass = 0 .. sa_top_passes - 1, on one stream:
+ *   sa_top_hist ADDS to hist[d] the eligible rows whose higher digits equal the state's prefix and
+ *     whose digit `pass` is d (32-bit counts by LDS atomics; one integer global atomic per
+ *     non-empty bin and workgroup);
+ *   sa_top_pick (one workgroup) scans hist from the top bin, appends the digit of the bin that
+ *     holds the k-th eligible row to the prefix, adds the rows of the bins above it to state[1]
+ *     and clears hist.  With fewer than k eligible rows every one of them is selected.
+ * After the last pick the state holds: [0] the threshold key T, [1] `above`, the rows whose key is
+ * higher than T, [3] the eligible rows, [4] the rows whose key equals T, [5] `take` = how many of
+ * those are selected, [6] m = above + take ([2] and [7] are the remaining rank and the collect's cursor).
+ *   sa_top_tie_count writes chunk_ties[c] = the eligible rows with key T among rows
+ *     [c * SA_TOP_CHUNK_ROWS, (c + 1) * SA_TOP_CHUNK_ROWS), for every chunk c of the column;
+ *   the caller takes the exclusive scan of chunk_ties as int64: chunk_base;
+ *   sa_top_collect writes the selected row numbers to rows [k] int64: rows[0 .. above) the rows
+ *     above T in unspecified order (a cursor), rows[above + q] the q-th lowest-numbered row with
+ *     key T for q < take (chunk_base plus an ordered rank inside the workgroup).  rows[m ..] is
+ *     not written.  The caller sorts the m rows into rank order.
+ * The grids of the three row kernels are capped at SA_TOP_WG_PER_CU workgroups per compute unit; a
+ * workgroup takes SA_TOP_CHUNK_ROWS contiguous rows per loop step.  Nothing synchronises: the
+ * caller reads the state once, after the collect. */
+#define SA_TOP_DIGIT_BITS 11
+#define SA_TOP_CHUNK_ROWS 4096
+#define SA_TOP_WG_PER_CU 8
+#define SA_TOP_MAX_K 65536
+#define SA_TOP_STATE_WORDS 8
+int sa_top_passes(int32_t f32);
+int sa_top_hist(const void* values, int32_t f32, const uint8_t* keep, int64_t n, int32_t largest,
+                int32_t pass, const uint64_t* state, uint32_t* hist, void* stream);
+int sa_top_pick(int32_t f32, int64_t k, int32_t pass, uint64_t* state, uint32_t* hist, void* stream);
+int sa_top_tie_count(const void* values, int32_t f32, const uint8_t* keep, int64_t n,
+                     int32_t largest, const uint64_t* state, int32_t* chunk_ties, void* stream);
+int sa_top_collect(const void* values, int32_t f32, const uint8_t* keep, int64_t n, int32_t largest,
+                   int64_t k, uint64_t* state, const int64_t* chunk_base, int64_t* rows, void* stream);
+
 /* ---- boosted-tree training ------------------------------------------------------
  * Reproducible histogram gradient boosting (binary logistic loss, depth-limited trees, xgboost's
  * `hist` rules) on the device feature blocks: VAEP.fit's learner='device' (reference

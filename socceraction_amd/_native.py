@@ -47,6 +47,9 @@ SA_METRIC_CHUNK_ROWS = 4096
 SA_METRIC_WG_PER_CU = 8  # the score kernels' grid cap in workgroups per compute unit
 SA_METRIC_ERR_NAN, SA_METRIC_ERR_RANGE, SA_METRIC_ERR_LABEL = 1, 2, 4
 SA_AUC_LDS_SAMPLE = 1024  # sorted minority keys sa_auc_count keeps in LDS
+# filtered top-k (sa_topk.hip): digit width of the radix select, rows per chunk of the tie counts,
+# the row kernels' grid cap in workgroups per compute unit, the largest k, words of the state record
+SA_TOP_DIGIT_BITS, SA_TOP_CHUNK_ROWS, SA_TOP_WG_PER_CU, SA_TOP_MAX_K, SA_TOP_STATE_WORDS = 11, 4096, 8, 65536, 8
 # boosted-tree training (sa_boost.hip; mirrors include/socceraction_amd.h)
 SA_BOOST_MAX_DEPTH, SA_BOOST_MAX_CUTS, SA_BOOST_MISSING_BIN, SA_BOOST_NO_NODE = 6, 254, 255, 255
 SA_BOOST_MAX_LEVEL_NODES, SA_BOOST_FEATURE_GROUP = 32, 4
@@ -276,6 +279,13 @@ _SIGNATURES = {
                                    ctypes.c_int64, _p, _p]),
     'sa_auc_count': (ctypes.c_int, [_p, _p, ctypes.c_int32, ctypes.c_int64, _p, ctypes.c_int64,
                                     ctypes.c_int32, _p, _p]),
+    'sa_top_passes': (ctypes.c_int, [ctypes.c_int32]),
+    'sa_top_hist': (ctypes.c_int, [_p, ctypes.c_int32, _p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _p, _p,
+                                   _p]),
+    'sa_top_pick': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, _p, _p, _p]),
+    'sa_top_tie_count': (ctypes.c_int, [_p, ctypes.c_int32, _p, ctypes.c_int64, ctypes.c_int32, _p, _p, _p]),
+    'sa_top_collect': (ctypes.c_int, [_p, ctypes.c_int32, _p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, _p,
+                                      _p, _p, _p]),
     'sa_boost_bin': (ctypes.c_int, [ctypes.POINTER(SaBlock), ctypes.POINTER(SaBlock), ctypes.c_int32, _p, _p, _p,
                                     _p, ctypes.c_int32, ctypes.c_int64, _p, ctypes.c_int64, _p]),
     'sa_boost_grad': (ctypes.c_int, [_p, _p, _p, ctypes.c_int64, _p, ctypes.c_float, ctypes.c_int32, _p,

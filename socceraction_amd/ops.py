@@ -1298,6 +1298,74 @@ def binary_metrics(y: torch.Tensor, p: torch.Tensor, acc: Optional[BinaryMetrics
     return acc
 
 
+# ------------------------------------------------------------------------------- filtered top-k
+def top_rows(values: torch.Tensor, k: int, keep: Optional[torch.Tensor] = None,
+             largest: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The first ``k`` rows of ``pd.Series(values)[keep].dropna().sort_values(ascending=not
+    largest, kind='stable')`` as device tensors ``(rows int64 [m], vals [m])``, ``m = min(k,
+    #eligible)``: a row is eligible if ``keep`` (uint8 / bool, same length; None: every row) is
+    set and its value is not NaN; equal values (``-0.0 == +0.0``) come in ascending row order;
+    ``vals`` are the stored bits of those rows.  ``values``: a 1-D float32 / float64 device
+    tensor of fewer than 2**31 rows, of any alignment; ``1 <= k <= SA_TOP_MAX_K``.
+
+    A radix select finds the k-th order key (``sa_top_hist`` / ``sa_top_pick`` per digit, chained
+    on the stream), ``sa_top_tie_count`` / ``sa_top_collect`` write the m selected rows -- of the
+    rows equal to the k-th value the lowest-numbered ones -- and the m rows are put in rank order
+    here: rows ascending, then a stable sort by key.  One host read (the state record, for m).
+    The result depends on the (row, value, keep) set only."""
+    if values.dtype not in (torch.float32, torch.float64):
+        raise TypeError('values must be float32 or float64')
+    if values.dim() != 1 or not values.is_cuda:
+        raise ValueError('values must be a 1-D device tensor')
+    k = int(k)
+    if not 1 <= k <= _native.SA_TOP_MAX_K:
+        raise ValueError(f'k must be in [1, {_native.SA_TOP_MAX_K}]')
+    n = int(values.numel())
+    if n >= 2 ** 31:
+        raise ValueError('top_rows takes fewer than 2**31 rows')
+    if keep is not None:
+        if keep.dtype == torch.bool:
+            keep = keep.view(torch.uint8)
+        if keep.dtype != torch.uint8:
+            raise TypeError('keep must be uint8 or bool')
+        if keep.dim() != 1 or keep.numel() != n or keep.device != values.device:
+            raise ValueError('keep holds one byte per value, on the values\' device')
+        keep = keep.contiguous()
+    values = values.contiguous()
+    dev = values.device
+    if n == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev), values[:0]
+    f32 = int(values.dtype == torch.float32)
+    # one zeroed buffer: the state record, then the digit histogram (uint32 counts)
+    buf = torch.zeros(_native.SA_TOP_STATE_WORDS + (1 << _native.SA_TOP_DIGIT_BITS) // 2, dtype=torch.int64,
+                      device=dev)
+    state, hist = buf[:_native.SA_TOP_STATE_WORDS], buf[_native.SA_TOP_STATE_WORDS:]
+    n_chunks = (n + _native.SA_TOP_CHUNK_ROWS - 1) // _native.SA_TOP_CHUNK_ROWS
+    chunk_ties = torch.empty(n_chunks, dtype=torch.int32, device=dev)
+    rows = torch.empty(k, dtype=torch.int64, device=dev)
+    lib, st = _native.lib(), stream_handle()
+    for p in range(lib.sa_top_passes(f32)):
+        _native.check(lib.sa_top_hist(_ptr(values), f32, _ptr(keep), n, int(largest), p, _ptr(state), _ptr(hist), st))
+        _native.check(lib.sa_top_pick(f32, k, p, _ptr(state), _ptr(hist), st))
+    _native.check(lib.sa_top_tie_count(_ptr(values), f32, _ptr(keep), n, int(largest), _ptr(state),
+                                       _ptr(chunk_ties), st))
+    chunk_base = torch.cumsum(chunk_ties, 0, dtype=torch.int64) - chunk_ties
+    _native.check(lib.sa_top_collect(_ptr(values), f32, _ptr(keep), n, int(largest), k, _ptr(state),
+                                     _ptr(chunk_base), _ptr(rows), st))
+    m = int(state[6].item())  # above + take
+    rows = torch.sort(rows[:m]).values
+    vals = values[rows]
+    # rank order: the signed integer whose order is the values' (-0.0 folded onto +0.0),
+    # complemented for largest; the stable sort keeps equal values in ascending row order
+    it = torch.int32 if f32 else torch.int64
+    lo, hi = torch.iinfo(it).min, torch.iinfo(it).max
+    b = vals.view(it)
+    b = torch.where(b == lo, torch.zeros_like(b), b)
+    s = b ^ ((b >> (31 if f32 else 63)) & hi)
+    order = torch.sort(~s if largest else s, stable=True).indices
+    return rows[order], vals[order]
+
+
 def goalscore_into(batch: ActionBatch, out: FeatureBlocks) -> None:
     """Launch only the goalscore scan into the plan's goalscore columns."""
     from ._native import XFN

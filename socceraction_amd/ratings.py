@@ -132,6 +132,94 @@ def group_sums(actions: pd.DataFrame, values, by: By = 'player_id', groups=None,
     return table(acc, keys, names)
 
 
+def top_rows_host(values: np.ndarray, k: int, keep: Optional[np.ndarray] = None,
+                  largest: bool = True) -> np.ndarray:
+    """``ops.top_rows``' row numbers in numpy, by its definition: the eligible rows (kept, not
+    NaN) ordered by value -- ``-0.0 == +0.0`` -- then by row number, the first ``k`` of them."""
+    values = np.asarray(values)
+    k = int(k)
+    if not 1 <= k <= ops._native.SA_TOP_MAX_K:
+        raise ValueError(f'k must be in [1, {ops._native.SA_TOP_MAX_K}]')
+    ok = ~np.isnan(values)
+    if keep is not None:
+        ok &= np.asarray(keep, bool)
+    rows = np.flatnonzero(ok)
+    v = values[rows] + 0.0  # -0.0 + 0.0 = +0.0: the zeros tie
+    order = np.lexsort((rows, -v if largest else v))
+    return rows[order[:k]].astype(np.int64)
+
+
+def mask_bytes(where, n: int, index=None) -> Optional[np.ndarray]:
+    """``where`` (None, a boolean Series, array or tensor: one entry per action) as uint8 [n]
+    host bytes.  A Series is taken by position; its index must be the actions'."""
+    if where is None:
+        return None
+    if isinstance(where, torch.Tensor):
+        where = where.cpu().numpy()
+    if isinstance(where, pd.Series):
+        if index is not None and not where.index.equals(index):
+            raise ValueError('`where` must carry the actions\' index')
+        where = where.to_numpy()
+    where = np.asarray(where)
+    if where.shape != (n,):
+        raise ValueError('`where` must hold one entry per action')
+    if where.dtype != np.bool_:
+        where = where != 0
+    return np.ascontiguousarray(where).view(np.uint8)
+
+
+def mask_tensor(where, n: int, dev, index=None) -> Optional[torch.Tensor]:
+    """``where`` as a uint8 [n] tensor on ``dev``: a device tensor stays where it is, anything
+    else is uploaded at one byte per row."""
+    if isinstance(where, torch.Tensor) and where.is_cuda:
+        if where.dim() != 1 or where.numel() != n:
+            raise ValueError('`where` must hold one entry per action')
+        return where if where.dtype in (torch.bool, torch.uint8) else (where != 0)
+    m = mask_bytes(where, n, index)
+    return None if m is None else torch.from_numpy(m).to(dev)
+
+
+def top_actions(actions: pd.DataFrame, values, k: int = 10, column: Optional[str] = None, where=None,
+                largest: bool = True) -> pd.DataFrame:
+    """The last cell of the reference's notebook 4: ``pd.concat([actions, values],
+    axis=1).loc[where].dropna(subset=[column]).sort_values(column, ascending=not largest,
+    kind='stable').head(k)`` -- the ``k`` most (``largest=False``: least) valuable actions of a
+    selection, in rank order, ``actions``' index kept so that ``A.loc[i - 3:i + 1]`` shows an
+    action with its neighbours.
+
+    ``values``: one row per action (a DataFrame, a Series or a mapping, as :func:`group_sums`
+    takes); ``column``: the value column to rank by (default: the last).  ``where``: a boolean
+    mask per action (Series, array or device tensor; None: every action).  NaN values are never
+    selected; equal values come in row order.  With a ROCm device the column and one mask byte
+    per row are uploaded and selected by ``ops.top_rows``, and only the row numbers come back;
+    without one the same definition runs in numpy (:func:`top_rows_host`)."""
+    if isinstance(values, pd.Series):
+        values = values.to_frame(values.name if values.name is not None else 'value')
+    if not isinstance(values, pd.DataFrame):
+        values = pd.DataFrame(values)
+    n = len(actions)
+    if values.shape[1] == 0:
+        raise ValueError('no value column to rank by')
+    if len(values) != n:
+        raise ValueError('values must hold one row per action')
+    column = values.columns[-1] if column is None else column
+    if column not in values.columns:
+        raise ValueError(f'no value column {column!r}')
+    col = values[column].to_numpy()
+    col = np.ascontiguousarray(col, np.float32 if col.dtype == np.float32 else np.float64)
+    if n == 0 or not torch.cuda.is_available():
+        rows = top_rows_host(col, k, mask_bytes(where, n, actions.index), largest)
+    else:
+        from .batch import device
+        dev = device()
+        rows = ops.top_rows(torch.from_numpy(col).to(dev), k, mask_tensor(where, n, dev, actions.index),
+                            largest)[0].cpu().numpy()
+    out = actions.iloc[rows].copy()
+    for c in values.columns:
+        out[c] = values[c].to_numpy()[rows]
+    return out
+
+
 def per_90(ratings: pd.DataFrame, minutes_played: pd.DataFrame, min_minutes: float = 180,
            by: By = 'player_id') -> pd.DataFrame:
     """The notebook's normalisation, on the host: merge the minutes played (summed per ``by``),

@@ -572,6 +572,35 @@ class VAEP:
                                  scale_exp=(2, 2, 2), dev=v.device)
         return ratings.table(acc, keys, names)
 
+    def top_actions(self, games: pd.DataFrame, actions: pd.DataFrame, k: int = 10,
+                    column: str = 'vaep_value', where=None, largest: bool = True) -> pd.DataFrame:
+        """The most valuable actions of a selection, the last cell of the reference's notebook 4:
+        ``ratings.top_actions(actions, self.rate_batch(games, actions), k, column, where,
+        largest)`` -- the ``k`` rows of ``actions`` with the highest (``largest=False``: lowest)
+        ``column`` among those ``where`` (a boolean mask per action; None: all) holds, in rank
+        order with ``actions``' index, plus ``offensive_value``, ``defensive_value`` and
+        ``vaep_value`` -- but without the copy back of every value: the ``[3, ld]`` tensor of
+        :meth:`rate_batch`'s path stays in HBM, ``ops.top_rows`` selects on the chosen row (the
+        mask is uploaded at one byte per action), and only the selected rows' three values
+        leave the device."""
+        from .. import ratings
+        if not self.__models:
+            raise NotFittedError()
+        names = ['offensive_value', 'defensive_value', 'vaep_value']
+        if column not in names:
+            raise ValueError(f'column must be one of {names}')
+        n = len(actions)
+        if n == 0:
+            return ratings.top_actions(actions, {c: np.zeros(0) for c in names}, k, column, where, largest)
+        v = self._values_batch(games, actions)
+        keep = ratings.mask_tensor(where, n, v.device, actions.index)
+        rows, _ = ops.top_rows(v[names.index(column), :n], k, keep, largest)
+        sel = v[:, rows].cpu().numpy()
+        out = actions.iloc[rows.cpu().numpy()].copy()
+        for i, c in enumerate(names):
+            out[c] = sel[i]
+        return out
+
     def score(self, X: pd.DataFrame, y: pd.DataFrame) -> Dict[str, Dict[str, float]]:
         """Brier score and AUROC per label (reference vaep/base.py:335-366)."""
         if not self.__models:

@@ -384,6 +384,28 @@ class ExpectedThreat:
         acc = ratings.sum_device(codes, [out], len(keys), scale_exp=(1,), dev=out.device)
         return ratings.table(acc, keys, ['xT_value'])
 
+    def top_actions(self, actions: pd.DataFrame, k: int = 10, use_interpolation: bool = False,
+                    where=None, largest: bool = True) -> pd.DataFrame:
+        """The moves that gained the most threat: ``ratings.top_actions(actions,
+        pd.Series(self.rate(actions, use_interpolation), name='xT_value'), k, where=where,
+        largest=largest)`` -- the ``k`` rows of ``actions`` with the highest (``largest=False``:
+        lowest) xT value among those ``where`` (a boolean mask per action; None: all) holds, in
+        rank order with ``actions``' index, plus ``xT_value`` -- selected on the device
+        (``ops.top_rows``): only the selected rows' values are copied back.  The NaN of actions
+        that are not successful moves is never selected."""
+        from . import ratings
+        if not np.any(self.xT):
+            raise NotFittedError()
+        n = len(actions)
+        if n == 0:
+            return ratings.top_actions(actions, {'xT_value': np.zeros(0)}, k, where=where, largest=largest)
+        out = self._rate_device(actions, use_interpolation)
+        keep = ratings.mask_tensor(where, n, out.device, actions.index)
+        rows, vals = ops.top_rows(out[:n], k, keep, largest)
+        res = actions.iloc[rows.cpu().numpy()].copy()
+        res['xT_value'] = vals.cpu().numpy()
+        return res
+
     def save_model(self, filepath: str, overwrite: bool = True) -> None:
         """Save the xT surface as JSON (reference xthreat.py:467-504)."""
         if not np.any(self.xT):
