@@ -185,6 +185,9 @@ class ActionBatch:
             elif isinstance(home_team_id, pd.Series):  # one vectorised lookup (KeyError if absent)
                 gids = df['game_id'].to_numpy()[seg_off[:-1]]
                 homes = list(home_team_id.loc[gids]) if len(gids) else []
+                if len(homes) != len(gids):  # .loc returns every match of a repeated label
+                    repeated = home_team_id.index[home_team_id.index.duplicated()]
+                    raise ValueError(f'game_id {repeated[0]} occurs more than once in games')
             elif isinstance(home_team_id, dict):
                 gids = df['game_id'].to_numpy()[seg_off[:-1]]
                 homes = [home_team_id[g] for g in gids]

@@ -1894,7 +1894,7 @@ static int check_actions(const sa_actions* a, bool allow_explicit) {
     return fail(SA_EINVAL, "explicit-frame mode requires exactly one segment");
   if (a->n > 0 && (a->n_segments < 1 || !a->seg_off))
     return fail(SA_EINVAL, "n_segments must be >= 1 with seg_off");
-  for (int f = 0; f < a->n_frames; ++f) {
+  for (int f = 0; f < a->n_frames && a->n > 0; ++f) {  // an empty batch has no columns to check
     const sa_frame& F = a->frames[f];
     if (!F.type_id || !F.team || !F.bodypart_id || !F.period_id || !F.time_seconds || !F.c0 ||
         !F.c1 || !F.c2 || !F.c3 || (!a->atomic && !F.result_id))

@@ -78,7 +78,8 @@ def value_frames(model, games: pd.DataFrame, actions: pd.DataFrame,
     game_id -> home_team_id) for a VAEP / AtomicVAEP ``model`` whose transformers are all
     known ones.  ``values`` is None without probabilities (float32 or float64; values take
     their dtype, the reference's rule); ``labels=False``: features only (labels None; the
-    pipelined ``compute_features_batch``)."""
+    pipelined ``compute_features_batch``).  Every contiguous run of one ``game_id`` is a segment
+    of its own, also when the same id heads a second run further down."""
     t_call = time.perf_counter()
     known, unknown = model._split_xfns()
     if unknown:
@@ -94,6 +95,9 @@ def value_frames(model, games: pd.DataFrame, actions: pd.DataFrame,
     missing = ~pd.Index(seg_gid).isin(home_map.index)
     if missing.any():  # as the per-game lookup of compute_features_batch
         raise KeyError(seg_gid[np.flatnonzero(missing)[0]])
+    repeated = home_map.index.duplicated()
+    if repeated.any():  # reindex would refuse it without a name; .loc would return two homes
+        raise ValueError(f'game_id {home_map.index[repeated][0]} occurs more than once in games')
     homes = home_map.reindex(seg_gid).to_numpy()
     lab = model._lab
     names = {lab.scores: 'scores', lab.concedes: 'concedes', lab.goal_from_shot: 'goal_from_shot'}
@@ -141,50 +145,54 @@ def value_frames(model, games: pd.DataFrame, actions: pd.DataFrame,
     if timeline is not None:
         timeline.append({'setup_ms': round((t_start - t_call) * 1e3, 2)})
     evs = []
-    for k, (s0, s1) in enumerate(cuts):
-        r0, r1 = int(seg_off[s0]), int(seg_off[s1])
-        m = r1 - r0
-        slot = slots[k % len(slots)]
-        th0 = time.perf_counter()
-        # 1. host encode + H2D of this chunk (overlaps the copy out of the previous chunk)
-        ab = ActionBatch.from_frame(actions.iloc[r0:r1], atomic=atomic, home_team_id=list(homes[s0:s1]),
-                                    segments='game', dev=dev, pinned=True)
-        th1 = time.perf_counter()
-        # 2. kernels, once the slot's previous copy is done
-        if slot.used:
-            main.wait_event(slot.done)
-        fb = ops.FeatureBlocks(plan, m, slot.R, slot.R, slot.fb.bool_block, slot.fb.f64_block,
-                               slot.fb.i64_block)
-        ops.features_into(ab.struct(), fb)
-        lb = ops.LabelBlocks(m, slot.lab[0], slot.lab[1], slot.lab[2])
-        if labels and vdt is not None:
-            tps = torch.from_numpy(ps[r0:r1]).to(dev, non_blocking=True)
-            tpc = torch.from_numpy(pc[r0:r1]).to(dev, non_blocking=True)
-            ops.labels_formula(ab, tps, tpc, labels_out=lb, values_out=slot.val)
-        elif labels:
-            ops.labels(ab, out=lb)
-        # 3. pitched copies into the frame's host blocks, on the copy stream
-        ev = torch.cuda.Event()
-        ev.record(main)
-        copy.wait_event(ev)
-        if timeline is not None:  # diagnostics: the copy's device-side start / end
-            ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ea.record(copy)
-        d2h(hb, slot.fb.bool_block[0], r0, m, plan.n_bool)
-        d2h(hf, slot.fb.f64_block[0], r0, m, plan.n_f64)
-        d2h(hi, slot.fb.i64_block[0], r0, m, plan.n_i64)
-        if labels:
-            d2h(hl, slot.lab, r0, m, 3)
-        if vdt is not None:
-            d2h(hv, slot.val, r0, m, 3)
-        slot.done.record(copy)
-        if timeline is not None:
-            eb.record(copy)
-            evs.append((k, m, th0 - t_start, th1 - t_start, time.perf_counter() - t_start, ea, eb))
-        slot.used = True
-        slot.keep = (ab, tps, tpc) if vdt is not None else ab  # alive until the slot is reused
-    copy.synchronize()
-    main.synchronize()
+    try:
+        for k, (s0, s1) in enumerate(cuts):
+            r0, r1 = int(seg_off[s0]), int(seg_off[s1])
+            m = r1 - r0
+            slot = slots[k % len(slots)]
+            th0 = time.perf_counter()
+            # 1. host encode + H2D of this chunk (overlaps the copy out of the previous chunk)
+            ab = ActionBatch.from_frame(actions.iloc[r0:r1], atomic=atomic, home_team_id=list(homes[s0:s1]),
+                                        segments='game', dev=dev, pinned=True)
+            th1 = time.perf_counter()
+            # 2. kernels, once the slot's previous copy is done
+            if slot.used:
+                main.wait_event(slot.done)
+            fb = ops.FeatureBlocks(plan, m, slot.R, slot.R, slot.fb.bool_block, slot.fb.f64_block,
+                                   slot.fb.i64_block)
+            ops.features_into(ab.struct(), fb)
+            lb = ops.LabelBlocks(m, slot.lab[0], slot.lab[1], slot.lab[2])
+            if labels and vdt is not None:
+                tps = torch.from_numpy(ps[r0:r1]).to(dev, non_blocking=True)
+                tpc = torch.from_numpy(pc[r0:r1]).to(dev, non_blocking=True)
+                ops.labels_formula(ab, tps, tpc, labels_out=lb, values_out=slot.val)
+            elif labels:
+                ops.labels(ab, out=lb)
+            # 3. pitched copies into the frame's host blocks, on the copy stream
+            ev = torch.cuda.Event()
+            ev.record(main)
+            copy.wait_event(ev)
+            if timeline is not None:  # diagnostics: the copy's device-side start / end
+                ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ea.record(copy)
+            d2h(hb, slot.fb.bool_block[0], r0, m, plan.n_bool)
+            d2h(hf, slot.fb.f64_block[0], r0, m, plan.n_f64)
+            d2h(hi, slot.fb.i64_block[0], r0, m, plan.n_i64)
+            if labels:
+                d2h(hl, slot.lab, r0, m, 3)
+            if vdt is not None:
+                d2h(hv, slot.val, r0, m, 3)
+            slot.done.record(copy)
+            if timeline is not None:
+                eb.record(copy)
+                evs.append((k, m, th0 - t_start, th1 - t_start, time.perf_counter() - t_start, ea, eb))
+            slot.used = True
+            slot.keep = (ab, tps, tpc) if vdt is not None else ab  # alive until the slot is reused
+    finally:
+        # also when a later chunk's validation raises: the copies queued so far read the slots and
+        # write the pinned blocks, neither of which may go back to its allocator while they run
+        copy.synchronize()
+        main.synchronize()
     if timeline is not None and evs:
         e0 = evs[0][5]
         for k, m, a, b, c, ea, eb in evs:  # host ms: encode start / end, launches queued; device ms

@@ -29,7 +29,7 @@ import pandas as pd
 import torch
 
 from . import _native
-from .batch import ActionBatch, stream_handle
+from .batch import ActionBatch, segment_offsets, stream_handle
 
 try:
     import pyarrow as pa
@@ -279,6 +279,11 @@ def read_store(path: str, key: str) -> pd.DataFrame:
 # ------------------------------------------------------------------ batched writers
 def _games_batch(model, games: pd.DataFrame, actions: pd.DataFrame):
     home_of = games.set_index('game_id')['home_team_id']
+    gid = actions['game_id'].to_numpy()
+    heads = gid[segment_offsets(gid)[:-1]] if len(gid) else gid[:0]
+    again = pd.Index(heads).duplicated()
+    if again.any():  # one key per game: a second run would overwrite the first one's rows
+        raise ValueError(f'game_id {heads[again][0]} heads more than one run of rows in actions')
     ab = ActionBatch.from_frame(actions, atomic=model._atomic, home_team_id=home_of,
                                 segments='game')
     off = ab.cols['seg_off'].cpu().numpy()
