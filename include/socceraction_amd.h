@@ -1042,6 +1042,58 @@ int sa_boost_hist_unpack(const int64_t* payload, const int32_t* pairs, int32_t n
                          int32_t n_nodes, int32_t n_features, int64_t* hist, sa_boost_node* tree,
                          void* stream);
 
+/* ---- logistic regression on the feature blocks ------------------------------------
+ * The first model of the expected-goals notebook (EXTRA-build-expected-goals-model.ipynb:
+ * `LogisticRegression().fit(X, y)`), fitted by Newton's method: one sa_logit_moments launch per
+ * iterate gives the gradient, the Hessian and the loss as order-independent integer sums.
+ * Source: the blocks as sa_select_rows takes them (f_blk / i_blk tiled [tiles, C, R], R a multiple
+ * of 16; f32 = 0: float64 + int64 elements, f32 = 1: both float32; bits [n_bool][words] int64).
+ * slots[d] (HOST, model order): 0 << 24 | bitmap row, 1 << 24 | f_blk column or 2 << 24 | i_blk
+ * column; d <= SA_LOGIT_MAX_COLS.  beta (device): d + 1 float64 coefficients, the intercept last.
+ * A row's z = beta[d] + sum_j beta[j] * x_j, float64, in slot order, every product and every add
+ * rounded on its own; p = 1 / (1 + exp(-z)).
+ *
+ * sa_logit_moments: over the rows j < n with row_mask[j] != 0 (row_mask NULL: all), y (uint8,
+ *   non-zero = class 1), with D = d + 1 design columns (the last one the constant 1), r = p - y,
+ *   w = p * (1 - p) and loss = max(z, 0) + log1p(exp(-|z|)) - y * z, the T = D (D + 1) / 2 + D + 1
+ *   sums: the upper triangle of (w * x_j) * x_k, row-major (j <= k: item j * D - j * (j - 1) / 2 +
+ *   k - j), then the D terms r * x_k, then the loss.  limbs [T][3] int64 (OVERWRITTEN): every term
+ *   quantised as sa_group_sums quantises (Q = trunc(v * 2^(95 - E)), three 32-bit limbs carrying
+ *   the sign) with E = col_exp[j] + col_exp[k] - 2 for the triangle, col_exp[k] for the r terms and
+ *   loss_exp for the loss, and added as integers: the result does not depend on the row order or
+ *   the grid.  col_exp [d + 1] (HOST): |x_j| < 2^col_exp[j] over the rows that take part, each in
+ *   [SA_LOGIT_EXP_MIN, SA_LOGIT_EXP_MAX]; col_exp[d] >= 1.  err (one uint32, OVERWRITTEN): the
+ *   SA_LOGIT_ERR_* bits; a row with a NaN or infinite feature adds nothing to any sum, a term at or
+ *   beyond 2^E adds nothing to its own.  rowbuf (device scratch, 4 * n float64, OVERWRITTEN): the
+ *   rows' w, r, loss and takes-part flag, written by a first kernel (one thread per row) and read
+ *   by the second.  grid_x = 0: the library's grid (SA_LOGIT_WG_PER_CU workgroups per compute
+ *   unit, divided by the item blocks that hold an item); > 0: that many workgroups along the rows (capped at the row
+ *   tiles) -- any value gives the same limbs.  n < 2^30; block / bitmap column numbers < 16384.
+ *   Launch shape of the second kernel: the items are the cells of a (D + 2) x D table (row j < D:
+ *   the triangle's k >= j; row D: the r terms; row D + 1: the loss) cut into blocks of
+ *   SA_LOGIT_BLOCK_J x SA_LOGIT_BLOCK_K cells; grid (grid_x, ceil((D + 2) / SA_LOGIT_BLOCK_J) *
+ *   ceil(D / SA_LOGIT_BLOCK_K)), 256 threads; a workgroup stages its block's columns of
+ *   SA_LOGIT_TILE_ROWS rows at a time in LDS (41 KiB whatever the model's width) and ends with one
+ *   integer atomic per non-zero limb.
+ * sa_logit_predict: out[j] = p of row j < n, float32 (out_f32 != 0) or float64. */
+#define SA_LOGIT_MAX_COLS 640
+#define SA_LOGIT_TILE_ROWS 64
+#define SA_LOGIT_BLOCK_J 16
+#define SA_LOGIT_BLOCK_K 64
+#define SA_LOGIT_WG_PER_CU 4
+#define SA_LOGIT_EXP_MIN (-440)
+#define SA_LOGIT_EXP_MAX 440
+#define SA_LOGIT_ERR_NAN 1
+#define SA_LOGIT_ERR_NONFINITE 2
+#define SA_LOGIT_ERR_RANGE 4
+int sa_logit_moments(const sa_block* f_blk, const sa_block* i_blk, int32_t f32, const int64_t* bits,
+                     int64_t words, int32_t n_bool, const int32_t* slots, int32_t d, const double* beta,
+                     const int32_t* col_exp, int32_t loss_exp, const uint8_t* y, const uint8_t* row_mask,
+                     int64_t n, int32_t grid_x, double* rowbuf, int64_t* limbs, uint32_t* err, void* stream);
+int sa_logit_predict(const sa_block* f_blk, const sa_block* i_blk, int32_t f32, const int64_t* bits,
+                     int64_t words, int32_t n_bool, const int32_t* slots, int32_t d, const double* beta,
+                     int64_t n, int32_t out_f32, void* out, void* stream);
+
 /* ---- runtime ------------------------------------------------------------------ */
 int sa_abi_version(void);
 const char* sa_last_error(void);

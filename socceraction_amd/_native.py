@@ -57,6 +57,10 @@ SA_BOOST_MAX_SHIFT, SA_BOOST_SALT_ROWS, SA_BOOST_SALT_COLS = 20, 0x726F77, 0x636
 SA_BOOST_BIN_TILE, SA_BOOST_BITS_TILE, SA_BOOST_BINS_TILE = 1024, 2048, 1024
 # sa_boost_hist_bins' grid: gx = max(MIN_GRID_X, WG_PER_CU * CUs / groups); sa_boost_hist_bits' LDS sums per pass
 SA_BOOST_BINS_WG_PER_CU, SA_BOOST_BINS_MIN_GRID_X, SA_BOOST_BITS_ACC_BYTES = 4, 8, 131072
+# logistic regression (sa_linear.hip; mirrors include/socceraction_amd.h)
+SA_LOGIT_MAX_COLS, SA_LOGIT_TILE_ROWS, SA_LOGIT_BLOCK_J, SA_LOGIT_BLOCK_K, SA_LOGIT_WG_PER_CU = 640, 64, 16, 64, 4
+SA_LOGIT_EXP_MIN, SA_LOGIT_EXP_MAX = -440, 440
+SA_LOGIT_ERR_NAN, SA_LOGIT_ERR_NONFINITE, SA_LOGIT_ERR_RANGE = 1, 2, 4
 SA_OK, SA_EINVAL, SA_EHIP, SA_EDATA, SA_ENOMEM = 0, -1, -2, -3, -4
 
 # enum sa_xfn (order matters: mirrors include/socceraction_amd.h)
@@ -308,6 +312,13 @@ _SIGNATURES = {
                                           ctypes.c_int32, _p, _p]),
     'sa_boost_hist_unpack': (ctypes.c_int, [_p, _p, ctypes.c_int32, ctypes.c_int32, _p, ctypes.c_int32,
                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _p, _p, _p]),
+    'sa_logit_moments': (ctypes.c_int, [ctypes.POINTER(SaBlock), ctypes.POINTER(SaBlock), ctypes.c_int32, _p,
+                                        ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                        ctypes.c_int32, _p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, _p, _p,
+                                        ctypes.c_int64, ctypes.c_int32, _p, _p, _p, _p]),
+    'sa_logit_predict': (ctypes.c_int, [ctypes.POINTER(SaBlock), ctypes.POINTER(SaBlock), ctypes.c_int32, _p,
+                                        ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                        ctypes.c_int32, _p, ctypes.c_int64, ctypes.c_int32, _p, _p]),
     'sa_device_alloc': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
     'sa_device_free': (ctypes.c_int, [_p]),
     'sa_copy2d_async': (ctypes.c_int, [_p, ctypes.c_int64, _p, ctypes.c_int64, ctypes.c_int64,

@@ -8,8 +8,12 @@ bitmap-form feature blocks by ``ops.select_rows`` (``sa_select_rows``) into a co
 few per cent the size of the full one, and the device learner (:mod:`socceraction_amd.boost`),
 the tree predictor and the score kernels run on that table.  Only the shots ever cross the link.
 
-The notebook's logistic regression is not offered: its own fit stops at the iteration limit,
-so there is no reference result to hold one to.
+The notebook fits two models on the shot table, and both are offered: its ``XGBClassifier()``
+(``learner='device'``) and its ``LogisticRegression()`` (``learner='logistic'``,
+:mod:`socceraction_amd.linear`).  The notebook's own lbfgs fit of the latter stops at the
+iteration limit, 0.03 - 0.06 in probability away from the optimum, so it is no reference result;
+the optimum itself is one -- the objective is strictly convex -- and the device fit reaches it by
+Newton's method on integer sums, bit-identical from run to run and for any row order.
 """
 from __future__ import annotations
 
@@ -34,6 +38,8 @@ NB_PREV_ACTIONS = 2
 # what XGBClassifier() means there: 100 trees of depth 6 at learning rate 0.3
 TREE_PARAMS = dict(n_estimators=100, max_depth=6, learning_rate=0.3)
 SHOT_TYPES = tuple(i for i, t in enumerate(spadlcfg.actiontypes) if 'shot' in t)
+# what LogisticRegression() means there: C = 1 with an intercept (solved to the optimum here)
+LINEAR_PARAMS = dict(C=1.0, fit_intercept=True, tol=1e-10, max_iter=100)
 SUCCESS = spadlcfg.results.index('success')
 _LEAKS = ('dx_a0', 'dy_a0', 'movement_a0')  # a shot's own movement gives its result away
 
@@ -92,6 +98,27 @@ def get_shots(games: pd.DataFrame, actions: pd.DataFrame, xfns: Optional[Sequenc
     return compact.to_frame(index=pd.Index(rows.cpu().numpy()))
 
 
+class _LinearPredictor:
+    """A fitted linear model behind the tree predictor's ``predict_blocks``: float32 P(class 1)
+    of every row of bitmap-form feature blocks."""
+
+    def __init__(self, model) -> None:
+        self.model = model
+
+    def predict_blocks(self, blocks) -> torch.Tensor:
+        return self.model.predict_blocks(blocks, dtype=torch.float32)
+
+
+def _predictor(model):
+    """The one seam between the two model kinds: an object whose ``predict_blocks(blocks)`` gives
+    float32 probabilities on the device."""
+    from .linear import DeviceLogisticRegression
+    if isinstance(model, DeviceLogisticRegression):
+        return _LinearPredictor(model)
+    from .trees import TreeEnsemble
+    return TreeEnsemble.from_model(model)
+
+
 class ExpectedGoals:
     """An expected-goals model of the notebook's kind, fitted, applied and scored on the device.
 
@@ -111,7 +138,7 @@ class ExpectedGoals:
         self.nb_prev_actions = nb_prev_actions
         self.columns = None if columns is None else [str(c) for c in columns]
         self.model_ = None
-        self._trees = None
+        self._predictor = None
         self.device_eval_: Optional[Dict[str, float]] = None
 
     def _columns(self) -> List[str]:
@@ -121,7 +148,7 @@ class ExpectedGoals:
     def fit_batch(self, games: pd.DataFrame, actions: pd.DataFrame, learner: str = 'device',
                   tree_params: Optional[Dict[str, Any]] = None, val_size: float = 0.0,
                   early_stopping_rounds: Optional[int] = None, eval_metric: str = 'auc',
-                  sample_weight=None) -> 'ExpectedGoals':
+                  sample_weight=None, linear_params: Optional[Dict[str, Any]] = None) -> 'ExpectedGoals':
         """Fit the model on the shots of many games (contiguous per game): one ``ActionBatch``,
         the features as bitmaps plus numeric blocks, the shot rows gathered into a compact table
         (``ops.select_rows``), that table binned on the model's columns and the learner fitted
@@ -133,12 +160,24 @@ class ExpectedGoals:
         the compact table.  ``early_stopping_rounds`` (needs ``val_size > 0``) and
         ``eval_metric``: as in ``VAEP.fit_batch``.  ``sample_weight``: one weight per row of
         ``actions``; the shots' are gathered.  With ``subsample`` a round's row sample is keyed by
-        ``fm(game_id) + action_id`` of the shot."""
-        from . import boost, metrics
-        from .trees import TreeEnsemble
+        ``fm(game_id) + action_id`` of the shot.
+
+        ``learner='logistic'``: the notebook's other model, a
+        :class:`~socceraction_amd.linear.DeviceLogisticRegression` (``linear_params`` over
+        :data:`LINEAR_PARAMS`) on the same compact table and columns, the training shots again a
+        mask when ``val_size`` holds some out.  It has no rounds to stop early and takes no
+        weights: ``early_stopping_rounds``, ``sample_weight`` and ``tree_params`` are a ``ValueError``
+        (``eval_metric`` names what early stopping watches and is not looked at)."""
+        from . import boost
         from .vaep.base import VAEP
+        if learner == 'logistic':
+            if tree_params is not None:
+                raise ValueError('tree_params go with learner=\'device\'')
+            return self._fit_logistic(games, actions, linear_params, val_size, early_stopping_rounds, sample_weight)
         if learner != 'device':
             raise ValueError(f'A {learner} learner is not supported by fit_batch')
+        if linear_params is not None:
+            raise ValueError('linear_params go with learner=\'logistic\'')
         params = boost.check_params({**TREE_PARAMS, **dict(tree_params or {})})  # before any device call
         stop = VAEP._device_stop_params(early_stopping_rounds, eval_metric, val_size > 0)
         weight = sample_weight
@@ -149,6 +188,20 @@ class ExpectedGoals:
             raise ValueError('subsample needs the game_id and action_id columns (they key the row sample)')
         known = _known_xfns(self.xfns)
         columns = self._columns()
+        ab, rows, y, compact, train, val = self._shot_table(games, actions, known, val_size)
+        data = boost.bin_blocks(compact, rows=train, columns=columns)
+        host_rows = rows.cpu().numpy() if (sampled or weight is not None) else None
+        keys = boost.row_keys(actions['game_id'].to_numpy()[host_rows], actions['action_id'].to_numpy()[host_rows],
+                              ab.device) if sampled else None
+        if weight is not None:
+            weight = boost.weights_to_device(weight[host_rows], ab.device)
+        eval_rows = val if stop['early_stopping_rounds'] is not None else None
+        clf = boost.make_classifier(params, **stop).fit_binned(data, y, train, eval_rows, weight, keys)
+        return self._fitted_model(clf, columns, compact, y, val)
+
+    def _shot_table(self, games: pd.DataFrame, actions: pd.DataFrame, known: Sequence[str], val_size: float):
+        """``(batch, shot rows, labels, compact blocks, training rows, held-out rows)``: what either
+        learner is fitted on.  The row lists index the compact table (``None`` without a split)."""
         ab = _game_batch(games, actions)
         rows = shot_rows(ab)
         m = int(rows.numel())
@@ -166,44 +219,61 @@ class ExpectedGoals:
             cut = math.floor(m * (1 - val_size))
             train = torch.from_numpy(np.sort(idx[:cut])).to(ab.device)
             val = torch.from_numpy(np.sort(idx[cut + 1:])).to(ab.device)
-        data = boost.bin_blocks(compact, rows=train, columns=columns)
-        host_rows = rows.cpu().numpy() if (sampled or weight is not None) else None
-        keys = boost.row_keys(actions['game_id'].to_numpy()[host_rows], actions['action_id'].to_numpy()[host_rows],
-                              ab.device) if sampled else None
-        if weight is not None:
-            weight = boost.weights_to_device(weight[host_rows], ab.device)
-        eval_rows = val if stop['early_stopping_rounds'] is not None else None
-        clf = boost.make_classifier(params, **stop).fit_binned(data, y, train, eval_rows, weight, keys)
+        return ab, rows, y, compact, train, val
+
+    def _fitted_model(self, model, columns: Sequence[str], compact, y, val) -> 'ExpectedGoals':
+        """Keep ``model``; with held-out shots, score it on them once into ``device_eval_``."""
+        from . import metrics
         self.device_eval_ = None
         if val is not None and val.numel():
-            p = TreeEnsemble.from_model(clf).predict_blocks(compact)
+            p = _predictor(model).predict_blocks(compact)
             self.device_eval_ = metrics.binary_scores(y[val].contiguous(), p[val].contiguous())
-        self.model_ = clf
+        self.model_ = model
         self.feature_names_in_ = list(columns)
-        self._trees = None
+        self._predictor = None
         return self
+
+    def _fit_logistic(self, games, actions, linear_params, val_size, early_stopping_rounds, sample_weight):
+        from . import linear
+        if early_stopping_rounds is not None:
+            raise ValueError('early_stopping_rounds needs a learner that trains in rounds: the logistic learner '
+                             'solves to the optimum')
+        if sample_weight is not None:
+            raise ValueError('the logistic learner takes no sample weights')
+        params = {**LINEAR_PARAMS, **dict(linear_params or {})}
+        unknown = sorted(set(params) - set(LINEAR_PARAMS))
+        if unknown:
+            raise ValueError(f'unknown linear_params: {unknown}')
+        linear.check_params(params['C'], params['tol'], params['max_iter'])  # before any device call
+        known = _known_xfns(self.xfns)
+        columns = self._columns()
+        _, _, y, compact, train, val = self._shot_table(games, actions, known, val_size)
+        model = linear.DeviceLogisticRegression(**params).fit_blocks(compact, y, rows=train, columns=columns)
+        return self._fitted_model(model, columns, compact, y, val)
 
     def _fitted(self):
         if self.model_ is None:
             raise NotFittedError()
-        if self._trees is None:
-            from .trees import TreeEnsemble
-            self._trees = TreeEnsemble.from_model(self.model_)
-        return self._trees
+        if self._predictor is None:
+            self._predictor = _predictor(self.model_)
+        return self._predictor
 
     def to_xgboost_json(self) -> dict:
-        """The fitted classifier as an xgboost-1.6-shaped JSON model."""
+        """The fitted classifier as an xgboost-1.6-shaped JSON model (the tree learner's only)."""
         self._fitted()
+        if not hasattr(self.model_, 'to_xgboost_json'):
+            raise ValueError('a logistic model has no xgboost form: its parameters are model_.coef_ and '
+                             'model_.intercept_')
         return self.model_.to_xgboost_json()
 
     # ---------------------------------------------------------------- rating
     def _rate(self, ab: ActionBatch):
         """``(shot rows, their labels, their xG)``, all on the device."""
-        trees = self._fitted()
+        predictor = self._fitted()
         rows, compact = _shot_blocks(ab, _known_xfns(self.xfns), self.nb_prev_actions)
         if rows.numel() == 0:
             return rows, shot_labels(ab, rows), torch.zeros(0, dtype=torch.float32, device=ab.device)
-        return rows, shot_labels(ab, rows), trees.predict_blocks(compact)
+        return rows, shot_labels(ab, rows), predictor.predict_blocks(compact)
 
     @staticmethod
     def _frame(actions: pd.DataFrame, rows: torch.Tensor, p: torch.Tensor) -> pd.DataFrame:
