@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SA_ABI_VERSION 5
+#define SA_ABI_VERSION 6
 #define SA_MAX_FRAMES 8 /* max frames n_frames == k of explicit-frame mode (windowed mode: any k) */
 #define SA_BOOL_TILE_QUANTUM 1024 /* bool block: rows per tile must be a multiple of this */
 #define SA_NUM_TILE_QUANTUM 128   /* f64 / i64 blocks: rows per tile must be a multiple of this */
@@ -145,34 +145,27 @@ typedef struct sa_block {
 /* ---- VAEP / Atomic-VAEP ------------------------------------------------------
  * Replaces VAEP.compute_features (vaep/base.py:97-116): gamestates + flip + the
  * transformers of `plan`, for every segment of `a` at once.  A block (or its data) may
- * be NULL when the plan writes no column of that dtype. */
+ * be NULL when the plan writes no column of that dtype.
+ * xt_cells ([n] u32, 16-byte aligned, or NULL; xt_l / xt_w are ignored when NULL): the same
+ * pass also writes the xT cell code (sa_xt_cells) of every action for a fit + rate of these
+ * actions on the (xt_l, xt_w) grid -- the VAEP + xT step of one batch (BASELINE cfg2 + cfg4)
+ * reads the coordinates from HBM once.  SPADL windowed mode, xt_l * xt_w <= SA_XT_CELLS_MAX_C. */
 int sa_vaep_features(const sa_actions* a, const sa_feature_plan* plan, const sa_block* bool_out,
-                     const sa_block* f64_out, const sa_block* i64_out, void* stream);
-
-/* sa_vaep_features that also writes, in the same pass, the xT cell code (sa_xt_cells) of every
- * action for a fit + rate of these actions on the (xt_l, xt_w) grid -- the VAEP + xT step of
- * one batch (BASELINE cfg2 + cfg4) reads the coordinates from HBM once.  SPADL windowed mode;
- * xt_cells: [n] u32, 16-byte aligned. */
-int sa_vaep_features_xt(const sa_actions* a, const sa_feature_plan* plan, const sa_block* bool_out,
-                        const sa_block* f64_out, const sa_block* i64_out, int32_t xt_l, int32_t xt_w,
-                        uint32_t* xt_cells, void* stream);
+                     const sa_block* f64_out, const sa_block* i64_out, int32_t xt_l, int32_t xt_w,
+                     uint32_t* xt_cells, void* stream);
 
 /* sa_vaep_features with the bool features written as bitmaps instead of a bool block (the
  * on-device VAEP.rate: the tree kernels read one bit per value, 64 instead of 515 B/action
  * written; windowed mode): bitmap c (plan bool column c, c < n_bool_cols) at bool_bits + c * bits_stride, bit i
  * of byte k = row 8k + i (the Arrow layout of sa_pack_bits), rows >= n clear; bits_stride even
- * and >= 2 * ceil(n / 16) (a multiple of 8 for sa_tree_predict_staged). */
+ * and >= 2 * ceil(n / 16) (a multiple of 8 for sa_tree_predict_staged).
+ * f32 != 0: the numeric blocks in float32 (same tiled layout, 4-B elements: f64_out holds the
+ * plan's f64 columns rounded to nearest, i64_out its i64 columns converted) -- the features of
+ * the on-device VAEP.rate for xgboost learners, which compare float32 values (the DMatrix
+ * conversion), so half the numeric bytes are written and staged.  Needs k <= 3. */
 int sa_vaep_features_bits(const sa_actions* a, const sa_feature_plan* plan, uint8_t* bool_bits,
-                          int64_t bits_stride, int32_t n_bool_cols, const sa_block* f64_out,
-                          const sa_block* i64_out, void* stream);
-
-/* sa_vaep_features_bits with the numeric blocks in float32 (same tiled layout, 4-B elements:
- * f32_out holds the plan's f64 columns rounded to nearest, i32f_out its i64 columns converted):
- * the features of the on-device VAEP.rate for xgboost learners, which compare float32 values
- * (the DMatrix conversion), so half the numeric bytes are written and staged.  k <= 3. */
-int sa_vaep_features_bits_f32(const sa_actions* a, const sa_feature_plan* plan, uint8_t* bool_bits,
-                              int64_t bits_stride, int32_t n_bool_cols, const sa_block* f32_out,
-                              const sa_block* i32f_out, void* stream);
+                          int64_t bits_stride, int32_t n_bool_cols, int32_t f32,
+                          const sa_block* f64_out, const sa_block* i64_out, void* stream);
 
 /* VAEP.rate's features for xgboost learners as CONDITION bitmaps: bitmap rows [0, n_bool_cols)
  * = the bool features (as sa_vaep_features_bits), rows n_bool_cols + c = split condition c of
@@ -202,51 +195,40 @@ int sa_vaep_goalscore(const sa_actions* a, const sa_block* i64_out, int32_t col,
 int sa_vaep_labels(const sa_actions* a, int32_t nr_actions, uint8_t* scores, uint8_t* concedes,
                    uint8_t* goal_from_shot, int64_t ld, void* stream);
 
-/* Replaces formula.value (vaep/formula.py:116-151; atomic/vaep/formula.py:116-141)
- * with float64 probabilities; outputs offensive, defensive, vaep: vectors of length
- * >= round_up(n, 4), 16-byte aligned. */
-int sa_vaep_formula_f64(const sa_actions* a, const double* p_scores, const double* p_concedes,
-                        double* off, double* def, double* val, void* stream);
-/* Same with float32 probabilities (the reference keeps the probability dtype). */
-int sa_vaep_formula_f32(const sa_actions* a, const float* p_scores, const float* p_concedes,
-                        float* off, float* def, float* val, void* stream);
+/* Replaces formula.value (vaep/formula.py:116-151; atomic/vaep/formula.py:116-141).  f32 (0 or
+ * 1) is the element type of the probabilities and of the outputs (the reference keeps the
+ * probability dtype): float64 or float32.  Outputs offensive, defensive, vaep: vectors of
+ * length >= round_up(n, 4), 16-byte aligned. */
+int sa_vaep_formula(const sa_actions* a, int32_t f32, const void* p_scores, const void* p_concedes,
+                    void* off, void* def, void* val, void* stream);
 
 /* compute_labels + formula.value of the same actions in one launch (the tail of a VAEP
- * step: the ids and team codes are read once): exactly sa_vaep_labels then
- * sa_vaep_formula_f64 / _f32 with the same arguments.  Formula outputs need length
- * >= round_up(n, 16) here. */
-int sa_vaep_labels_formula_f64(const sa_actions* a, int32_t nr_actions, uint8_t* scores,
-                               uint8_t* concedes, uint8_t* goal_from_shot, int64_t ld,
-                               const double* p_scores, const double* p_concedes, double* off,
-                               double* def, double* val, void* stream);
-int sa_vaep_labels_formula_f32(const sa_actions* a, int32_t nr_actions, uint8_t* scores,
-                               uint8_t* concedes, uint8_t* goal_from_shot, int64_t ld,
-                               const float* p_scores, const float* p_concedes, float* off,
-                               float* def, float* val, void* stream);
+ * step: the ids and team codes are read once): exactly sa_vaep_labels then sa_vaep_formula
+ * with the same arguments.  Formula outputs need length >= round_up(n, 16) here. */
+int sa_vaep_labels_formula(const sa_actions* a, int32_t nr_actions, uint8_t* scores,
+                           uint8_t* concedes, uint8_t* goal_from_shot, int64_t ld, int32_t f32,
+                           const void* p_scores, const void* p_concedes, void* off, void* def,
+                           void* val, void* stream);
 
 /* The batch valuation step in one call -- the notebook loop compute_features +
  * compute_labels + formula.value (vaep/base.py:97-137, vaep/formula.py:116-151) over every
- * segment: exactly sa_vaep_features (sa_vaep_features_xt when xt_cells != NULL) followed by
- * sa_vaep_labels_formula_f64 with the same arguments.  With nb_prev_actions <= 3 and
- * nr_actions <= 11 the labels and the formula are computed inside the numeric feature pass
- * (no launch of their own); otherwise the two launches run.  Windowed mode.  With p_scores,
- * p_concedes, off, def and val all NULL: features + labels only (compute_labels, no formula). */
+ * segment: exactly sa_vaep_features followed by sa_vaep_labels_formula (f32 = 0) with the same
+ * arguments.  With nb_prev_actions <= 3 and nr_actions <= 11 the labels and the formula are
+ * computed inside the numeric feature pass (no launch of their own); otherwise the two launches
+ * run.  Windowed mode.  With p_scores, p_concedes, off, def and val all NULL: features + labels
+ * only (compute_labels, no formula).
+ * chunk_rows != 0 (a multiple of 512; prefetch is ignored when 0): the numeric pass in launches
+ * of chunk_rows rows, each optionally preceded (prefetch != 0) by a pure-read pass that pulls the
+ * chunk's inputs into the Infinity Cache: an A/B probe of the pass's read / write turnaround
+ * (bench.py --num-chunks).  Only the fused SPADL form with probabilities and non-null outputs,
+ * and the numeric pass only (bool_out without columns of the plan); the same outputs bit for
+ * bit. */
 int sa_vaep_step_f64(const sa_actions* a, const sa_feature_plan* plan, const sa_block* bool_out,
                      const sa_block* f64_out, const sa_block* i64_out, int32_t xt_l, int32_t xt_w,
                      uint32_t* xt_cells, int32_t nr_actions, uint8_t* scores, uint8_t* concedes,
                      uint8_t* goal_from_shot, int64_t ld, const double* p_scores,
-                     const double* p_concedes, double* off, double* def, double* val, void* stream);
-/* sa_vaep_step_f64's numeric pass in launches of chunk_rows rows (a multiple of 512; 0: one
- * launch), each optionally preceded (prefetch != 0) by a pure-read pass that pulls the chunk's
- * inputs into the Infinity Cache: an A/B probe of the pass's read / write turnaround
- * (bench.py --num-chunks).  The numeric pass only (bool_out without columns of the plan); the
- * same outputs bit for bit. */
-int sa_vaep_step_f64_chunked(const sa_actions* a, const sa_feature_plan* plan, const sa_block* bool_out,
-                             const sa_block* f64_out, const sa_block* i64_out, int32_t xt_l, int32_t xt_w,
-                             uint32_t* xt_cells, int32_t nr_actions, uint8_t* scores, uint8_t* concedes,
-                             uint8_t* goal_from_shot, int64_t ld, const double* p_scores,
-                             const double* p_concedes, double* off, double* def, double* val,
-                             int64_t chunk_rows, int32_t prefetch, void* stream);
+                     const double* p_concedes, double* off, double* def, double* val,
+                     int64_t chunk_rows, int32_t prefetch, void* stream);
 
 /* ---- Expected Threat (xthreat.py) --------------------------------------------
  * Count pass over SPADL actions (frames[0] of `a`; segments ignored):
@@ -261,22 +243,19 @@ int sa_vaep_step_f64_chunked(const sa_actions* a, const sa_feature_plan* plan, c
  * 0x1 = infinite shot start (scoring_prob, action_prob, fit raise), 0x100 = infinite move
  * start (action_prob, move_transition_matrix, fit raise), 0x10000 = NaN move start or
  * non-finite move end (only move_transition_matrix and fit, which cast every move
- * coordinate, raise; such a move is left out of the transition counts). */
-int sa_xt_count(const sa_actions* a, int32_t l, int32_t w, int64_t* shot, int64_t* goal,
-                int64_t* move, int32_t* trans, int32_t* err_flags, void* stream);
-
-/* sa_xt_count that also writes, per action, the operand of a later rate() of the SAME actions
- * on the same (l, w) grid without interpolation (fit + rate of one frame, xthreat.py:322-345
- * then :408-465): codes[j] = start cell | end cell << 16 for a successful move, 0xFFFFFFFE for
- * a successful move with a non-finite coordinate, 0xFFFFFFFF otherwise.  codes: [n] u32,
- * 16-byte aligned, or NULL; l * w <= 65535.  flags: SA_XT_COUNT_SHARED when the pass runs
- * concurrently with other kernels (smaller workgroups that co-reside with them). */
+ * coordinate, raise; such a move is left out of the transition counts).
+ * codes ([n] u32, 16-byte aligned, or NULL; needs l * w <= 65535): per action the operand of a
+ * later rate() of the SAME actions on the same (l, w) grid without interpolation (fit + rate of
+ * one frame, xthreat.py:322-345 then :408-465): codes[j] = start cell | end cell << 16 for a
+ * successful move, 0xFFFFFFFE for a successful move with a non-finite coordinate, 0xFFFFFFFF
+ * otherwise.  flags: 0, or SA_XT_COUNT_SHARED when the pass runs concurrently with other
+ * kernels (smaller workgroups that co-reside with them). */
 #define SA_XT_COUNT_SHARED 1
-int sa_xt_count_codes(const sa_actions* a, int32_t l, int32_t w, int64_t* shot, int64_t* goal,
-                      int64_t* move, int32_t* trans, int32_t* err_flags, uint32_t* codes,
-                      int32_t flags, void* stream);
+int sa_xt_count(const sa_actions* a, int32_t l, int32_t w, int64_t* shot, int64_t* goal,
+                int64_t* move, int32_t* trans, int32_t* err_flags, uint32_t* codes, int32_t flags,
+                void* stream);
 
-/* Which count pass sa_xt_count, sa_xt_count_codes and sa_xt_count_cells run for an (l, w) grid,
+/* Which count pass sa_xt_count and sa_xt_count_cells run for an (l, w) grid,
  * n actions and `flags` (host only, no device call; the launcher itself asks this function):
  * WIDE = every bin as u32 in one workgroup's LDS per CU (l * w <= 194, without
  * SA_XT_COUNT_SHARED), SMALL = per-32768-action LDS histograms with the C x C bins packed two
@@ -293,7 +272,7 @@ int sa_xt_count_mode(int32_t l, int32_t w, int64_t n, int32_t flags);
 
 /* xT cell codes: the binning of a fit + rate of the SAME actions on an (l, w) grid with
  * l * w <= SA_XT_CELLS_MAX_C, computed once per action where the coordinates are read anyway
- * (sa_vaep_features_xt, or sa_xt_cells alone) and consumed by sa_xt_count_cells and
+ * (sa_vaep_features, or sa_xt_cells alone) and consumed by sa_xt_count_cells and
  * sa_xt_rate_cells, which then read 4 B per action instead of the 34 B of coordinates and ids.
  * Code (u32): bits 0-11 start cell, 12-23 end cell (xthreat.py:25-37 binning), 24-25 class
  * (1 = shot, type 11; 2 = move: pass / dribble / cross), 26 result == success, 27 NaN in the
@@ -318,8 +297,8 @@ int sa_xt_rate_cells(const uint32_t* cells, int64_t n, int32_t l, int32_t w, con
 
 /* Band-owned count of large grids (200 <= C <= 12000 cells, e.g. 105 x 68; sa_xt_count_mode
  * says whether a grid takes it, sa_xt_band_shape its shape -- also of smaller grids, which the
- * bucket calls below accept): the transition counts without global atomics.  sa_xt_count,
- * sa_xt_count_codes and sa_xt_count_cells use it internally for such grids; a fit over several
+ * bucket calls below accept): the transition counts without global atomics.  sa_xt_count
+ * and sa_xt_count_cells use it internally for such grids; a fit over several
  * device batches calls, per batch, sa_xt_count_bucket -- one key per counted action, sorted by
  * start-cell band into buckets[n] (u16: the action's bin in its band's R x P histogram,
  * (start cell - band * R) * P + slot, slot = the end cell of a successful move or C / C+1 / C+2
@@ -328,7 +307,7 @@ int sa_xt_rate_cells(const uint32_t* cells, int64_t n, int32_t l, int32_t w, con
  * SA_XT_COUNT_OVERWRITE writes) shot / goal / move and the C x C transition counts exactly as
  * sa_xt_count over all the batches would; err_flags as sa_xt_count, set by the bucket call.
  * `cells` (C <= SA_XT_CELLS_MAX_C) replaces the coordinates of `a` when not NULL (then `a` may
- * be NULL and n is the action count); `codes` as in sa_xt_count_codes (coordinates only).
+ * be NULL and n is the action count); `codes` as in sa_xt_count (coordinates only).
  * buckets / band_off are plain device arrays the caller keeps until the count call.
  * Replaces xthreat.py:40-67 (`_count`) and :177-218 (`move_transition_matrix` counts). */
 #define SA_XT_COUNT_OVERWRITE 2
@@ -350,23 +329,18 @@ int sa_xt_count_band_rows(int32_t nsets, const uint16_t* const* buckets,
  * later rate(use_interpolation=True) of the SAME actions on the L x W node grid -- start node |
  * end node << 32 of a successful move, 2^64 - 2 for one with a non-finite coordinate, 2^64 - 1
  * otherwise -- consumed by sa_xt_rate_interp_codes, which then equals sa_xt_rate_interp on those
- * actions bit for bit (values, NaN pattern, err_flags bit 4) reading 8 B per action. */
-int sa_xt_rate_interp_codes(const uint64_t* interp_codes, int64_t n, const double* xT,
-                            const double* cx, const double* cy, int32_t l, int32_t w,
-                            const double* xs, int32_t L, const double* ys, int32_t W, double* out,
-                            int32_t* err_flags, void* stream);
-/* sa_xt_rate_interp_codes of nsets action sets (a fit's device batches) in one launch per 16
- * sets, the surface staged once: set q's interp_codes[q] / n[q] / out[q] as above, one err_flags
- * for all.  (ExpectedThreat.rate(use_interpolation=True) xthreat.py:443-464 of a fit's
- * batches.) */
-int sa_xt_rate_interp_codes_many(int32_t nsets, const uint64_t* const* interp_codes,
-                                 const int64_t* n, const double* xT, const double* cx,
-                                 const double* cy, int32_t l, int32_t w, const double* xs,
-                                 int32_t L, const double* ys, int32_t W, double* const* out,
-                                 int32_t* err_flags, void* stream);
+ * actions bit for bit (values, NaN pattern, err_flags bit 4) reading 8 B per action.
+ * It rates nsets action sets (a fit's device batches; one batch is nsets = 1) in one launch per
+ * 16 sets, the surface staged once: set q's interp_codes[q] / n[q] / out[q] ([host] arrays of
+ * nsets entries; codes and out 16-byte aligned), one err_flags for all.
+ * (ExpectedThreat.rate(use_interpolation=True) xthreat.py:443-464 of a fit's batches.) */
+int sa_xt_rate_interp_codes(int32_t nsets, const uint64_t* const* interp_codes, const int64_t* n,
+                            const double* xT, const double* cx, const double* cy, int32_t l,
+                            int32_t w, const double* xs, int32_t L, const double* ys, int32_t W,
+                            double* const* out, int32_t* err_flags, void* stream);
 /* ExpectedThreat.fit + rate(use_interpolation=True) of the same actions (xthreat.py:322-345,
- * 408-465) in one call, for grids above the small-grid limit: sa_xt_solve_ex (no transposed
- * matrix; ell / row_len the count's compact rows or NULL) then sa_xt_rate_interp_codes_many over
+ * 408-465) in one call, for grids above the small-grid limit: sa_xt_solve (no transposed
+ * matrix; ell / row_len the count's compact rows or NULL) then sa_xt_rate_interp_codes over
  * the surface mats[3 * C ..] -- the rate queued right behind the one-launch reordered solve,
  * before the host waits for the solve's status, and run again when the status sends the solve to
  * the reference's order.  The same outputs as the two calls. */
@@ -379,25 +353,21 @@ int sa_xt_fit_rate_interp_codes(const int64_t* shot, const int64_t* goal, const 
                                 const double* cx, const double* cy, const double* xs, int32_t L,
                                 const double* ys, int32_t W, double* const* out,
                                 int32_t* err_flags, void* stream);
-int sa_xt_count_from_buckets(int32_t nsets, const uint16_t* const* buckets,
-                             const int64_t* const* band_off, int32_t l, int32_t w, int64_t* shot,
-                             int64_t* goal, int64_t* move, int32_t* trans, int32_t flags,
-                             void* stream);
-/* sa_xt_count_from_buckets that also writes the count rows in the compact form of
- * sa_xt_compact_rows (ell [C * sa_xt_compact_bytes(C, 1) / 4] u32, 16-byte aligned; row_len [C]),
- * straight from the bins: the large-grid solve (sa_xt_solve_ex with ell / row_len) then skips
- * its own build pass over the dense table.  Needs SA_XT_COUNT_OVERWRITE, at most 24 bucket sets
- * and 1025 <= C <= 9472; ell = row_len = NULL is sa_xt_count_from_buckets.
+/* The count over every batch's buckets (above).  ell / row_len (both, or both NULL): also writes
+ * the count rows in the compact form of sa_xt_compact_rows (ell [C * sa_xt_compact_bytes(C, 1) / 4]
+ * u32, 16-byte aligned; row_len [C]), straight from the bins: the large-grid solve (sa_xt_solve
+ * with ell / row_len) then skips its own build pass over the dense table.  That needs
+ * SA_XT_COUNT_OVERWRITE, at most 24 bucket sets and 1025 <= C <= 9472.
  * flags | SA_XT_COUNT_COMPACT_ONLY (with ell): the dense C x C rows of `trans` are written only
  * for the bands (sa_xt_band_shape's rows per band) that hold a transition count >= 65535 -- the
  * only dense entries the compact solve reads; the other rows are left as they were.  shot / goal
  * / move, ell and row_len are written in full.  (A fit that reads only the compact rows: no
  * 4 C^2-byte flush, 204 MB at 105 x 68.) */
 #define SA_XT_COUNT_COMPACT_ONLY 4
-int sa_xt_count_from_buckets_ex(int32_t nsets, const uint16_t* const* buckets,
-                                const int64_t* const* band_off, int32_t l, int32_t w,
-                                int64_t* shot, int64_t* goal, int64_t* move, int32_t* trans,
-                                int32_t flags, uint32_t* ell, int32_t* row_len, void* stream);
+int sa_xt_count_from_buckets(int32_t nsets, const uint16_t* const* buckets,
+                             const int64_t* const* band_off, int32_t l, int32_t w, int64_t* shot,
+                             int64_t* goal, int64_t* move, int32_t* trans, int32_t flags,
+                             uint32_t* ell, int32_t* row_len, void* stream);
 
 /* Grids up to SA_XT_SOLVE_MAX_C cells solve in one workgroup from the transposed matrix. */
 #define SA_XT_SOLVE_MAX_C 1024
@@ -411,22 +381,19 @@ int sa_xt_count_from_buckets_ex(int32_t nsets, const uint16_t* const* buckets,
  *   heatmaps[(max_iter+1)*C] = x after 0..n_iter iterations
  * *n_iter [host] receives the iteration count (-1: max_iter reached first).
  * Synchronises the stream.  Like the counts, every entry point that takes a grid needs
- * l * w <= 46340 (int32 indexing of the C x C counts) and returns SA_EINVAL above. */
-int sa_xt_solve(const int64_t* shot, const int64_t* goal, const int64_t* move,
-                const int32_t* trans, int32_t l, int32_t w, double eps, int32_t max_iter,
-                double* mats, double* trans_t, double* heatmaps, int32_t* n_iter, void* stream);
-/* sa_xt_solve (ExpectedThreat.fit xthreat.py:322-345 + __solve :278-320) with a choice of
- * summation order for grids above SA_XT_SOLVE_MAX_C cells (smaller
- * grids always sum in the reference's order, bit-exact).  Large grids by default solve in ONE
+ * l * w <= 46340 (int32 indexing of the C x C counts) and returns SA_EINVAL above.
+ * (ExpectedThreat.fit xthreat.py:322-345 + __solve :278-320.)
+ * flags chooses the summation order for grids above SA_XT_SOLVE_MAX_C cells (smaller grids
+ * always sum in the reference's order, bit-exact).  With 0, large grids solve in ONE
  * launch with each row's sum reordered into a fixed parallel tree (run-to-run reproducible)
  * under a rigorous error bound: every `diff > eps` decision, and so the iteration count, is the
  * reference's, and the iterates are within 4e-11 relative of the reference's (26 iterations at
  * 105 x 68); when some cell's diff falls inside the bound the system is re-solved in the
- * reference's order.  flags: SA_XT_SOLVE_EXACT = always the reference's order (bit-exact
- * iterates, one launch per iteration).  *path (may be NULL) receives which path produced the
- * result (SA_XT_PATH_*).  ell / row_len (both or NULL; grids of 1025 - 9472 cells): the compact
- * form of `trans` as sa_xt_count_from_buckets_ex or sa_xt_compact_rows wrote it, used instead of
- * building it again.  Same outputs and synchronisation as sa_xt_solve. */
+ * reference's order.  SA_XT_SOLVE_EXACT = always the reference's order (bit-exact iterates, one
+ * launch per iteration).  *path (may be NULL) receives which path produced the result
+ * (SA_XT_PATH_*).  ell / row_len (both or NULL; grids of 1025 - 9472 cells): the compact form of
+ * `trans` as sa_xt_count_from_buckets or sa_xt_compact_rows wrote it, used instead of building
+ * it again. */
 #define SA_XT_SOLVE_EXACT 1
 #define SA_XT_PATH_SEQUENTIAL 0   /* the reference's order (small grid, or SA_XT_SOLVE_EXACT) */
 #define SA_XT_PATH_REORDERED 1    /* reordered sums, every decision outside the error bound */
@@ -434,10 +401,10 @@ int sa_xt_solve(const int64_t* shot, const int64_t* goal, const int64_t* move,
 #define SA_XT_PATH_UNAVAILABLE 3  /* reordered solve not launchable here: solved in order */
 #define SA_XT_PATH_TIMEOUT 4      /* the reordered solve's grid barrier timed out (another grid held
                                      CUs: 50 ms at the first barrier, 1 s later): solved in order */
-int sa_xt_solve_ex(const int64_t* shot, const int64_t* goal, const int64_t* move,
-                   const int32_t* trans, int32_t l, int32_t w, double eps, int32_t max_iter,
-                   int32_t flags, double* mats, double* trans_t, double* heatmaps, int32_t* n_iter,
-                   int32_t* path, const uint32_t* ell, const int32_t* row_len, void* stream);
+int sa_xt_solve(const int64_t* shot, const int64_t* goal, const int64_t* move,
+                const int32_t* trans, int32_t l, int32_t w, double eps, int32_t max_iter,
+                int32_t flags, double* mats, double* trans_t, double* heatmaps, int32_t* n_iter,
+                int32_t* path, const uint32_t* ell, const int32_t* row_len, void* stream);
 /* sa_xt_solve for grids of <= SA_XT_SOLVE_MAX_C cells without the host round trip: the
  * iteration count (-1: max_iter reached first) is written to device memory *n_iter_dev and
  * nothing is synchronised, so a consumer of the surface (sa_xt_rate_cells) can be enqueued
@@ -488,7 +455,7 @@ int sa_xt_iterate_compact(const uint32_t* ell, const int32_t* row_len, const int
  * its C rows (as built by
  * sa_xt_compact_rows; the multi-GPU fit gathers it from the ranks): heatmaps[(max_iter+1)*C]
  * = x after 0..n_iter iterations, *n_iter [host] the count (-1: max_iter reached first), the
- * summation order chosen by `flags` exactly as in sa_xt_solve_ex (*path may be NULL).
+ * summation order chosen by `flags` exactly as in sa_xt_solve (*path may be NULL).
  * cnt_rows: the dense count rows, read only for counts >= 65535.  Synchronises the stream. */
 int sa_xt_solve_compact(const uint32_t* ell, const int32_t* row_len, const int32_t* cnt_rows,
                         const int64_t* move, const double* gs, const double* pmove, int32_t C,
@@ -522,7 +489,7 @@ int sa_xt_rate_interp(const sa_actions* a, const double* xT, const double* cx, c
 int sa_xt_rate(const sa_actions* a, const double* grid, int32_t L, int32_t W, double* out,
                int32_t* err_flags, void* stream);
 
-/* sa_xt_rate from the codes of sa_xt_count_codes (grid = the fitted (w, l) xT surface):
+/* sa_xt_rate from the codes of sa_xt_count (grid = the fitted (w, l) xT surface):
  * same values and err_flags bit 4 as sa_xt_rate on those actions, reading 4 B per action
  * instead of the coordinates and ids.  out: [n] f64, 16-byte aligned. */
 int sa_xt_rate_codes(const uint32_t* codes, int64_t n, const double* grid, double* out,
@@ -590,11 +557,16 @@ typedef struct sa_atomic_frame {
 /* Device scratch the two calls below share (bytes, 16-byte aligned). */
 int64_t sa_atomic_scratch_bytes(int64_t n);
 /* Pass 1: the output row count of every SA_ATOMIC_BLOCK_ROWS-row block and their exclusive prefix;
- * *n_out [host] receives the total.  Synchronises the stream. */
-int sa_atomic_count(const sa_spadl_frame* in, void* scratch, int64_t* n_out, void* stream);
-/* Pass 2: writes the n_out output rows (scratch from sa_atomic_count, same input). */
-int sa_atomic_emit(const sa_spadl_frame* in, const void* scratch, const sa_atomic_frame* out,
-                   void* stream);
+ * *n_out [host] receives the total.  Synchronises the stream.
+ * after_passes != 0 (both calls; in->order must be NULL): `in` is the sorted output of
+ * sa_atomic_passes_emit (below), so the first pass is skipped -- the reference's remaining passes
+ * (_add_dribbles, _extra_from_shots, _extra_from_fouls) and the column conversion. */
+int sa_atomic_count(const sa_spadl_frame* in, int32_t after_passes, void* scratch, int64_t* n_out,
+                    void* stream);
+/* Pass 2: writes the n_out output rows (scratch from sa_atomic_count, same input and
+ * after_passes). */
+int sa_atomic_emit(const sa_spadl_frame* in, int32_t after_passes, const void* scratch,
+                   const sa_atomic_frame* out, void* stream);
 
 /* ---- _add_dribbles (spadl/base.py:54-93) ------------------------------------------
  * SPADL rows out (device, length n_out): the input columns' codes plus `src`, the input row a
@@ -648,16 +620,10 @@ int sa_dribble_emit(const sa_spadl_frame* in, double min_len2, double max_len2, 
  *     of (game, period, action_id / action_id + 0.1), from the host).  Inserted rows carry
  *     start = end = the parent's end, the midpoint time, bodypart foot, result 255 (the
  *     reference's -1) and the atomic type id; src = input row, or ~parent for an inserted row.
- *   sa_atomic_count_after_passes / sa_atomic_emit_after_passes: sa_atomic_count / emit of that
- *     sorted output (order NULL) without the first pass -- the reference's remaining passes
- *     (_add_dribbles, _extra_from_shots, _extra_from_fouls) and the column conversion. */
+ *   sa_atomic_count / sa_atomic_emit with after_passes = 1 then run on that sorted output. */
 int sa_atomic_passes_flags(const sa_spadl_frame* in, uint8_t* flags, void* stream);
 int sa_atomic_passes_emit(const sa_spadl_frame* in, const int64_t* parents, int64_t m,
                           const int64_t* dest, const sa_spadl_out* out, void* stream);
-int sa_atomic_count_after_passes(const sa_spadl_frame* in, void* scratch, int64_t* n_out,
-                                 void* stream);
-int sa_atomic_emit_after_passes(const sa_spadl_frame* in, const void* scratch,
-                                const sa_atomic_frame* out, void* stream);
 
 /* Segment (game) offsets of a row-sorted key column whose values are exactly 0..n_segments-1,
  * each present -- e.g. the game codes of sa_atomic_emit's output:
@@ -722,7 +688,7 @@ int sa_tree_predict(const void* nodes, int32_t n_nodes, const int32_t* roots, co
  * levels of each tree; p_out[n]: the probabilities.  T = float for f32 = 1 (xgboost), else
  * double.  The bool columns come from bool_blk, or -- when bool_bits is not NULL -- from the
  * bitmaps of sa_vaep_features_bits (bool_cols index its bitmaps; bits_stride a multiple of 8).
- * f32 bit 1 (f32 = 3): the f64 / i64 blocks hold float32 values (sa_vaep_features_bits_f32);
+ * f32 bit 1 (f32 = 3): the f64 / i64 blocks hold float32 values (sa_vaep_features_bits with f32);
  * xgboost arithmetic only (bit 0 set), and the same probabilities bit for bit.
  * sa_tree_staged_lds_bytes: the LDS a model needs at most (<= 160 KiB; n_cond = 1 + n_bool +
  * n_num; the walk also stages the roots and depths, bounded here by n_nodes trees). */

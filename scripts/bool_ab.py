@@ -61,7 +61,7 @@ def main():
         for v, lib in libs.items():
             def run():
                 N.check(lib.sa_vaep_features(ctypes.byref(s), ctypes.byref(q.struct),
-                                             ctypes.byref(blk), None, None, stream))
+                                             ctypes.byref(blk), None, None, 0, 0, None, stream))
             bb.zero_()
             run()
             torch.cuda.synchronize()

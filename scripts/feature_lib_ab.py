@@ -78,15 +78,11 @@ def main():
                             10, lab[0].data_ptr(), lab[1].data_ptr(), None, ld,
                             None if lo else ps.data_ptr(), None if lo else pc.data_ptr(),
                             None if lo else val[0].data_ptr(), None if lo else val[1].data_ptr(),
-                            None if lo else val[2].data_ptr(), stream))
-                        return
-                    if tag == 'num_cells':
-                        N.check(lib.sa_vaep_features_xt(ctypes.byref(s), ctypes.byref(p.struct), ctypes.byref(bb),
-                                                        ctypes.byref(fb), ctypes.byref(ib), 16, 12,
-                                                        cells.data_ptr(), stream))
+                            None if lo else val[2].data_ptr(), 0, 0, stream))
                         return
                     N.check(lib.sa_vaep_features(ctypes.byref(s), ctypes.byref(p.struct), ctypes.byref(bb),
-                                                 ctypes.byref(fb), ctypes.byref(ib), stream))
+                                                 ctypes.byref(fb), ctypes.byref(ib), 16, 12,
+                                                 cells.data_ptr() if tag == 'num_cells' else None, stream))
                 run()
                 torch.cuda.synchronize()
                 if tag == 'step':  # the step form's outputs, compared across the builds too
@@ -119,11 +115,11 @@ def main():
                         ctypes.byref(s), ctypes.byref(num.struct), ctypes.byref(bb), ctypes.byref(fb),
                         ctypes.byref(ib), 16, 12, cells.data_ptr(), 10, lab[0].data_ptr(), lab[1].data_ptr(), None,
                         ld, ps.data_ptr(), pc.data_ptr(), val[0].data_ptr(), val[1].data_ptr(), val[2].data_ptr(),
-                        stream))
+                        0, 0, stream))
 
                 def boolp():
                     N.check(lib.sa_vaep_features(ctypes.byref(s), ctypes.byref(bonly.struct), ctypes.byref(bb),
-                                                 ctypes.byref(fb), ctypes.byref(ib), stream))
+                                                 ctypes.byref(fb), ctypes.byref(ib), 0, 0, None, stream))
                 step()
                 boolp()
                 ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.reps)]

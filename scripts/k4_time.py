@@ -1,4 +1,4 @@
-"""K4 (the band count's table pass, sa_xt_count_from_buckets_ex) over cfg5's 7 bucketed batches,
+"""K4 (the band count's table pass, sa_xt_count_from_buckets) over cfg5's 7 bucketed batches,
 with and without the compact-row emission, HIP events."""
 import json
 import os

@@ -1,4 +1,4 @@
-"""A/B of the interpolated rate from count-pass operands (sa_xt_rate_interp_codes_many) across
+"""A/B of the interpolated rate from count-pass operands (sa_xt_rate_interp_codes) across
 library builds on the SAME operands: the default library and variant builds
 (``python -m socceraction_amd.build -DNAME=V --variant=tag``), HIP events, round-robin; the
 outputs must be bit-identical.
@@ -52,7 +52,7 @@ def main():
     for rnd in range(3):
         for name, lib in libs.items():
             def run():
-                N.check(lib.sa_xt_rate_interp_codes_many(
+                N.check(lib.sa_xt_rate_interp_codes(
                     k, cp, nn, xT.data_ptr(), axes[:l].data_ptr(), axes[l:o].data_ptr(), l, w,
                     axes[o:o + L].data_ptr(), L, axes[o + L:].data_ptr(), W, op, err.data_ptr(), stream))
             run()

@@ -71,7 +71,7 @@ def large(ab, libs, reps):
 
             def run():
                 N.check(lib.sa_xt_count(ctypes.byref(s), 105, 68, acc.shot.data_ptr(), acc.goal.data_ptr(),
-                                        acc.move.data_ptr(), acc.trans.data_ptr(), acc.err.data_ptr(), stream))
+                                        acc.move.data_ptr(), acc.trans.data_ptr(), acc.err.data_ptr(), None, 0, stream))
             run()
             torch.cuda.synchronize()
             out['equal'][name] = bool(torch.equal(acc.trans, ref.trans) and torch.equal(acc.move, ref.move)

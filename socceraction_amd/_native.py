@@ -29,8 +29,8 @@ SA_XT_COUNT_SHARED, SA_XT_COUNT_OVERWRITE, SA_XT_COUNT_COMPACT_ONLY = 1, 2, 4
  SA_XT_COUNT_MODE_BANDS) = 0, 1, 2, 3, 4
 SA_XT_CELLS16_MAX_C = 202  # xT cell codes: 16 bits per action up to this many cells
 SA_XT_COMPACT_MAX_C = 9472  # sa_xt_compact_rows / sa_xt_iterate_compact
-SA_XT_SOLVE_EXACT = 1  # sa_xt_solve_ex / sa_xt_solve_compact: the reference's summation order
-# which path produced a large-grid solve (sa_xt_solve_ex's *path)
+SA_XT_SOLVE_EXACT = 1  # sa_xt_solve / sa_xt_solve_compact: the reference's summation order
+# which path produced a large-grid solve (sa_xt_solve's *path)
 XT_SOLVE_PATHS = ('sequential', 'reordered', 'inside-bound', 'unavailable', 'timeout')
 SA_BOOL_TILE_QUANTUM = 1024
 SA_NUM_TILE_QUANTUM = 128
@@ -131,46 +131,28 @@ class SaSpadlOut(ctypes.Structure):
 _SIGNATURES = {
     'sa_vaep_features': (ctypes.c_int, [ctypes.POINTER(SaActions), ctypes.POINTER(SaFeaturePlan),
                                         ctypes.POINTER(SaBlock), ctypes.POINTER(SaBlock),
-                                        ctypes.POINTER(SaBlock), _p]),
+                                        ctypes.POINTER(SaBlock), ctypes.c_int32, ctypes.c_int32, _p, _p]),
     'sa_vaep_goalscore': (ctypes.c_int, [ctypes.POINTER(SaActions), ctypes.POINTER(SaBlock),
                                          ctypes.c_int32, _p]),
     'sa_vaep_labels': (ctypes.c_int, [ctypes.POINTER(SaActions), ctypes.c_int32, _p, _p, _p,
                                       ctypes.c_int64, _p]),
-    'sa_vaep_formula_f64': (ctypes.c_int, [ctypes.POINTER(SaActions), _p, _p, _p, _p, _p, _p]),
-    'sa_vaep_formula_f32': (ctypes.c_int, [ctypes.POINTER(SaActions), _p, _p, _p, _p, _p, _p]),
-    'sa_vaep_labels_formula_f64': (ctypes.c_int, [ctypes.POINTER(SaActions), ctypes.c_int32, _p, _p,
-                                                  _p, ctypes.c_int64, _p, _p, _p, _p, _p, _p]),
-    'sa_vaep_labels_formula_f32': (ctypes.c_int, [ctypes.POINTER(SaActions), ctypes.c_int32, _p, _p,
-                                                  _p, ctypes.c_int64, _p, _p, _p, _p, _p, _p]),
+    'sa_vaep_formula': (ctypes.c_int, [ctypes.POINTER(SaActions), ctypes.c_int32, _p, _p, _p, _p, _p, _p]),
+    'sa_vaep_labels_formula': (ctypes.c_int, [ctypes.POINTER(SaActions), ctypes.c_int32, _p, _p, _p,
+                                              ctypes.c_int64, ctypes.c_int32, _p, _p, _p, _p, _p, _p]),
     'sa_vaep_step_f64': (ctypes.c_int, [ctypes.POINTER(SaActions), ctypes.POINTER(SaFeaturePlan),
                                         ctypes.POINTER(SaBlock), ctypes.POINTER(SaBlock),
                                         ctypes.POINTER(SaBlock), ctypes.c_int32, ctypes.c_int32, _p,
                                         ctypes.c_int32, _p, _p, _p, ctypes.c_int64, _p, _p, _p, _p,
-                                        _p, _p]),
-    'sa_vaep_step_f64_chunked': (ctypes.c_int, [ctypes.POINTER(SaActions), ctypes.POINTER(SaFeaturePlan),
-                                                ctypes.POINTER(SaBlock), ctypes.POINTER(SaBlock),
-                                                ctypes.POINTER(SaBlock), ctypes.c_int32, ctypes.c_int32, _p,
-                                                ctypes.c_int32, _p, _p, _p, ctypes.c_int64, _p, _p, _p, _p,
-                                                _p, ctypes.c_int64, ctypes.c_int32, _p]),
+                                        _p, ctypes.c_int64, ctypes.c_int32, _p]),
     'sa_xt_count': (ctypes.c_int, [ctypes.POINTER(SaActions), ctypes.c_int32, ctypes.c_int32,
-                                   _p, _p, _p, _p, _p, _p]),
-    'sa_xt_count_codes': (ctypes.c_int, [ctypes.POINTER(SaActions), ctypes.c_int32,
-                                         ctypes.c_int32, _p, _p, _p, _p, _p, _p,
-                                         ctypes.c_int32, _p]),
+                                   _p, _p, _p, _p, _p, _p, ctypes.c_int32, _p]),
     'sa_xt_rate_codes': (ctypes.c_int, [_p, ctypes.c_int64, _p, _p, _p, _p]),
     'sa_vaep_features_bits': (ctypes.c_int, [ctypes.POINTER(SaActions), ctypes.POINTER(SaFeaturePlan),
-                                             _p, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(SaBlock),
-                                             ctypes.POINTER(SaBlock), _p]),
-    'sa_vaep_features_bits_f32': (ctypes.c_int, [ctypes.POINTER(SaActions), ctypes.POINTER(SaFeaturePlan),
-                                                 _p, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(SaBlock),
-                                                 ctypes.POINTER(SaBlock), _p]),
+                                             _p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.POINTER(SaBlock), ctypes.POINTER(SaBlock), _p]),
     'sa_vaep_features_conditions': (ctypes.c_int, [ctypes.POINTER(SaActions), ctypes.POINTER(SaFeaturePlan),
                                                    _p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.c_int32, _p, _p, _p, _p, ctypes.c_int32, _p]),
-    'sa_vaep_features_xt': (ctypes.c_int, [ctypes.POINTER(SaActions),
-                                           ctypes.POINTER(SaFeaturePlan), ctypes.POINTER(SaBlock),
-                                           ctypes.POINTER(SaBlock), ctypes.POINTER(SaBlock),
-                                           ctypes.c_int32, ctypes.c_int32, _p, _p]),
     'sa_xt_cells': (ctypes.c_int, [ctypes.POINTER(SaActions), ctypes.c_int32, ctypes.c_int32, _p,
                                    _p]),
     'sa_xt_count_cells': (ctypes.c_int, [_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _p,
@@ -178,12 +160,9 @@ _SIGNATURES = {
     'sa_xt_rate_cells': (ctypes.c_int, [_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _p,
                                         _p, _p, _p]),
     'sa_xt_solve': (ctypes.c_int, [_p, _p, _p, _p, ctypes.c_int32, ctypes.c_int32,
-                                   ctypes.c_double, ctypes.c_int32, _p, _p, _p,
-                                   ctypes.POINTER(ctypes.c_int32), _p]),
-    'sa_xt_solve_ex': (ctypes.c_int, [_p, _p, _p, _p, ctypes.c_int32, ctypes.c_int32,
-                                      ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _p, _p, _p,
-                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
-                                      _p, _p, _p]),
+                                   ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _p, _p, _p,
+                                   ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                   _p, _p, _p]),
     'sa_xt_solve_compact': (ctypes.c_int, [_p, _p, _p, _p, _p, _p, ctypes.c_int32, ctypes.c_double,
                                            ctypes.c_int32, ctypes.c_int32, _p,
                                            ctypes.POINTER(ctypes.c_int32),
@@ -202,13 +181,10 @@ _SIGNATURES = {
     'sa_xt_count_bucket': (ctypes.c_int, [ctypes.POINTER(SaActions), _p, ctypes.c_int64, ctypes.c_int32,
                                           ctypes.c_int32, _p, _p, _p, _p, _p, ctypes.c_int32,
                                           ctypes.c_int32, _p]),
-    'sa_xt_rate_interp_codes': (ctypes.c_int, [_p, ctypes.c_int64, _p, _p, _p, ctypes.c_int32,
-                                               ctypes.c_int32, _p, ctypes.c_int32, _p, ctypes.c_int32,
-                                               _p, _p, _p]),
-    'sa_xt_rate_interp_codes_many': (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(_p),
-                                                    ctypes.POINTER(ctypes.c_int64), _p, _p, _p,
-                                                    ctypes.c_int32, ctypes.c_int32, _p, ctypes.c_int32,
-                                                    _p, ctypes.c_int32, ctypes.POINTER(_p), _p, _p]),
+    'sa_xt_rate_interp_codes': (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(_p),
+                                               ctypes.POINTER(ctypes.c_int64), _p, _p, _p,
+                                               ctypes.c_int32, ctypes.c_int32, _p, ctypes.c_int32,
+                                               _p, ctypes.c_int32, ctypes.POINTER(_p), _p, _p]),
     'sa_xt_fit_rate_interp_codes': (ctypes.c_int, [_p, _p, _p, _p, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _p, _p,
                                                    ctypes.POINTER(ctypes.c_int32),
@@ -216,12 +192,9 @@ _SIGNATURES = {
                                                    ctypes.POINTER(_p), ctypes.POINTER(ctypes.c_int64), _p, _p,
                                                    _p, ctypes.c_int32, _p, ctypes.c_int32, ctypes.POINTER(_p),
                                                    _p, _p]),
-    'sa_xt_count_from_buckets_ex': (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(_p), ctypes.POINTER(_p),
-                                                   ctypes.c_int32, ctypes.c_int32, _p, _p, _p, _p,
-                                                   ctypes.c_int32, _p, _p, _p]),
     'sa_xt_count_from_buckets': (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(_p), ctypes.POINTER(_p),
                                                 ctypes.c_int32, ctypes.c_int32, _p, _p, _p, _p,
-                                                ctypes.c_int32, _p]),
+                                                ctypes.c_int32, _p, _p, _p]),
     'sa_xt_count_band_rows': (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(_p), ctypes.POINTER(_p),
                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                              ctypes.c_int32, _p, _p, _p, _p, ctypes.c_int32, _p]),
@@ -237,9 +210,9 @@ _SIGNATURES = {
                                          ctypes.c_int32, _p, ctypes.c_int32, _p, ctypes.c_int32,
                                          _p, _p, _p]),
     'sa_atomic_scratch_bytes': (ctypes.c_int64, [ctypes.c_int64]),
-    'sa_atomic_count': (ctypes.c_int, [ctypes.POINTER(SaSpadlFrame), _p,
+    'sa_atomic_count': (ctypes.c_int, [ctypes.POINTER(SaSpadlFrame), ctypes.c_int32, _p,
                                        ctypes.POINTER(ctypes.c_int64), _p]),
-    'sa_atomic_emit': (ctypes.c_int, [ctypes.POINTER(SaSpadlFrame), _p,
+    'sa_atomic_emit': (ctypes.c_int, [ctypes.POINTER(SaSpadlFrame), ctypes.c_int32, _p,
                                       ctypes.POINTER(SaAtomicFrame), _p]),
     'sa_dribble_count': (ctypes.c_int, [ctypes.POINTER(SaSpadlFrame), ctypes.c_double,
                                         ctypes.c_double, ctypes.c_double, _p, _p, _p,
@@ -248,10 +221,6 @@ _SIGNATURES = {
     'sa_atomic_passes_flags': (ctypes.c_int, [ctypes.POINTER(SaSpadlFrame), _p, _p]),
     'sa_atomic_passes_emit': (ctypes.c_int, [ctypes.POINTER(SaSpadlFrame), _p, ctypes.c_int64, _p,
                                              ctypes.POINTER(SaSpadlOut), _p]),
-    'sa_atomic_count_after_passes': (ctypes.c_int, [ctypes.POINTER(SaSpadlFrame), _p,
-                                                    ctypes.POINTER(ctypes.c_int64), _p]),
-    'sa_atomic_emit_after_passes': (ctypes.c_int, [ctypes.POINTER(SaSpadlFrame), _p,
-                                                   ctypes.POINTER(SaAtomicFrame), _p]),
     'sa_dribble_emit': (ctypes.c_int, [ctypes.POINTER(SaSpadlFrame), ctypes.c_double,
                                        ctypes.c_double, ctypes.c_double, _p, _p,
                                        ctypes.POINTER(SaSpadlOut), _p]),
@@ -367,7 +336,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    if lib.sa_abi_version() != 5:
+    if lib.sa_abi_version() != 6:
         raise ImportError('libsocceraction_amd ABI version mismatch')
     _check_build_id(lib, path)
     if path == LIB_PATH:

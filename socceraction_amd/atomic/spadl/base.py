@@ -280,14 +280,14 @@ def convert_device(frame: SpadlFrame) -> AtomicColumns:
     lib = _native.lib()
     if frame.keys is not None and not frame.after_passes:
         frame = first_pass_device(frame)
-    count, emit = ((lib.sa_atomic_count_after_passes, lib.sa_atomic_emit_after_passes)
-                   if frame.after_passes else (lib.sa_atomic_count, lib.sa_atomic_emit))
+    after = int(bool(frame.after_passes))
     dev = frame.buffer.device
     s = frame.struct()
     scratch = torch.empty(max(int(lib.sa_atomic_scratch_bytes(frame.n)), 16), dtype=torch.uint8,
                           device=dev)
     n_out = ctypes.c_int64(0)
-    _native.check(count(ctypes.byref(s), scratch.data_ptr(), ctypes.byref(n_out), stream_handle()))
+    _native.check(lib.sa_atomic_count(ctypes.byref(s), after, scratch.data_ptr(), ctypes.byref(n_out),
+                                      stream_handle()))
     m = int(n_out.value)
     spec = {'time_seconds': np.float64, 'x': np.float64, 'y': np.float64, 'dx': np.float64,
             'dy': np.float64, 'game': np.int32, 'team': np.int32, 'player': np.int32,
@@ -296,7 +296,7 @@ def convert_device(frame: SpadlFrame) -> AtomicColumns:
     out = AtomicColumns(m, buf, cols)
     if m:
         o = out.struct()
-        _native.check(emit(ctypes.byref(s), scratch.data_ptr(), ctypes.byref(o), stream_handle()))
+        _native.check(lib.sa_atomic_emit(ctypes.byref(s), after, scratch.data_ptr(), ctypes.byref(o), stream_handle()))
     return out
 
 

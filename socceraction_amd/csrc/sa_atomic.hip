@@ -616,9 +616,16 @@ static int check_spadl_frame(const sa_spadl_frame* F) {
   return SA_OK;
 }
 
-template <bool PASSES>
-static int atomic_count(const sa_spadl_frame* in, void* scratch, int64_t* n_out, void* stream) {
-  int rc = check_spadl_frame(in);
+// after_passes: the first pass (_extra_from_passes) ran on its own, so the kernels skip it
+static int check_expand_input(const sa_spadl_frame* in, int32_t after_passes) {
+  if (after_passes && in && in->order)
+    return fail(SA_EINVAL, "the first pass's output is sorted: order must be NULL");
+  return check_spadl_frame(in);
+}
+
+extern "C" int sa_atomic_count(const sa_spadl_frame* in, int32_t after_passes, void* scratch, int64_t* n_out,
+                               void* stream) {
+  int rc = check_expand_input(in, after_passes);
   if (rc) return rc;
   if (!n_out || (in->n > 0 && !scratch)) return fail(SA_EINVAL, "null scratch or n_out");
   *n_out = 0;
@@ -626,7 +633,10 @@ static int atomic_count(const sa_spadl_frame* in, void* scratch, int64_t* n_out,
   hipStream_t st = (hipStream_t)stream;
   const int64_t nb = n_blocks(in->n);
   int64_t* bsum = (int64_t*)scratch;
-  hipLaunchKernelGGL(atomic_count_kernel<PASSES>, dim3((unsigned)nb), dim3(AC_THREADS), 0, st, *in, bsum);
+  if (after_passes)
+    hipLaunchKernelGGL(atomic_count_kernel<false>, dim3((unsigned)nb), dim3(AC_THREADS), 0, st, *in, bsum);
+  else
+    hipLaunchKernelGGL(atomic_count_kernel<true>, dim3((unsigned)nb), dim3(AC_THREADS), 0, st, *in, bsum);
   if ((rc = check_launch("atomic_count_kernel"))) return rc;
   hipLaunchKernelGGL(atomic_scan_kernel, dim3(1), dim3(SC_THREADS), 0, st, bsum, nb);
   if ((rc = check_launch("atomic_scan_kernel"))) return rc;
@@ -636,9 +646,9 @@ static int atomic_count(const sa_spadl_frame* in, void* scratch, int64_t* n_out,
   return check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
 }
 
-template <bool PASSES>
-static int atomic_emit(const sa_spadl_frame* in, const void* scratch, const sa_atomic_frame* out, void* stream) {
-  int rc = check_spadl_frame(in);
+extern "C" int sa_atomic_emit(const sa_spadl_frame* in, int32_t after_passes, const void* scratch,
+                              const sa_atomic_frame* out, void* stream) {
+  int rc = check_expand_input(in, after_passes);
   if (rc) return rc;
   if (in->n == 0) return SA_OK;
   if (!scratch || !out || !out->time_seconds || !out->x || !out->y || !out->dx || !out->dy ||
@@ -646,30 +656,13 @@ static int atomic_emit(const sa_spadl_frame* in, const void* scratch, const sa_a
       !out->bodypart_id)
     return fail(SA_EINVAL, "null scratch or output column");
   const int64_t nb = n_blocks(in->n);
-  hipLaunchKernelGGL(atomic_emit_kernel<PASSES>, dim3((unsigned)nb), dim3(AC_THREADS), 0, (hipStream_t)stream,
-                     *in, (const int64_t*)scratch, *out);
+  if (after_passes)
+    hipLaunchKernelGGL(atomic_emit_kernel<false>, dim3((unsigned)nb), dim3(AC_THREADS), 0, (hipStream_t)stream,
+                       *in, (const int64_t*)scratch, *out);
+  else
+    hipLaunchKernelGGL(atomic_emit_kernel<true>, dim3((unsigned)nb), dim3(AC_THREADS), 0, (hipStream_t)stream,
+                       *in, (const int64_t*)scratch, *out);
   return check_launch("atomic_emit_kernel");
-}
-
-extern "C" int sa_atomic_count(const sa_spadl_frame* in, void* scratch, int64_t* n_out, void* stream) {
-  return atomic_count<true>(in, scratch, n_out, stream);
-}
-
-extern "C" int sa_atomic_emit(const sa_spadl_frame* in, const void* scratch, const sa_atomic_frame* out,
-                              void* stream) {
-  return atomic_emit<true>(in, scratch, out, stream);
-}
-
-extern "C" int sa_atomic_count_after_passes(const sa_spadl_frame* in, void* scratch, int64_t* n_out,
-                                            void* stream) {
-  if (in && in->order) return fail(SA_EINVAL, "the first pass's output is sorted: order must be NULL");
-  return atomic_count<false>(in, scratch, n_out, stream);
-}
-
-extern "C" int sa_atomic_emit_after_passes(const sa_spadl_frame* in, const void* scratch,
-                                           const sa_atomic_frame* out, void* stream) {
-  if (in && in->order) return fail(SA_EINVAL, "the first pass's output is sorted: order must be NULL");
-  return atomic_emit<false>(in, scratch, out, stream);
 }
 
 static bool spadl_out_ok(const sa_spadl_out* out) {

@@ -349,7 +349,7 @@ __device__ __forceinline__ void stage_conditions(const CondSet<A>& P, const int3
   // 8-B load per row and column, all in flight before use), then column q's thresholds
   // (conditions col_start[q] .. col_start[q+1]) are balloted into the wave's 64-bit words
   const int64_t j = R0 + s < n ? R0 + s : n - 1;
-  if (N32) {  // float32 numeric blocks (sa_vaep_features_bits_f32): one 4-B load per row and column
+  if (N32) {  // float32 numeric blocks (sa_vaep_features_bits with f32): one 4-B load per row and column
     const int64_t tf = j / Bf.tile_rows, ti = j / Bi.tile_rows;
     const float* pf = (const float*)Bf.data + (tf * Bf.n_cols * Bf.tile_rows + (j - tf * Bf.tile_rows));
     const float* pi = (const float*)Bi.data + (ti * Bi.n_cols * Bi.tile_rows + (j - ti * Bi.tile_rows));

@@ -63,7 +63,7 @@ struct FeatArgs {
   int64_t* iout;
   int64_t Cb, Cf, Ci;  // columns of each block
   int64_t Rb, Rf, Ri;  // rows per tile of each block (include/socceraction_amd.h)
-  uint32_t* xt_cells;  // optional: xT cell code of every action (sa_vaep_features_xt)
+  uint32_t* xt_cells;  // optional: xT cell code of every action (sa_vaep_features with xt_cells)
   int32_t xt_l, xt_w;
   uint16_t* bbits;     // optional: bool features as bitmaps instead of bout (sa_vaep_features_bits)
   int64_t bstride;     // u16 per bitmap
@@ -81,7 +81,7 @@ struct FeatArgs {
   int32_t cond_row0;                         // bitmap row of condition 0 (after the bool columns)
   int32_t cond_n;                             // conditions (num_cond_lds_kernel stages the tables)
   // the numeric pass over rows [row0, row_end) only (row_end 0: to n); row0 a multiple of
-  // BLOCK_ACTS (sa_vaep_step_f64_chunked: one launch per chunk of the batch)
+  // BLOCK_ACTS (sa_vaep_step_f64 with chunk_rows: one launch per chunk of the batch)
   int64_t row0, row_end;
 };
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -381,7 +381,7 @@ __device__ __forceinline__ void st_i64x2(CondSink* s, int64_t col, int64_t, int6
   cond_store(s, col, (float)v0, (float)v1);
 }
 
-// float32 form of the numeric blocks (sa_vaep_features_bits_f32: what xgboost learners compare,
+// float32 form of the numeric blocks (sa_vaep_features_bits with f32: what xgboost learners compare,
 // values rounded to nearest like xgboost's own float32 conversion): 8-B stores, 512 B per wave
 // instruction
 __device__ __forceinline__ void st_f64x2(float* __restrict__ base, int64_t col, int64_t C, int64_t R,
@@ -1154,7 +1154,7 @@ constexpr int num_min_waves() {
 template <bool ATOMIC, bool EXPLICIT, int KF, bool TAIL = false, bool N32 = false, bool COND = false>
 __device__ __forceinline__ void num_features_body(const FeatArgs& args, int64_t wave_base, const sa_frame& F0,
                                                   const double* ps_in, const double* pc_in) {
-  // N32: the f64 and i64 blocks hold float32 values (sa_vaep_features_bits_f32); COND: no blocks,
+  // N32: the f64 and i64 blocks hold float32 values (sa_vaep_features_bits with f32); COND: no blocks,
   // the columns' split conditions as bitmaps (sa_vaep_features_conditions)
   using FT = typename std::conditional<COND, CondSink, typename std::conditional<N32, float, double>::type>::type;
   using IT = typename std::conditional<COND, CondSink, typename std::conditional<N32, float, int64_t>::type>::type;
@@ -1927,11 +1927,11 @@ struct TailArgs {  // labels + f64 formula riding in the numeric pass (sa_vaep_s
   uint8_t *sc, *co, *gfs;
   const double *ps, *pc;
   double *off, *def, *val;
-  int64_t chunk;     // > 0: the numeric pass in launches of `chunk` rows (sa_vaep_step_f64_chunked)
+  int64_t chunk;     // > 0: the numeric pass in launches of `chunk` rows (sa_vaep_step_f64's chunk_rows)
   int32_t prefetch;  // each chunk's inputs read into the Infinity Cache first
 };
 
-// sa_vaep_step_f64_chunked's probe of the numeric pass's read / write turnaround: rows [r0, r1)'s
+// The chunked sa_vaep_step_f64's probe of the numeric pass's read / write turnaround: rows [r0, r1)'s
 // inputs (coordinates, time, ids, team codes, probabilities: 64 B per row) read once with the
 // default cache policy, so the Infinity Cache holds them when the pass over the chunk runs --
 // the chunk's HBM reads happen in one pure-read burst instead of inside the pass's write stream.
@@ -2132,12 +2132,12 @@ static int launch_features(const sa_actions* a, const sa_feature_plan* plan, con
         SA_NUM_LAUNCH(grid, true, false, 3, false, false, true);
       else
         SA_NUM_LAUNCH(grid, false, false, 3, false, false, true);
-    } else if (q.num32) {  // windowed, K <= 3 (checked by sa_vaep_features_bits_f32)
+    } else if (q.num32) {  // windowed, K <= 3 (checked by sa_vaep_features_bits)
       if (atomic)
         SA_NUM_LAUNCH(grid, true, false, 3, false, true);
       else
         SA_NUM_LAUNCH(grid, false, false, 3, false, true);
-    } else if (tail && tail->chunk > 0 && !atomic) {  // sa_vaep_step_f64_chunked (probe)
+    } else if (tail && tail->chunk > 0 && !atomic) {  // sa_vaep_step_f64 with chunk_rows (probe)
       for (int64_t c0 = 0; c0 < a->n; c0 += tail->chunk) {
         const int64_t c1 = c0 + tail->chunk < a->n ? c0 + tail->chunk : a->n;
         if (tail->prefetch) {
@@ -2180,44 +2180,27 @@ static int launch_features(const sa_actions* a, const sa_feature_plan* plan, con
 
 extern "C" int sa_vaep_features(const sa_actions* a, const sa_feature_plan* plan,
                                 const sa_block* bool_out, const sa_block* f64_out,
-                                const sa_block* i64_out, void* stream) {
-  const FeatReq q{bool_out, f64_out, i64_out};
-  return launch_features(a, plan, q, stream);
-}
-
-extern "C" int sa_vaep_features_xt(const sa_actions* a, const sa_feature_plan* plan,
-                                   const sa_block* bool_out, const sa_block* f64_out,
-                                   const sa_block* i64_out, int32_t xt_l, int32_t xt_w,
-                                   uint32_t* xt_cells, void* stream) {
+                                const sa_block* i64_out, int32_t xt_l, int32_t xt_w, uint32_t* xt_cells,
+                                void* stream) {
+  if (!xt_cells) return launch_features(a, plan, FeatReq{bool_out, f64_out, i64_out}, stream);
   if (!a) return fail(SA_EINVAL, "null sa_actions");
   if (a->atomic || a->n_frames != 1) return fail(SA_EINVAL, "xT cells need SPADL actions in windowed mode");
   if (xt_l < 1 || xt_w < 1 || (int64_t)xt_l * xt_w > SA_XT_CELLS_MAX_C)
     return fail(SA_EINVAL, "xT cell codes need 1 <= l * w <= %d", SA_XT_CELLS_MAX_C);
-  if (!xt_cells || !aligned16(xt_cells)) return fail(SA_EINVAL, "xt_cells must be 16-byte aligned");
-  const FeatReq q{bool_out, f64_out, i64_out, xt_l, xt_w, xt_cells};
-  return launch_features(a, plan, q, stream);
+  if (!aligned16(xt_cells)) return fail(SA_EINVAL, "xt_cells must be 16-byte aligned");
+  return launch_features(a, plan, FeatReq{bool_out, f64_out, i64_out, xt_l, xt_w, xt_cells}, stream);
 }
 
 extern "C" int sa_vaep_features_bits(const sa_actions* a, const sa_feature_plan* plan, uint8_t* bool_bits,
-                                     int64_t bits_stride, int32_t n_bool_cols, const sa_block* f64_out,
-                                     const sa_block* i64_out, void* stream) {
+                                     int64_t bits_stride, int32_t n_bool_cols, int32_t f32,
+                                     const sa_block* f64_out, const sa_block* i64_out, void* stream) {
   if (!a) return fail(SA_EINVAL, "null sa_actions");
   if (int rc = check_bool_bits(a->n, bool_bits, bits_stride, n_bool_cols)) return rc;
   if (a->n_frames != 1) return fail(SA_EINVAL, "bool bitmaps: windowed mode only");
-  const FeatReq q{nullptr, f64_out, i64_out, 0, 0, nullptr, bool_bits, bits_stride, n_bool_cols};
-  return launch_features(a, plan, q, stream);
-}
-
-extern "C" int sa_vaep_features_bits_f32(const sa_actions* a, const sa_feature_plan* plan, uint8_t* bool_bits,
-                                         int64_t bits_stride, int32_t n_bool_cols, const sa_block* f32_out,
-                                         const sa_block* i32f_out, void* stream) {
-  if (!a) return fail(SA_EINVAL, "null sa_actions");
-  if (int rc = check_bool_bits(a->n, bool_bits, bits_stride, n_bool_cols)) return rc;
-  if (a->n_frames != 1) return fail(SA_EINVAL, "bool bitmaps: windowed mode only");
-  if (!plan || plan->nb_prev_actions > 3)
-    return fail(SA_EINVAL, "float32 numeric blocks: nb_prev_actions <= 3 (use sa_vaep_features_bits)");
-  FeatReq q{nullptr, f32_out, i32f_out, 0, 0, nullptr, bool_bits, bits_stride, n_bool_cols};
-  q.num32 = true;
+  if (f32 && (!plan || plan->nb_prev_actions > 3))
+    return fail(SA_EINVAL, "float32 numeric blocks: nb_prev_actions <= 3 (use f32 = 0)");
+  FeatReq q{nullptr, f64_out, i64_out, 0, 0, nullptr, bool_bits, bits_stride, n_bool_cols};
+  q.num32 = f32 != 0;
   return launch_features(a, plan, q, stream);
 }
 
@@ -2250,18 +2233,35 @@ extern "C" int sa_vaep_features_conditions(const sa_actions* a, const sa_feature
   return launch_features(a, plan, q, stream);
 }
 
+template <typename T>
+static int launch_labels_formula(const sa_actions* a, int32_t nr_actions, uint8_t* scores,
+                                 uint8_t* concedes, uint8_t* goal_from_shot, int64_t ld, const T* ps,
+                                 const T* pc, T* off, T* def, T* val, void* stream);
+
 extern "C" int sa_vaep_step_f64(const sa_actions* a, const sa_feature_plan* plan, const sa_block* bool_out,
                                 const sa_block* f64_out, const sa_block* i64_out, int32_t xt_l, int32_t xt_w,
                                 uint32_t* xt_cells, int32_t nr_actions, uint8_t* scores, uint8_t* concedes,
                                 uint8_t* goal_from_shot, int64_t ld, const double* p_scores,
                                 const double* p_concedes, double* off, double* def, double* val,
-                                void* stream) {
+                                int64_t chunk_rows, int32_t prefetch, void* stream) {
+  if (chunk_rows != 0) {  // the chunked numeric pass: the fused SPADL form only
+    if (chunk_rows < 0 || chunk_rows % BLOCK_ACTS != 0)
+      return fail(SA_EINVAL, "chunk_rows must be a non-negative multiple of %d", BLOCK_ACTS);
+    if (!a || a->atomic || !plan || plan->nb_prev_actions > 3 || nr_actions < 1 || nr_actions > SA_STEP_MAX_NR ||
+        !p_scores || !p_concedes)
+      return fail(SA_EINVAL, "the chunked step takes the fused SPADL step form with probabilities");
+    if (bool_out && bool_out->n_cols > 0) {
+      for (int x = 0; x < SA_XFN_COUNT; ++x)
+        if (plan->bool_col[x] >= 0) return fail(SA_EINVAL, "the chunked step is the numeric pass only");
+    }
+  }
   int rc = check_actions(a, false);
   if (rc) return rc;
   if (!plan) return fail(SA_EINVAL, "null plan");
   if (nr_actions < 1) return fail(SA_EINVAL, "nr_actions must be >= 1");
   if ((rc = check_label_outputs(a->n, scores, concedes, goal_from_shot, ld))) return rc;
-  const bool formula = p_scores || p_concedes || off || def || val;  // all NULL: labels only
+  // all NULL: labels only (never with chunk_rows: its probabilities make the output checks apply)
+  const bool formula = p_scores || p_concedes || off || def || val;
   if (formula && (rc = check_formula_args(p_scores, p_concedes, off, def, val, "round_up(n, 16)"))) return rc;
   if (xt_cells) {
     if (a->atomic) return fail(SA_EINVAL, "xT cells need SPADL actions");
@@ -2277,44 +2277,11 @@ extern "C" int sa_vaep_step_f64(const sa_actions* a, const sa_feature_plan* plan
   if (a->atomic || plan->nb_prev_actions > 3 || nr_actions > SA_STEP_MAX_NR) {
     if ((rc = launch_features(a, plan, q, stream))) return rc;
     if (!formula) return sa_vaep_labels(a, nr_actions, scores, concedes, goal_from_shot, ld, stream);
-    return sa_vaep_labels_formula_f64(a, nr_actions, scores, concedes, goal_from_shot, ld, p_scores,
-                                      p_concedes, off, def, val, stream);
+    return launch_labels_formula<double>(a, nr_actions, scores, concedes, goal_from_shot, ld, p_scores,
+                                         p_concedes, off, def, val, stream);
   }
-  const TailArgs t{nr_actions, scores, concedes, goal_from_shot, p_scores, p_concedes, off, def, val, 0, 0};
-  q.tail = &t;
-  return launch_features(a, plan, q, stream);
-}
-
-extern "C" int sa_vaep_step_f64_chunked(const sa_actions* a, const sa_feature_plan* plan, const sa_block* bool_out,
-                                        const sa_block* f64_out, const sa_block* i64_out, int32_t xt_l, int32_t xt_w,
-                                        uint32_t* xt_cells, int32_t nr_actions, uint8_t* scores, uint8_t* concedes,
-                                        uint8_t* goal_from_shot, int64_t ld, const double* p_scores,
-                                        const double* p_concedes, double* off, double* def, double* val,
-                                        int64_t chunk_rows, int32_t prefetch, void* stream) {
-  if (chunk_rows < 0 || chunk_rows % BLOCK_ACTS != 0)
-    return fail(SA_EINVAL, "chunk_rows must be a non-negative multiple of %d", BLOCK_ACTS);
-  if (!a || a->atomic || !plan || plan->nb_prev_actions > 3 || nr_actions < 1 || nr_actions > SA_STEP_MAX_NR ||
-      !p_scores || !p_concedes)
-    return fail(SA_EINVAL, "the chunked step takes the fused SPADL step form with probabilities");
-  if (bool_out && bool_out->n_cols > 0) {
-    for (int x = 0; x < SA_XFN_COUNT; ++x)
-      if (plan->bool_col[x] >= 0) return fail(SA_EINVAL, "the chunked step is the numeric pass only");
-  }
-  if (chunk_rows == 0)
-    return sa_vaep_step_f64(a, plan, bool_out, f64_out, i64_out, xt_l, xt_w, xt_cells, nr_actions, scores, concedes,
-                            goal_from_shot, ld, p_scores, p_concedes, off, def, val, stream);
-  int rc = check_actions(a, false);
-  if (rc) return rc;
-  if (ld % 16 != 0 || ld < ((a->n + 15) / 16) * 16)
-    return fail(SA_EINVAL, "ld must be a multiple of 16 and >= round_up(n, 16)");
-  if (!aligned16(scores) || !aligned16(concedes) || !aligned16(goal_from_shot) || !off || !def || !val ||
-      !aligned16(off) || !aligned16(def) || !aligned16(val))
-    return fail(SA_EINVAL, "label / formula outputs: non-null, 16-byte aligned");
-  if (xt_cells && (xt_l < 1 || xt_w < 1 || (int64_t)xt_l * xt_w > SA_XT_CELLS_MAX_C || !aligned16(xt_cells)))
-    return fail(SA_EINVAL, "bad xT cell code arguments");
   const TailArgs t{nr_actions, scores, concedes, goal_from_shot, p_scores, p_concedes, off, def, val, chunk_rows,
                    prefetch};
-  FeatReq q{bool_out, f64_out, i64_out, xt_l, xt_w, xt_cells};
   q.tail = &t;
   return launch_features(a, plan, q, stream);
 }
@@ -2376,15 +2343,14 @@ static int launch_formula(const sa_actions* a, const T* ps, const T* pc, T* off,
   return check_launch("formula_kernel");
 }
 
-extern "C" int sa_vaep_formula_f64(const sa_actions* a, const double* p_scores,
-                                   const double* p_concedes, double* off, double* def, double* val,
-                                   void* stream) {
-  return launch_formula<double>(a, p_scores, p_concedes, off, def, val, stream);
-}
-
-extern "C" int sa_vaep_formula_f32(const sa_actions* a, const float* p_scores, const float* p_concedes,
-                                   float* off, float* def, float* val, void* stream) {
-  return launch_formula<float>(a, p_scores, p_concedes, off, def, val, stream);
+extern "C" int sa_vaep_formula(const sa_actions* a, int32_t f32, const void* p_scores, const void* p_concedes,
+                               void* off, void* def, void* val, void* stream) {
+  if (f32 != 0 && f32 != 1) return fail(SA_EINVAL, "f32 must be 0 or 1");
+  if (f32)
+    return launch_formula<float>(a, (const float*)p_scores, (const float*)p_concedes, (float*)off, (float*)def,
+                                 (float*)val, stream);
+  return launch_formula<double>(a, (const double*)p_scores, (const double*)p_concedes, (double*)off,
+                                (double*)def, (double*)val, stream);
 }
 
 template <typename T>
@@ -2410,18 +2376,16 @@ static int launch_labels_formula(const sa_actions* a, int32_t nr_actions, uint8_
   return check_launch("labels_formula_kernel");
 }
 
-extern "C" int sa_vaep_labels_formula_f64(const sa_actions* a, int32_t nr_actions, uint8_t* scores,
-                                          uint8_t* concedes, uint8_t* goal_from_shot, int64_t ld,
-                                          const double* p_scores, const double* p_concedes, double* off,
-                                          double* def, double* val, void* stream) {
-  return launch_labels_formula<double>(a, nr_actions, scores, concedes, goal_from_shot, ld, p_scores,
-                                       p_concedes, off, def, val, stream);
-}
-
-extern "C" int sa_vaep_labels_formula_f32(const sa_actions* a, int32_t nr_actions, uint8_t* scores,
-                                          uint8_t* concedes, uint8_t* goal_from_shot, int64_t ld,
-                                          const float* p_scores, const float* p_concedes, float* off,
-                                          float* def, float* val, void* stream) {
-  return launch_labels_formula<float>(a, nr_actions, scores, concedes, goal_from_shot, ld, p_scores,
-                                      p_concedes, off, def, val, stream);
+extern "C" int sa_vaep_labels_formula(const sa_actions* a, int32_t nr_actions, uint8_t* scores,
+                                      uint8_t* concedes, uint8_t* goal_from_shot, int64_t ld, int32_t f32,
+                                      const void* p_scores, const void* p_concedes, void* off, void* def,
+                                      void* val, void* stream) {
+  if (f32 != 0 && f32 != 1) return fail(SA_EINVAL, "f32 must be 0 or 1");
+  if (f32)
+    return launch_labels_formula<float>(a, nr_actions, scores, concedes, goal_from_shot, ld,
+                                        (const float*)p_scores, (const float*)p_concedes, (float*)off,
+                                        (float*)def, (float*)val, stream);
+  return launch_labels_formula<double>(a, nr_actions, scores, concedes, goal_from_shot, ld,
+                                       (const double*)p_scores, (const double*)p_concedes, (double*)off,
+                                       (double*)def, (double*)val, stream);
 }

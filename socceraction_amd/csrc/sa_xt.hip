@@ -95,7 +95,7 @@ __device__ __forceinline__ void count_one(const XtAct& a, int C, uint32_t* hs, u
 }
 
 // CELLS = false: reads the actions' coordinates and ids (34 B per action) and may write each
-// action's rate operand (`codes`, sa_xt_count_codes).  CELLS = true: reads the 4-B cell codes a
+// action's rate operand (`codes` of sa_xt_count).  CELLS = true: reads the 4-B cell codes a
 // producer wrote (sa_xt_count_cells).
 template <int MODE, bool CELLS>
 __global__ __launch_bounds__(XT_WIDE_THREADS) void xt_count_kernel(sa_actions A, const uint32_t* __restrict__ cells,
@@ -975,11 +975,6 @@ __global__ __launch_bounds__(256) void xt_rate_cells_kernel(const uint32_t* __re
 // ================================== C ABI =================================================
 using namespace sa;
 
-extern "C" int sa_xt_count(const sa_actions* a, int32_t l, int32_t w, int64_t* shot, int64_t* goal,
-                           int64_t* move, int32_t* trans, int32_t* err_flags, void* stream) {
-  return sa_xt_count_codes(a, l, w, shot, goal, move, trans, err_flags, nullptr, 0, stream);
-}
-
 // Which count pass a grid of C cells and a batch of n actions take (host only; what
 // sa_xt_count_mode reports).  XC_WIDE while 3C + C*C u32 bins fit 150 KB of LDS (C <= 194), unless
 // SA_XT_COUNT_SHARED: the pass runs next to other kernels (bench.py's side stream), so use the
@@ -1057,9 +1052,9 @@ static int launch_count(const sa_actions& A, const uint32_t* cells, int64_t n, i
   return check_launch("xt_count_kernel");
 }
 
-extern "C" int sa_xt_count_codes(const sa_actions* a, int32_t l, int32_t w, int64_t* shot,
-                                 int64_t* goal, int64_t* move, int32_t* trans, int32_t* err_flags,
-                                 uint32_t* codes, int32_t flags, void* stream) {
+extern "C" int sa_xt_count(const sa_actions* a, int32_t l, int32_t w, int64_t* shot, int64_t* goal,
+                           int64_t* move, int32_t* trans, int32_t* err_flags, uint32_t* codes, int32_t flags,
+                           void* stream) {
   if (!a || a->n < 0) return fail(SA_EINVAL, "bad sa_actions");
   if (int rc = check_grid(l, w)) return rc;
   if (!shot || !goal || !move || !trans || !err_flags) return fail(SA_EINVAL, "null output");
@@ -1147,15 +1142,7 @@ extern "C" int sa_xt_solve_async(const int64_t* shot, const int64_t* goal, const
   return launch_small_solve(trans_t, gs, gs + C, C, eps, max_iter, heatmaps, mats + 3 * C, n_iter_dev, st);
 }
 
-extern "C" int sa_xt_solve(const int64_t* shot, const int64_t* goal, const int64_t* move,
-                           const int32_t* trans, int32_t l, int32_t w, double eps, int32_t max_iter,
-                           double* mats, double* trans_t, double* heatmaps, int32_t* n_iter,
-                           void* stream) {
-  return sa_xt_solve_ex(shot, goal, move, trans, l, w, eps, max_iter, 0, mats, trans_t, heatmaps, n_iter, nullptr,
-                        nullptr, nullptr, stream);
-}
-
-// The three solves of sa_xt_solve_ex.  Each leaves the iterates in `heat`, the surface in `xt`
+// The three solves of sa_xt_solve.  Each leaves the iterates in `heat`, the surface in `xt`
 // and *n_iter = the iteration count or -1, and returns with the stream synchronised.
 static int copy_surface(const double* heat, int n_iter, int max_iter, int C, double* xt, hipStream_t st) {
   const int last = n_iter < 0 ? max_iter : n_iter;
@@ -1175,7 +1162,7 @@ static int solve_small(const double* trans_t, const double* gs, const double* pm
 }
 
 // Up to the compact form's limit (sa_xt_large.hip): over the compact rows, [ell | row_len]
-// prebuilt by the count (sa_xt_count_from_buckets_ex) or built here; reordered under the error
+// prebuilt by the count (sa_xt_count_from_buckets) or built here; reordered under the error
 // bound or in the reference's order (*path).  heat row 0 is zero already.
 static int solve_compact(const int32_t* trans, const int64_t* move, const double* gs, const double* pmove, int C,
                          double eps, int max_iter, int flags, const uint32_t* ell, const int32_t* row_len,
@@ -1209,11 +1196,11 @@ static int solve_dense(const int32_t* trans, const int64_t* move, const double* 
   return rc ? rc : copy_surface(heat, *n_iter, max_iter, C, xt, st);
 }
 
-// sa_xt_solve_ex, with the hook of the fused fit + rate (sa_internal.h: SolveHook).
-static int solve_ex(const int64_t* shot, const int64_t* goal, const int64_t* move, const int32_t* trans, int32_t l,
-                    int32_t w, double eps, int32_t max_iter, int32_t flags, double* mats, double* trans_t,
-                    double* heatmaps, int32_t* n_iter, int32_t* path, const uint32_t* ell_in,
-                    const int32_t* row_len_in, void* stream, SolveHook* hook) {
+// sa_xt_solve, with the hook of the fused fit + rate (sa_internal.h: SolveHook).
+static int solve_hooked(const int64_t* shot, const int64_t* goal, const int64_t* move, const int32_t* trans, int32_t l,
+                        int32_t w, double eps, int32_t max_iter, int32_t flags, double* mats, double* trans_t,
+                        double* heatmaps, int32_t* n_iter, int32_t* path, const uint32_t* ell_in,
+                        const int32_t* row_len_in, void* stream, SolveHook* hook) {
   if (int rc = check_grid(l, w)) return rc;
   if (max_iter < 0) return fail(SA_EINVAL, "bad max_iter");
   const int C = l * w;
@@ -1251,12 +1238,12 @@ static int solve_ex(const int64_t* shot, const int64_t* goal, const int64_t* mov
   return rc;
 }
 
-extern "C" int sa_xt_solve_ex(const int64_t* shot, const int64_t* goal, const int64_t* move,
-                              const int32_t* trans, int32_t l, int32_t w, double eps, int32_t max_iter,
-                              int32_t flags, double* mats, double* trans_t, double* heatmaps, int32_t* n_iter,
-                              int32_t* path, const uint32_t* ell_in, const int32_t* row_len_in, void* stream) {
-  return solve_ex(shot, goal, move, trans, l, w, eps, max_iter, flags, mats, trans_t, heatmaps, n_iter, path, ell_in,
-                  row_len_in, stream, nullptr);
+extern "C" int sa_xt_solve(const int64_t* shot, const int64_t* goal, const int64_t* move,
+                           const int32_t* trans, int32_t l, int32_t w, double eps, int32_t max_iter,
+                           int32_t flags, double* mats, double* trans_t, double* heatmaps, int32_t* n_iter,
+                           int32_t* path, const uint32_t* ell_in, const int32_t* row_len_in, void* stream) {
+  return solve_hooked(shot, goal, move, trans, l, w, eps, max_iter, flags, mats, trans_t, heatmaps, n_iter, path,
+                      ell_in, row_len_in, stream, nullptr);
 }
 
 extern "C" int sa_xt_interp_grid(const double* xT, const double* cx, const double* cy, int32_t l,
@@ -1363,10 +1350,10 @@ static int check_rate_sets(int nsets, const uint64_t* const* codes, const int64_
   return SA_OK;
 }
 
-extern "C" int sa_xt_rate_interp_codes_many(int32_t nsets, const uint64_t* const* interp_codes, const int64_t* n,
-                                            const double* xT, const double* cx, const double* cy, int32_t l, int32_t w,
-                                            const double* xs, int32_t L, const double* ys, int32_t W,
-                                            double* const* out, int32_t* err_flags, void* stream) {
+extern "C" int sa_xt_rate_interp_codes(int32_t nsets, const uint64_t* const* interp_codes, const int64_t* n,
+                                       const double* xT, const double* cx, const double* cy, int32_t l, int32_t w,
+                                       const double* xs, int32_t L, const double* ys, int32_t W,
+                                       double* const* out, int32_t* err_flags, void* stream) {
   if (!xT || !cx || !cy || !xs || !ys || L < 1 || W < 1) return fail(SA_EINVAL, "bad xt_rate_interp_codes args");
   if (l < 2 || w < 2) return fail(SA_EINVAL, "interpolation needs at least 2 cells per axis");
   if ((int64_t)L * W > INT32_MAX) return fail(SA_EINVAL, "interpolated grid too large");
@@ -1395,8 +1382,8 @@ extern "C" int sa_xt_rate_interp_codes_many(int32_t nsets, const uint64_t* const
   return SA_OK;
 }
 
-// ExpectedThreat.fit + rate(use_interpolation=True) of the same actions in one call: sa_xt_solve_ex
-// (no transposed matrix) then sa_xt_rate_interp_codes_many over the surface it wrote.  Above the
+// ExpectedThreat.fit + rate(use_interpolation=True) of the same actions in one call: sa_xt_solve
+// (no transposed matrix) then sa_xt_rate_interp_codes over the surface it wrote.  Above the
 // small-grid limit the rate is queued right behind the one-launch reordered solve, before the
 // host waits for the solve's status -- no host round trip between the two; when the status
 // sends the solve to another path (the reference's order: a decision inside the bound, a
@@ -1411,28 +1398,21 @@ extern "C" int sa_xt_fit_rate_interp_codes(const int64_t* shot, const int64_t* g
   if (int rc = check_grid(l, w)) return rc;
   if (!mats || !path) return fail(SA_EINVAL, "null mats / path");
   if (l * w <= XT_SOLVE_MAX_C) return fail(SA_EINVAL, "the fused fit + rate is for grids above %d cells", XT_SOLVE_MAX_C);
-  // the rate's arguments checked before anything is launched (sa_xt_rate_interp_codes_many's own
+  // the rate's arguments checked before anything is launched (sa_xt_rate_interp_codes' own
   // checks would first run behind the solve)
   if (!cx || !cy || !xs || !ys || L < 1 || W < 1 || l < 2 || w < 2 || (int64_t)L * W > INT32_MAX)
     return fail(SA_EINVAL, "bad rate arguments");
   int64_t most_n = 0;
   if (int rc = check_rate_sets(nsets, interp_codes, n, out, &most_n)) return rc;
   auto rate = [&]() {  // over the surface in mats[3]
-    return sa_xt_rate_interp_codes_many(nsets, interp_codes, n, mats + 3 * (int64_t)(l * w), cx, cy, l, w, xs, L, ys, W,
-                                        out, err_flags, stream);
+    return sa_xt_rate_interp_codes(nsets, interp_codes, n, mats + 3 * (int64_t)(l * w), cx, cy, l, w, xs, L, ys, W,
+                                   out, err_flags, stream);
   };
   SolveHook hook{[](void* p) { return (*static_cast<decltype(rate)*>(p))(); }, &rate, false};
-  if (int rc = solve_ex(shot, goal, move, trans, l, w, eps, max_iter, flags, mats, nullptr, heatmaps, n_iter, path, ell,
-                        row_len, stream, &hook))
+  if (int rc = solve_hooked(shot, goal, move, trans, l, w, eps, max_iter, flags, mats, nullptr, heatmaps, n_iter, path,
+                            ell, row_len, stream, &hook))
     return rc;
   return !hook.ran || *path != SA_XT_PATH_REORDERED ? rate() : SA_OK;  // the surface the solve returned
-}
-
-extern "C" int sa_xt_rate_interp_codes(const uint64_t* interp_codes, int64_t n, const double* xT, const double* cx,
-                                       const double* cy, int32_t l, int32_t w, const double* xs, int32_t L,
-                                       const double* ys, int32_t W, double* out, int32_t* err_flags, void* stream) {
-  if (n < 0 || (n > 0 && (!interp_codes || !out))) return fail(SA_EINVAL, "bad xt_rate_interp_codes args");
-  return sa_xt_rate_interp_codes_many(1, &interp_codes, &n, xT, cx, cy, l, w, xs, L, ys, W, &out, err_flags, stream);
 }
 
 extern "C" int sa_xt_probabilities(const int64_t* shot, const int64_t* goal, const int64_t* move, int32_t C,

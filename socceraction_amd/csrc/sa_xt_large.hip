@@ -144,7 +144,7 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t m) {
 }
 
 // Per-action rate operands the coordinate pass can write while it holds the coordinates:
-// codes = sa_xt_count_codes' u32 operand of a rate on the (l, w) grid; icodes = the u64 operand
+// codes = sa_xt_count's u32 operand of a rate on the (l, w) grid; icodes = the u64 operand
 // of a rate(use_interpolation=True) on the L x W node grid (start node | end node << 32 of a
 // successful move, XT_ICODE_BAD / XT_ICODE_NAN as rate_code's markers).
 struct XkRate {
@@ -482,7 +482,7 @@ __device__ __forceinline__ void xe_emit_tail(uint32_t* __restrict__ E, const uin
 // skips its build pass and its 204 MB read of the table.  dense = 0 (with ell): the dense rows
 // are written only for a band that holds a transition count >= 65535 (the one entry the compact
 // form escapes to its dense row); every other band's dense rows stay unwritten -- 204 MB of
-// stores a fit that reads only the compact rows does not need (sa_xt_count_from_buckets_ex
+// stores a fit that reads only the compact rows does not need (sa_xt_count_from_buckets
 // with SA_XT_COUNT_COMPACT_ONLY).
 __device__ __forceinline__ int xe_slot(int k);
 __global__ __launch_bounds__(XB_THREADS) void xt_band_count_kernel(XbSets sets, XbShape S, int band0,
@@ -1457,8 +1457,8 @@ static int count_from_buckets(int nsets, const xb_key_t* const* buckets, const i
   return SA_OK;
 }
 
-// The whole band-owned count of one batch (sa_xt_count / sa_xt_count_codes / sa_xt_count_cells
-// for grids the band path holds): buckets in scratch, added into the caller's counts.
+// The whole band-owned count of one batch (sa_xt_count / sa_xt_count_cells for grids the band
+// path holds): buckets in scratch, added into the caller's counts.
 int xt_count_bands(const sa_actions& A, const uint32_t* cells, int64_t n, int l, int w, int64_t* shot,
                    int64_t* goal, int64_t* move, int32_t* trans, int32_t* err, uint32_t* codes, hipStream_t st) {
   XbShape S;
@@ -1475,7 +1475,7 @@ int xt_count_bands(const sa_actions& A, const uint32_t* cells, int64_t n, int l,
 }
 
 // The compact form of count rows (ell | row_len) and one value iteration over it, for grids of
-// up to XE_XMAX cells: sa_xt_solve_ex above SA_XT_SOLVE_MAX_C cells, sa_xt_compact_rows,
+// up to XE_XMAX cells: sa_xt_solve above SA_XT_SOLVE_MAX_C cells, sa_xt_compact_rows,
 // sa_xt_iterate_compact and the row-sharded solve.
 bool xt_compact_ok(int C) { return C >= 1 && C <= XE_XMAX; }
 size_t xt_compact_bytes(int C, int nrows) { return (size_t)(nrows > 0 ? nrows : 0) * (size_t)xe_pitch(C) * 4; }
@@ -1659,15 +1659,7 @@ extern "C" int sa_xt_count_bucket(const sa_actions* a, const uint32_t* cells, in
 
 extern "C" int sa_xt_count_from_buckets(int32_t nsets, const uint16_t* const* buckets, const int64_t* const* band_off,
                                         int32_t l, int32_t w, int64_t* shot, int64_t* goal, int64_t* move,
-                                        int32_t* trans, int32_t flags, void* stream) {
-  return sa_xt_count_from_buckets_ex(nsets, buckets, band_off, l, w, shot, goal, move, trans, flags, nullptr, nullptr,
-                                     stream);
-}
-
-extern "C" int sa_xt_count_from_buckets_ex(int32_t nsets, const uint16_t* const* buckets,
-                                           const int64_t* const* band_off, int32_t l, int32_t w, int64_t* shot,
-                                           int64_t* goal, int64_t* move, int32_t* trans, int32_t flags,
-                                           uint32_t* ell, int32_t* row_len, void* stream) {
+                                        int32_t* trans, int32_t flags, uint32_t* ell, int32_t* row_len, void* stream) {
   XbShape S;
   if (int rc = band_grid(l, w, &S)) return rc;
   if (int rc = check_bucket_sets(nsets, buckets, band_off)) return rc;

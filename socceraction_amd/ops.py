@@ -213,19 +213,14 @@ def _ptr(t: Optional[torch.Tensor]):
 def features_into(s: _native.SaActions, out: FeatureBlocks, xt_cells: Optional[tuple] = None) -> None:
     """Launch the feature kernels into ``out``. ``xt_cells = (l, w, cells)``: the same pass also
     writes every action's xT cell code for a fit + rate on the (l, w) grid
-    (``sa_vaep_features_xt``; ``cells`` from :func:`xt_cells_buffer`)."""
+    (``sa_vaep_features``' ``xt_cells``; ``cells`` from :func:`xt_cells_buffer`)."""
     bb, fb, ib = out.sa_blocks()
-    if xt_cells is None:
-        _native.check(_native.lib().sa_vaep_features(
-            ctypes.byref(s), ctypes.byref(out.plan.struct), ctypes.byref(bb), ctypes.byref(fb),
-            ctypes.byref(ib), stream_handle()))
-    else:
-        l, w, cells = xt_cells
-        if cells.dtype != torch.int32 or cells.numel() < s.n:
-            raise ValueError('cells must be an int32 tensor of at least n elements')
-        _native.check(_native.lib().sa_vaep_features_xt(
-            ctypes.byref(s), ctypes.byref(out.plan.struct), ctypes.byref(bb), ctypes.byref(fb),
-            ctypes.byref(ib), int(l), int(w), _ptr(cells), stream_handle()))
+    l, w, cells = xt_cells if xt_cells is not None else (0, 0, None)
+    if cells is not None and (cells.dtype != torch.int32 or cells.numel() < s.n):
+        raise ValueError('cells must be an int32 tensor of at least n elements')
+    _native.check(_native.lib().sa_vaep_features(
+        ctypes.byref(s), ctypes.byref(out.plan.struct), ctypes.byref(bb), ctypes.byref(fb),
+        ctypes.byref(ib), int(l), int(w), _ptr(cells), stream_handle()))
 
 
 def features(batch: ActionBatch, xfns: Sequence[str], k: int, flip: bool = True,
@@ -235,7 +230,7 @@ def features(batch: ActionBatch, xfns: Sequence[str], k: int, flip: bool = True,
     """Game-state features of every segment of ``batch`` (windowed mode). ``bool_bits``: the
     bool features as bitmaps (``sa_vaep_features_bits``; 64 instead of 515 B/action written:
     what the staged tree walk of the on-device ``VAEP.rate`` reads). ``num32`` (with
-    ``bool_bits``, k <= 3): the numeric blocks in float32 (``sa_vaep_features_bits_f32``: what
+    ``bool_bits``, k <= 3): the numeric blocks in float32 (its ``f32`` argument: what
     xgboost learners compare; half the numeric bytes written and staged)."""
     plan = out.plan if out is not None else build_plan(xfns, k, batch.atomic)
     if num32 and not bool_bits and out is None:
@@ -253,10 +248,9 @@ def features(batch: ActionBatch, xfns: Sequence[str], k: int, flip: bool = True,
     out = out or alloc_feature_blocks(plan, batch.n, batch.device, bool_tile, num_tile)
     if out.bool_bits is not None and out.bool_block is None:
         _, fb, ib = out.sa_blocks()
-        fn = _native.lib().sa_vaep_features_bits_f32 if out.num32 else _native.lib().sa_vaep_features_bits
-        _native.check(fn(
+        _native.check(_native.lib().sa_vaep_features_bits(
             ctypes.byref(batch.struct(flip=flip)), ctypes.byref(out.plan.struct),
-            out.bool_bits.data_ptr(), out.bool_bits.shape[1] * 8, max(plan.n_bool, 1),
+            out.bool_bits.data_ptr(), out.bool_bits.shape[1] * 8, max(plan.n_bool, 1), int(out.num32),
             ctypes.byref(fb), ctypes.byref(ib), stream_handle()))
         if batch.n % 64:  # the kernel clears rows >= n of the 16-row group holding row n - 1;
             # the last word's later groups are cleared here
@@ -327,22 +321,27 @@ def labels(batch: ActionBatch, nr_actions: int = 10, out: Optional[LabelBlocks] 
     return out
 
 
-def formula(batch: ActionBatch, p_scores: torch.Tensor, p_concedes: torch.Tensor,
-            out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """offensive / defensive / vaep value as a ``[3, ld]`` tensor of the probability dtype."""
+def _check_probabilities(n: int, p_scores: torch.Tensor, p_concedes: torch.Tensor) -> torch.dtype:
+    """The probabilities of the formula: one dtype, float32 or float64, one value per action."""
     dt = p_scores.dtype
     if dt not in (torch.float32, torch.float64) or p_concedes.dtype != dt:
         raise TypeError('probabilities must both be float32 or both float64')
-    if p_scores.numel() < batch.n or p_concedes.numel() < batch.n:
+    if p_scores.numel() < n or p_concedes.numel() < n:
         raise ValueError('one probability per action is required')
+    return dt
+
+
+def formula(batch: ActionBatch, p_scores: torch.Tensor, p_concedes: torch.Tensor,
+            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """offensive / defensive / vaep value as a ``[3, ld]`` tensor of the probability dtype."""
+    dt = _check_probabilities(batch.n, p_scores, p_concedes)
     ps, pc = p_scores.contiguous(), p_concedes.contiguous()
     if out is None:
         out = torch.empty((3, _ld(batch.n)), dtype=dt, device=batch.device)
     s = batch.struct()
-    fn = _native.lib().sa_vaep_formula_f64 if dt == torch.float64 else \
-        _native.lib().sa_vaep_formula_f32
-    _native.check(fn(ctypes.byref(s), _ptr(ps), _ptr(pc), _ptr(out[0]), _ptr(out[1]),
-                     _ptr(out[2]), stream_handle()))
+    _native.check(_native.lib().sa_vaep_formula(
+        ctypes.byref(s), int(dt == torch.float32), _ptr(ps), _ptr(pc), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+        stream_handle()))
     return out
 
 
@@ -350,11 +349,7 @@ def labels_formula(batch: ActionBatch, p_scores: torch.Tensor, p_concedes: torch
                    nr_actions: int = 10, labels_out: Optional[LabelBlocks] = None,
                    values_out: Optional[torch.Tensor] = None) -> Tuple[LabelBlocks, torch.Tensor]:
     """:func:`labels` and :func:`formula` of the same actions in one launch."""
-    dt = p_scores.dtype
-    if dt not in (torch.float32, torch.float64) or p_concedes.dtype != dt:
-        raise TypeError('probabilities must both be float32 or both float64')
-    if p_scores.numel() < batch.n or p_concedes.numel() < batch.n:
-        raise ValueError('one probability per action is required')
+    dt = _check_probabilities(batch.n, p_scores, p_concedes)
     ld = _ld(batch.n)
     if labels_out is None:
         buf = torch.empty((3, ld), dtype=torch.uint8, device=batch.device)
@@ -363,12 +358,11 @@ def labels_formula(batch: ActionBatch, p_scores: torch.Tensor, p_concedes: torch
         values_out = torch.empty((3, ld), dtype=dt, device=batch.device)
     ps, pc = p_scores.contiguous(), p_concedes.contiguous()
     s = batch.struct()
-    fn = _native.lib().sa_vaep_labels_formula_f64 if dt == torch.float64 else \
-        _native.lib().sa_vaep_labels_formula_f32
     o = values_out
-    _native.check(fn(ctypes.byref(s), int(nr_actions), _ptr(labels_out.scores),
-                     _ptr(labels_out.concedes), _ptr(labels_out.goal_from_shot), ld, _ptr(ps),
-                     _ptr(pc), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), stream_handle()))
+    _native.check(_native.lib().sa_vaep_labels_formula(
+        ctypes.byref(s), int(nr_actions), _ptr(labels_out.scores), _ptr(labels_out.concedes),
+        _ptr(labels_out.goal_from_shot), ld, int(dt == torch.float32), _ptr(ps), _ptr(pc), _ptr(o[0]), _ptr(o[1]),
+        _ptr(o[2]), stream_handle()))
     return labels_out, values_out
 
 
@@ -380,7 +374,8 @@ def step_into(s: _native.SaActions, out: FeatureBlocks, p_scores: Optional[torch
     plan (and, with ``xt_cells = (l, w, cells)``, every action's xT cell code), the labels and
     the f64 formula of the same actions -- exactly :func:`features_into` followed by
     :func:`labels_formula`, with the labels and formula computed inside the numeric pass.
-    ``p_scores = p_concedes = values_out = None``: features + labels only."""
+    ``p_scores = p_concedes = values_out = None``: features + labels only.  ``chunk_rows``: an A/B
+    probe, the numeric pass in chunks, optionally prefetched (bench --num-chunks)."""
     if p_scores is not None:
         if p_scores.dtype != torch.float64 or p_concedes.dtype != torch.float64:
             raise TypeError('the fused step takes float64 probabilities (float32: labels_formula)')
@@ -395,18 +390,11 @@ def step_into(s: _native.SaActions, out: FeatureBlocks, p_scores: Optional[torch
     if cells is not None and (cells.dtype != torch.int32 or cells.numel() < s.n):
         raise ValueError('cells must be an int32 tensor of at least n elements')
     bb, fb, ib = out.sa_blocks()
-    if chunk_rows:  # A/B probe: the numeric pass in chunks, optionally prefetched (bench --num-chunks)
-        _native.check(_native.lib().sa_vaep_step_f64_chunked(
-            ctypes.byref(s), ctypes.byref(out.plan.struct), ctypes.byref(bb), ctypes.byref(fb),
-            ctypes.byref(ib), int(l), int(w), _ptr(cells), int(nr_actions), _ptr(labels_out.scores),
-            _ptr(labels_out.concedes), _ptr(labels_out.goal_from_shot), _ld(s.n), _ptr(ps), _ptr(pc),
-            _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), int(chunk_rows), int(prefetch), stream_handle()))
-        return
     _native.check(_native.lib().sa_vaep_step_f64(
         ctypes.byref(s), ctypes.byref(out.plan.struct), ctypes.byref(bb), ctypes.byref(fb),
         ctypes.byref(ib), int(l), int(w), _ptr(cells), int(nr_actions), _ptr(labels_out.scores),
         _ptr(labels_out.concedes), _ptr(labels_out.goal_from_shot), _ld(s.n), _ptr(ps), _ptr(pc),
-        _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), stream_handle()))
+        _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), int(chunk_rows), int(prefetch), stream_handle()))
 
 
 # ------------------------------------------------------------------------------- xT
@@ -480,18 +468,11 @@ def xt_count(batch: ActionBatch, l: int, w: int, acc: Optional[XTCounts] = None,
     acc.require_dense('adding to a count')
     acc.compact = None  # the counts change
     s = batch.struct()
-    if codes is None and not shared:
-        _native.check(_native.lib().sa_xt_count(ctypes.byref(s), l, w, _ptr(acc.shot),
-                                                _ptr(acc.goal), _ptr(acc.move), _ptr(acc.trans),
-                                                _ptr(acc.err), stream_handle()))
-    else:
-        if codes is not None and (codes.dtype != torch.int32 or codes.numel() < batch.n):
-            raise ValueError('codes must be an int32 tensor of at least n elements')
-        _native.check(_native.lib().sa_xt_count_codes(ctypes.byref(s), l, w, _ptr(acc.shot),
-                                                      _ptr(acc.goal), _ptr(acc.move),
-                                                      _ptr(acc.trans), _ptr(acc.err),
-                                                      _ptr(codes), int(shared),
-                                                      stream_handle()))
+    if codes is not None and (codes.dtype != torch.int32 or codes.numel() < batch.n):
+        raise ValueError('codes must be an int32 tensor of at least n elements')
+    _native.check(_native.lib().sa_xt_count(
+        ctypes.byref(s), l, w, _ptr(acc.shot), _ptr(acc.goal), _ptr(acc.move), _ptr(acc.trans), _ptr(acc.err),
+        _ptr(codes), _native.SA_XT_COUNT_SHARED if shared else 0, stream_handle()))
     return acc
 
 
@@ -555,34 +536,13 @@ def xt_interp_codes_buffer(n: int, dev) -> torch.Tensor:
     return torch.empty(max(_ld(n), 16), dtype=torch.int64, device=dev)
 
 
-def xt_rate_interp_codes(icodes: torch.Tensor, n: int, xT: torch.Tensor, l: int, w: int,
-                         L: int = 1050, W: int = 680, axes: Optional[torch.Tensor] = None,
-                         out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """:func:`xt_rate_interp` of the actions whose bucket pass wrote ``icodes``: the same
-    values, NaN pattern and error bit, reading 8 B per action."""
-    dev = icodes.device
-    axes = xt_interp_axes(l, w, dev, L, W) if axes is None else axes
-    if axes.numel() != l + w + L + W:
-        raise ValueError('axes must hold l + w + L + W node positions')
-    out = torch.empty(max(_ld(n), 16), dtype=torch.float64, device=dev) if out is None else out
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    o = l + w
-    _native.check(_native.lib().sa_xt_rate_interp_codes(
-        _ptr(icodes), int(n), _ptr(xT.contiguous()), _ptr(axes[:l]), _ptr(axes[l:o]), l, w,
-        _ptr(axes[o:o + L]), L, _ptr(axes[o + L:]), W, _ptr(out), _ptr(err), stream_handle()))
-    return out[:n], err
-
-
-def xt_rate_interp_codes_many(icodes: Sequence[torch.Tensor], ns: Sequence[int], xT: torch.Tensor,
-                              l: int, w: int, L: int = 1050, W: int = 680,
-                              axes: Optional[torch.Tensor] = None,
-                              outs: Optional[Sequence[torch.Tensor]] = None
-                              ) -> Tuple[List[torch.Tensor], torch.Tensor]:
-    """:func:`xt_rate_interp_codes` of several batches (a fit's device batches) in one launch
-    (``sa_xt_rate_interp_codes_many``): the same values per batch, one error word for all."""
+def _rate_sets(icodes: Sequence[torch.Tensor], ns: Sequence[int], outs: Optional[Sequence[torch.Tensor]],
+               l: int, w: int, L: int, W: int, axes: Optional[torch.Tensor], dev) -> tuple:
+    """The arguments the interpolated rates from operand codes share, checked: the counts, the
+    outs (allocated when None), the node axes (kept alive by the caller until its launch) and
+    the library's ``(nsets, codes[], n[])``, ``(cx, cy)``, ``(xs, L, ys, W, out[])`` groups."""
     if len(icodes) != len(ns) or (outs is not None and len(outs) != len(ns)):
         raise ValueError('one operand buffer, count (and out) per batch')
-    dev = xT.device
     axes = xt_interp_axes(l, w, dev, L, W) if axes is None else axes
     if axes.numel() != l + w + L + W:
         raise ValueError('axes must hold l + w + L + W node positions')
@@ -595,15 +555,36 @@ def xt_rate_interp_codes_many(icodes: Sequence[torch.Tensor], ns: Sequence[int],
     for o, n in zip(outs, ns):
         if o.dtype != torch.float64 or o.numel() < n:
             raise ValueError('out must be float64 with room for n values')
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
     k = len(ns)
     cp = (ctypes.c_void_p * max(k, 1))(*[c.data_ptr() for c in icodes])
     op = (ctypes.c_void_p * max(k, 1))(*[o.data_ptr() for o in outs])
     nn = (ctypes.c_int64 * max(k, 1))(*ns)
     o = l + w
-    _native.check(_native.lib().sa_xt_rate_interp_codes_many(
-        k, cp, nn, _ptr(xT.contiguous()), _ptr(axes[:l]), _ptr(axes[l:o]), l, w,
-        _ptr(axes[o:o + L]), L, _ptr(axes[o + L:]), W, op, _ptr(err), stream_handle()))
+    return (ns, outs, axes, (k, cp, nn), (_ptr(axes[:l]), _ptr(axes[l:o])),
+            (_ptr(axes[o:o + L]), L, _ptr(axes[o + L:]), W, op))
+
+
+def xt_rate_interp_codes(icodes: torch.Tensor, n: int, xT: torch.Tensor, l: int, w: int,
+                         L: int = 1050, W: int = 680, axes: Optional[torch.Tensor] = None,
+                         out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """:func:`xt_rate_interp` of the actions whose bucket pass wrote ``icodes``: the same
+    values, NaN pattern and error bit, reading 8 B per action."""
+    outs, err = xt_rate_interp_codes_many([icodes], [n], xT, l, w, L, W, axes, None if out is None else [out])
+    return outs[0], err
+
+
+def xt_rate_interp_codes_many(icodes: Sequence[torch.Tensor], ns: Sequence[int], xT: torch.Tensor,
+                              l: int, w: int, L: int = 1050, W: int = 680,
+                              axes: Optional[torch.Tensor] = None,
+                              outs: Optional[Sequence[torch.Tensor]] = None
+                              ) -> Tuple[List[torch.Tensor], torch.Tensor]:
+    """:func:`xt_rate_interp_codes` of several batches (a fit's device batches) in one launch
+    (``sa_xt_rate_interp_codes``' sets): the same values per batch, one error word for all."""
+    dev = xT.device
+    ns, outs, axes, sets, centres, nodes = _rate_sets(icodes, ns, outs, l, w, L, W, axes, dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _native.check(_native.lib().sa_xt_rate_interp_codes(
+        *sets, _ptr(xT.contiguous()), *centres, l, w, *nodes, _ptr(err), stream_handle()))
     return [t[:n] for t, n in zip(outs, ns)], err
 
 
@@ -619,38 +600,20 @@ def xt_fit_rate_interp_codes(acc: XTCounts, icodes: Sequence[torch.Tensor], ns: 
     C, l, w = acc.C, acc.l, acc.w
     if C <= _native.SA_XT_SOLVE_MAX_C:
         raise ValueError('the fused fit + rate is for grids above SA_XT_SOLVE_MAX_C cells')
-    if len(icodes) != len(ns) or (outs is not None and len(outs) != len(ns)):
-        raise ValueError('one operand buffer, count (and out) per batch')
     if getattr(acc, 'compact', None) is None:
         acc.require_dense('xt_fit_rate_interp_codes without compact rows')
     dev = acc.shot.device
-    axes = xt_interp_axes(l, w, dev, L, W) if axes is None else axes
-    if axes.numel() != l + w + L + W:
-        raise ValueError('axes must hold l + w + L + W node positions')
-    ns = [int(n) for n in ns]
-    for c, n in zip(icodes, ns):
-        if n < 0 or c.numel() * c.element_size() < 8 * n:
-            raise ValueError('an operand buffer holds fewer than n codes')
-    outs = [torch.empty(max(_ld(n), 16), dtype=torch.float64, device=dev) for n in ns] \
-        if outs is None else list(outs)
-    for o, n in zip(outs, ns):
-        if o.dtype != torch.float64 or o.numel() < n:
-            raise ValueError('out must be float64 with room for n values')
+    ns, outs, axes, sets, centres, nodes = _rate_sets(icodes, ns, outs, l, w, L, W, axes, dev)
     mats = torch.empty((4, C), dtype=torch.float64, device=dev)
     heat = torch.empty((max_iter + 1, C), dtype=torch.float64, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    k = len(ns)
-    cp = (ctypes.c_void_p * max(k, 1))(*[c.data_ptr() for c in icodes])
-    op = (ctypes.c_void_p * max(k, 1))(*[o.data_ptr() for o in outs])
-    nn = (ctypes.c_int64 * max(k, 1))(*ns)
     n_iter, path = ctypes.c_int32(0), ctypes.c_int32(0)
     ell, rl = acc.compact if getattr(acc, 'compact', None) is not None else (None, None)
-    o = l + w
     _native.check(_native.lib().sa_xt_fit_rate_interp_codes(
         _ptr(acc.shot), _ptr(acc.goal), _ptr(acc.move), _ptr(acc.trans), l, w, float(eps),
         int(max_iter), _native.SA_XT_SOLVE_EXACT if exact_order else 0, _ptr(mats), _ptr(heat),
-        ctypes.byref(n_iter), ctypes.byref(path), _ptr(ell), _ptr(rl), k, cp, nn, _ptr(axes[:l]),
-        _ptr(axes[l:o]), _ptr(axes[o:o + L]), L, _ptr(axes[o + L:]), W, op, _ptr(err), stream_handle()))
+        ctypes.byref(n_iter), ctypes.byref(path), _ptr(ell), _ptr(rl), *sets, *centres, *nodes, _ptr(err),
+        stream_handle()))
     if n_iter.value < 0:
         raise RuntimeError(f'xT value iteration did not converge within {max_iter} iterations')
     p = _native.XT_SOLVE_PATHS[path.value]
@@ -672,7 +635,7 @@ def xt_count_buckets(parts: Sequence[XTBuckets], l: int, w: int, acc: XTCounts,
     """The once-per-fit half of the band-owned count: every batch's buckets into ``acc`` (added;
     ``overwrite``: written, the rows' old values never read).  ``compact`` (default: whenever it
     can) also writes the transition counts' compact rows for the large-grid solve
-    (``sa_xt_count_from_buckets_ex``; ``acc.compact``): overwrite, <= 24 batches and
+    (``sa_xt_count_from_buckets``' ``ell``; ``acc.compact``): overwrite, <= 24 batches and
     1025 <= C <= 9472 only.  ``dense=False`` (with the compact rows): the dense C x C table is
     not written (``SA_XT_COUNT_COMPACT_ONLY``: only the rows of bands holding a count >= 65535,
     which the compact solve reads) -- for a fit that reads the compact rows alone (the solve,
@@ -695,7 +658,7 @@ def xt_count_buckets(parts: Sequence[XTBuckets], l: int, w: int, acc: XTCounts,
     offs = (ctypes.c_void_p * max(k, 1))(*[p.band_off.data_ptr() for p in parts])
     flags = (_native.SA_XT_COUNT_OVERWRITE if overwrite else 0) | \
         (0 if dense else _native.SA_XT_COUNT_COMPACT_ONLY)
-    _native.check(_native.lib().sa_xt_count_from_buckets_ex(
+    _native.check(_native.lib().sa_xt_count_from_buckets(
         k, keys, offs, int(l), int(w), _ptr(acc.shot), _ptr(acc.goal), _ptr(acc.move),
         _ptr(acc.trans), flags, _ptr(ell), _ptr(rl), stream_handle()))
     if compact:
@@ -876,7 +839,7 @@ def xt_solve(acc: XTCounts, eps: float = 1e-5, max_iter: int = 1000,
     which the large-grid iteration never reads (408 MB at 105 x 68).  Grids above
     ``SA_XT_SOLVE_MAX_C`` cells sum each row in a fixed parallel order under an error bound that
     keeps every convergence decision, and so the iteration count, the reference's (iterates
-    within 4e-11 relative at 105 x 68; ``sa_xt_solve_ex``); ``exact_order=True`` sums in the
+    within 4e-11 relative at 105 x 68; ``sa_xt_solve``); ``exact_order=True`` sums in the
     reference's order (bit-exact iterates).  ``XTSolution.path`` says which ran."""
     C = acc.C
     dev = acc.shot.device
@@ -889,7 +852,7 @@ def xt_solve(acc: XTCounts, eps: float = 1e-5, max_iter: int = 1000,
     heat = torch.empty((max_iter + 1, C), dtype=torch.float64, device=dev)
     n_iter, path = ctypes.c_int32(0), ctypes.c_int32(0)
     ell, rl = acc.compact if getattr(acc, 'compact', None) is not None else (None, None)
-    _native.check(_native.lib().sa_xt_solve_ex(
+    _native.check(_native.lib().sa_xt_solve(
         _ptr(acc.shot), _ptr(acc.goal), _ptr(acc.move), _ptr(acc.trans), acc.l, acc.w, float(eps),
         int(max_iter), _native.SA_XT_SOLVE_EXACT if exact_order else 0, _ptr(mats), _ptr(tt),
         _ptr(heat), ctypes.byref(n_iter), ctypes.byref(path), _ptr(ell), _ptr(rl),

@@ -86,7 +86,7 @@ def test_an_empty_batch_is_not_refused_for_its_null_columns():
     for n, named in ((1, True), (0, False)):
         s = _native.SaActions()
         s.n, s.n_segments, s.n_frames, s.seg_off = n, 1, 1, 256
-        rc = lib.sa_vaep_features(ctypes.byref(s), ctypes.byref(plan), None, None, None, None)
+        rc = lib.sa_vaep_features(ctypes.byref(s), ctypes.byref(plan), None, None, None, 0, 0, None, None)
         assert rc == _native.SA_EINVAL   # a plan of depth 0: refused later, nothing is ever launched
         assert (b'null column' in lib.sa_last_error()) == named
 

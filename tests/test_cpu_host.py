@@ -30,7 +30,7 @@ def test_library_builds_and_exports_every_declared_symbol():
     for sym in declared:
         assert hasattr(lib, sym), sym
     assert set(declared) == set(_native.EXPORTED_SYMBOLS)
-    assert lib.sa_abi_version() == 5
+    assert lib.sa_abi_version() == 6
     assert lib.sa_debug_enabled() == 0
     assert lib.sa_debug_check() == 0  # default build: no device checks, no device call
 
@@ -95,7 +95,7 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     s = _native.SaActions()
     s.n, s.n_segments, s.n_frames = 10, 1, 0
     plan = _native.SaFeaturePlan()
-    rc = lib.sa_vaep_features(ctypes.byref(s), ctypes.byref(plan), None, None, None, None)
+    rc = lib.sa_vaep_features(ctypes.byref(s), ctypes.byref(plan), None, None, None, 0, 0, None, None)
     assert rc == _native.SA_EINVAL
     assert b'n_frames' in lib.sa_last_error()
     with pytest.raises(ValueError):
@@ -103,21 +103,21 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     # round-5 entry points: their argument checks too come before any HIP call
     fake = ctypes.c_void_p(256)  # never dereferenced on the host
     none_p = ctypes.POINTER(ctypes.c_void_p)()
-    rc = lib.sa_xt_count_from_buckets_ex(0, none_p, none_p, 105, 68, fake, fake, fake, fake,
-                                         _native.SA_XT_COUNT_OVERWRITE, fake, None, None)
+    rc = lib.sa_xt_count_from_buckets(0, none_p, none_p, 105, 68, fake, fake, fake, fake,
+                                      _native.SA_XT_COUNT_OVERWRITE, fake, None, None)
     assert rc == _native.SA_EINVAL and b'together' in lib.sa_last_error()
-    rc = lib.sa_xt_count_from_buckets_ex(0, none_p, none_p, 105, 68, fake, fake, fake, fake, 0,
-                                         fake, fake, None)
+    rc = lib.sa_xt_count_from_buckets(0, none_p, none_p, 105, 68, fake, fake, fake, fake, 0,
+                                      fake, fake, None)
     assert rc == _native.SA_EINVAL and b'OVERWRITE' in lib.sa_last_error()
     n_iter, path = ctypes.c_int32(0), ctypes.c_int32(0)
-    rc = lib.sa_xt_solve_ex(fake, fake, fake, fake, 16, 12, 1e-5, 100, 0, fake, fake, fake,
-                            ctypes.byref(n_iter), ctypes.byref(path), fake, fake, None)
+    rc = lib.sa_xt_solve(fake, fake, fake, fake, 16, 12, 1e-5, 100, 0, fake, fake, fake,
+                         ctypes.byref(n_iter), ctypes.byref(path), fake, fake, None)
     assert rc == _native.SA_EINVAL and b'compact' in lib.sa_last_error()
-    rc = lib.sa_xt_solve_ex(fake, fake, fake, fake, 105, 68, 1e-5, 100, 4, fake, None, fake,
-                            ctypes.byref(n_iter), ctypes.byref(path), None, None, None)
+    rc = lib.sa_xt_solve(fake, fake, fake, fake, 105, 68, 1e-5, 100, 4, fake, None, fake,
+                         ctypes.byref(n_iter), ctypes.byref(path), None, None, None)
     assert rc == _native.SA_EINVAL and b'flags' in lib.sa_last_error()
-    rc = lib.sa_xt_rate_interp_codes_many(-1, none_p, None, fake, fake, fake, 105, 68, fake, 1050,
-                                          fake, 680, none_p, fake, None)
+    rc = lib.sa_xt_rate_interp_codes(-1, none_p, None, fake, fake, fake, 105, 68, fake, 1050,
+                                     fake, 680, none_p, fake, None)
     assert rc == _native.SA_EINVAL
     # round 6: the fused fit + rate checks its grid and the rate's arguments before launching
     fit_rate = lambda l, w, nsets, L: lib.sa_xt_fit_rate_interp_codes(  # noqa: E731
@@ -137,15 +137,15 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     assert einval(band_rows(0, none_p, none_p, 105, -1, 1), b'band range')
     assert einval(band_rows(0, none_p, none_p, 105, 0, 1 << 20), b'band range')
     assert einval(band_rows(0, none_p, none_p, 0, 0, 1), b'bad l')
-    assert einval(lib.sa_xt_count_from_buckets_ex(1, ptrs(256), ptrs(None), 105, 68, fake, fake, fake, fake,
-                                                  _native.SA_XT_COUNT_OVERWRITE, None, None, None),
+    assert einval(lib.sa_xt_count_from_buckets(1, ptrs(256), ptrs(None), 105, 68, fake, fake, fake, fake,
+                                               _native.SA_XT_COUNT_OVERWRITE, None, None, None),
                   b'null band offsets')
     bucket = lambda a, l, w: lib.sa_xt_count_bucket(a, None, 0, l, w, fake, fake, fake, None, None,  # noqa: E731
                                                    0, 0, None)
     assert einval(bucket(ctypes.byref(s), 105, 68), b'null input column')  # n = 10, no columns
     assert einval(bucket(ctypes.byref(s), 0, 68), b'bad l')
     assert einval(bucket(ctypes.byref(s), 1000, 1000), b'bad l')
-    assert einval(lib.sa_xt_count_codes(ctypes.byref(s), 16, 12, fake, fake, fake, fake, fake, None, 0, None),
+    assert einval(lib.sa_xt_count(ctypes.byref(s), 16, 12, fake, fake, fake, fake, fake, None, 0, None),
                   b'null input column')
     assert einval(lib.sa_xt_compact_rows(fake, 0, 1, fake, fake, None), b'compact')
     assert einval(lib.sa_xt_compact_rows(fake, 9473, 1, fake, fake, None), b'compact')
@@ -166,13 +166,44 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     assert einval(solve_async(16, 12, -1), b'max_iter')
     assert einval(solve_async(40, 30, 100), b'asynchronous')
     # l * w is bounded in 64 bits wherever a grid comes in: 65536 * 65536 is 0 in 32 bits
-    solve_ex = lambda l, w: lib.sa_xt_solve_ex(fake, fake, fake, fake, l, w, 1e-5, 100, 0, fake, fake,  # noqa: E731
-                                               fake, ctypes.byref(n_iter), ctypes.byref(path), None, None, None)
+    solve = lambda l, w: lib.sa_xt_solve(fake, fake, fake, fake, l, w, 1e-5, 100, 0, fake, fake,  # noqa: E731
+                                         fake, ctypes.byref(n_iter), ctypes.byref(path), None, None, None)
     for l, w in ((65536, 65536), (46341, 1), (300, 300)):
-        assert einval(solve_ex(l, w), b'bad l')
+        assert einval(solve(l, w), b'bad l')
         assert einval(solve_async(l, w, 100), b'bad l')
         assert einval(normalize(l, w), b'bad l')
         assert einval(fit_rate(l, w, 0, 1050), b'bad l')
+    # the optional arguments of the folded entry points: each brings its form's checks, its
+    # neutral value none of them
+    ref, pref = ctypes.byref, ctypes.byref(plan)
+    assert einval(lib.sa_vaep_formula(ref(s), 2, fake, fake, fake, fake, fake, None), b'f32 must be 0 or 1')
+    assert einval(lib.sa_vaep_labels_formula(ref(s), 10, fake, fake, fake, 16, 2, fake, fake, fake, fake, fake, None),
+                  b'f32 must be 0 or 1')
+    win, atomic = _native.SaActions(), _native.SaActions()  # windowed SPADL; atomic without frames
+    win.n, win.n_segments, win.n_frames = 10, 1, 1
+    atomic.n, atomic.n_segments, atomic.n_frames, atomic.atomic = 10, 1, 0, 1
+    plan4 = _native.SaFeaturePlan()
+    plan4.nb_prev_actions = 4
+    assert einval(lib.sa_vaep_features_bits(ref(win), ref(plan4), fake, 16, 1, 1, None, None, None),
+                  b'float32 numeric blocks')
+    features = lambda a, l, w, cells: lib.sa_vaep_features(ref(a), pref, None, None, None, l, w, cells, None)  # noqa: E731
+    assert einval(features(win, 16, 12, ctypes.c_void_p(260)), b'xt_cells must be 16-byte aligned')
+    assert einval(features(win, 4097, 1, fake), b'xT cell codes need 1 <= l * w')
+    assert einval(features(atomic, 16, 12, fake), b'xT cells need SPADL actions')
+    step = lambda a, chunk: lib.sa_vaep_step_f64(  # noqa: E731
+        ref(a), pref, None, None, None, 0, 0, None, 10, fake, fake, fake, 16, fake, fake, fake, fake, fake, chunk, 0,
+        None)
+    assert einval(step(win, 100), b'chunk_rows must be a non-negative multiple of 512')
+    assert einval(step(atomic, 512), b'the chunked step takes the fused SPADL step form')
+    assert einval(step(atomic, 0), b'n_frames') and b'chunked' not in lib.sa_last_error()
+    sorted_frame = _native.SaSpadlFrame()
+    sorted_frame.order = 256
+    n_out = ctypes.c_int64(0)
+    assert einval(lib.sa_atomic_count(ref(sorted_frame), 1, fake, ref(n_out), None), b'order must be NULL')
+    assert einval(lib.sa_atomic_emit(ref(sorted_frame), 1, fake, ref(_native.SaAtomicFrame()), None),
+                  b'order must be NULL')
+    assert einval(lib.sa_xt_rate_interp_codes(1, ptrs(None), (ctypes.c_int64 * 1)(4), fake, fake, fake, 105, 68, fake,
+                                              1050, fake, 680, ptrs(256), fake, None), b'null codes or out')
 
 
 # ----------------------------------------------------------------------------- catalogue

@@ -132,7 +132,7 @@ def test_convert_enumeration_vs_oracle(conv, enum, layout):
     dribble among them) == the four-pass restatement: in key order (the single expansion),
     with the rows shuffled and with the two-row runs shuffled, which keeps the input-order
     successors the receival rule reads (both through ``order``), and with ``action_id // 3``
-    (repeated keys: the first pass on its own, then the ``_after_passes`` pair)."""
+    (repeated keys: the first pass on its own, then count and emit with ``after_passes``)."""
     from oracle import atomic_convert_oracle as co
     from socceraction_amd.atomic.spadl import base as cb
     f = {'as_built': enum, 'shuffled': cc.shuffled(enum), 'shuffled_runs': cc.shuffled_runs(enum),

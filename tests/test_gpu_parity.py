@@ -505,7 +505,7 @@ def test_full_size_sampled_games_vs_oracle(sa):
 
 @pytest.mark.parametrize('l,w,games', [(16, 12, 300), (30, 20, 60), (64, 64, 40), (1, 1, 5)])
 def test_xt_cell_codes_match_coordinate_path(sa, l, w, games):
-    """The xT cell codes -- written by the VAEP feature pass (sa_vaep_features_xt, both the k <= 3
+    """The xT cell codes -- written by the VAEP feature pass (sa_vaep_features' xt_cells, both the k <= 3
     register-window path and the generic path) or alone (sa_xt_cells) -- give the coordinate
     path's counts, error bits, rate values and NaN pattern bit for bit, incl. NaN / inf
     coordinates on successful moves, failed moves and shots, and an odd-length tail."""
@@ -617,7 +617,7 @@ def test_fused_goalscore_matches_scan(sa, atomic):
 def test_step_matches_separate_launches(sa, atomic):
     """sa_vaep_step_f64 (labels + f64 formula computed by the numeric pass, lane = 2 rows, the
     look-ahead by wave shuffles) == sa_vaep_features (+ the xT cell codes) followed by
-    sa_vaep_labels_formula_f64, byte for byte: the goldens (edge sizes 1..300, forced tail goals),
+    sa_vaep_labels_formula, byte for byte: the goldens (edge sizes 1..300, forced tail goals),
     full games + 300 games of 1..40 actions at nr_actions 1, 2, 10, 11 and 20 (the last runs the
     separate launches), k = 1..4, both layouts, and 2,000 full-size games; and the labels-only
     form (no probabilities) == features + labels."""
@@ -743,9 +743,9 @@ def test_contiguous_action_batch_matches(sa):
 
 
 def test_chunked_step_equals_step(sa):
-    """sa_vaep_step_f64_chunked (the numeric step pass in launches of whole 512-row blocks, each
+    """sa_vaep_step_f64 with chunk_rows (the numeric step pass in launches of whole 512-row blocks, each
     optionally after a pure-read pass over its inputs; bench.py's --ab probe of the pass's read /
-    write turnaround) == sa_vaep_step_f64 byte for byte: f64 / i64 blocks, xT cell codes, labels
+    write turnaround) == the unchunked step byte for byte: f64 / i64 blocks, xT cell codes, labels
     and formula, with a chunk that does not divide n."""
     import copy
     B, ops, syn = sa['batch'], sa['ops'], sa['synthetic']

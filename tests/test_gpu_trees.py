@@ -242,7 +242,7 @@ def test_bool_bitmap_features_and_trees(sa, atomic, k):
 
 @pytest.mark.parametrize('atomic', [False, True])
 def test_float32_numeric_blocks_and_trees(sa, atomic):
-    """sa_vaep_features_bits_f32: the numeric blocks in float32 equal the float64 / int64 blocks
+    """sa_vaep_features_bits with f32: the numeric blocks in float32 equal the float64 / int64 blocks
     rounded to nearest (torch's cast), the bitmaps are unchanged, and the staged walk of an
     xgboost learner over them gives the probabilities of the float64 form bit for bit (xgboost
     compares float32 values); scikit-learn learners and the gather walk refuse them."""

@@ -201,7 +201,7 @@ def test_step_vs_oracle(sa, atomic, k):
 
 @pytest.mark.parametrize('chunk', [512, 1024])
 def test_chunked_step_vs_oracle(sa, chunk):
-    """sa_vaep_step_f64_chunked (SPADL, the numeric pass in launches of ``chunk`` rows): numeric
+    """sa_vaep_step_f64 with chunk_rows (SPADL, the numeric pass in launches of ``chunk`` rows): numeric
     blocks, labels and f64 values as above."""
     ops = sa['ops']
     ab = _batch(sa, False)

@@ -263,7 +263,7 @@ def test_float32_and_condition_forms(sa, atomic):
 # ------------------------------------------------------------------ labels
 @pytest.mark.parametrize('atomic', PACKAGES)
 def test_labels_vs_oracle(sa, atomic):
-    """sa_vaep_labels and sa_vaep_labels_formula_f64 == the oracle at every nr_actions around the
+    """sa_vaep_labels and sa_vaep_labels_formula == the oracle at every nr_actions around the
     step's limit (11 -> 12) and the change of algorithm in labels_rows (17 -> 18), on a batch in
     which every seventh game has three teams (the full-compare branch on valid rows)."""
     ops = sa['ops']
@@ -329,7 +329,7 @@ def _misaligned(t):
 @pytest.mark.parametrize('atomic', PACKAGES)
 def test_formula_scalar_path(sa, atomic, dtype):
     """Probabilities that are not 16-byte aligned (``vec_ok`` false: the scalar loads of
-    formula_vals) through sa_vaep_formula_*, sa_vaep_labels_formula_* and, in f64, the fused
+    formula_vals) through sa_vaep_formula, sa_vaep_labels_formula and, in f64, the fused
     step == the oracle, and == the aligned call bit for bit."""
     ops = sa['ops']
     ab = _batch(sa, atomic)

@@ -191,7 +191,7 @@ def _counts(sa, s, l, w):
 
 @pytest.mark.parametrize('l,w', dc.SOLVE_SMALL)
 def test_small_solve_vs_oracle(sa, l, w):
-    """sa_xt_solve_ex and sa_xt_solve_async on the register kernel (<= 192 cells: a partly
+    """sa_xt_solve and sa_xt_solve_async on the register kernel (<= 192 cells: a partly
     filled second column part, partly filled waves) and the one-workgroup kernel (193 - 1024:
     its scalar tail where C % 8 != 0, the full 1024-thread workgroup) == xt_oracle.solve bit
     for bit: matrices, transposed transition matrix, every iterate, the surface, n_iter."""
@@ -356,7 +356,7 @@ def test_unaligned_columns_take_the_scalar_loads(sa, drop):
     assert _mode(sa, l, w, n) == dc.BANDS
     acc = ops.xt_zero_counts(l, w, dev)
     N.check(N.lib().sa_xt_count(ctypes.byref(s), l, w, acc.shot.data_ptr(), acc.goal.data_ptr(), acc.move.data_ptr(),
-                                acc.trans.data_ptr(), acc.err.data_ptr(), stream_handle()))
+                                acc.trans.data_ptr(), acc.err.data_ptr(), None, 0, stream_handle()))
     same_counts(sa, acc, ref_counts(tail, l, w), 'band count, unaligned')
     del keep
 

@@ -64,7 +64,7 @@ def _xe_slots(k):
 @pytest.mark.parametrize('l,w,hot', [(105, 68, False), (40, 30, False), (120, 68, False),
                                      (105, 68, True)])
 def test_band_count_emits_compact_rows(sa, l, w, hot):
-    """The band count's compact rows (sa_xt_count_from_buckets_ex, written from the bins) ==
+    """The band count's compact rows (sa_xt_count_from_buckets with ell / row_len, written from the bins) ==
     sa_xt_compact_rows of the dense table it wrote, entry for entry (incl. escaped counts >=
     65535), and the solve from them == the solve that builds its own (same path, iteration
     count and heatmaps bit for bit); an all-reduce or a further count drops them."""
@@ -362,8 +362,8 @@ def test_interp_codes_rate_equals_rate_interp(sa):
 
 
 def test_interp_codes_rate_many_equals_per_batch(sa):
-    """sa_xt_rate_interp_codes_many over 19 batches (two launches of <= 16 sets; odd, tiny and
-    empty batches) == sa_xt_rate_interp_codes of each batch, bit for bit, one error word."""
+    """sa_xt_rate_interp_codes over 19 batches (two launches of <= 16 sets; odd, tiny and
+    empty batches) == the same call on each batch alone (nsets = 1), bit for bit, one error word."""
     B, ops, syn = sa['batch'], sa['ops'], sa['synthetic']
     rng = np.random.default_rng(31)
     ns, ic, bs = [], [], []
@@ -491,7 +491,9 @@ def test_compact_only_count_skips_the_dense_table(sa, l, w, hot):
 def test_cell_code_bucket_count_small_grid(sa):
     """sa_xt_count_bucket from 16-bit cell codes (grids of <= SA_XT_CELLS16_MAX_C cells, 16 x 12;
     ADVICE r05): K1 loads and decodes them like the small-grid count, so the band-owned count
-    from the codes == sa_xt_count of the coordinates; 32-bit codes (40 x 30) the same."""
+    from the codes == sa_xt_count of the coordinates; 32-bit codes (40 x 30) the same.  A second
+    sa_xt_count_from_buckets without flags (and, as in the first, ell = row_len = NULL) adds the
+    same buckets into the now non-zero accumulator: every count doubles."""
     import ctypes
 
     B, ops, syn, N = sa['batch'], sa['ops'], sa['synthetic'], sa['_native']
@@ -514,12 +516,19 @@ def test_cell_code_bucket_count_small_grid(sa):
         op = (ctypes.c_void_p * 1)(off.data_ptr())
         N.check(lib.sa_xt_count_from_buckets(1, kp, op, l, w, acc.shot.data_ptr(), acc.goal.data_ptr(),
                                              acc.move.data_ptr(), acc.trans.data_ptr(),
-                                             N.SA_XT_COUNT_OVERWRITE, stream_handle()))
+                                             N.SA_XT_COUNT_OVERWRITE, None, None, stream_handle()))
         ref = ops.xt_count(ab, l, w)
         for a, b in ((acc.shot, ref.shot), (acc.goal, ref.goal), (acc.move, ref.move),
                      (acc.trans, ref.trans)):
             assert torch.equal(a, b), (l, w)
         assert int(err.item()) == int(ref.err.item())
+        assert int(ref.trans.sum()) > 0 and int(ref.shot.sum()) > 0  # the add below has something to add to
+        N.check(lib.sa_xt_count_from_buckets(1, kp, op, l, w, acc.shot.data_ptr(), acc.goal.data_ptr(),
+                                             acc.move.data_ptr(), acc.trans.data_ptr(), 0, None, None,
+                                             stream_handle()))
+        for a, b in ((acc.shot, ref.shot), (acc.goal, ref.goal), (acc.move, ref.move),
+                     (acc.trans, ref.trans)):
+            assert torch.equal(a, 2 * b), (l, w, 'add')
 
 
 @pytest.mark.parametrize('hot', [False, True])
@@ -553,8 +562,8 @@ def test_fused_fit_rate_equals_solve_then_rate(sa, hot):
 
 
 # ---------------------------------------------------------------- the host loops of the solve
-def _solve_ex(sa, acc, eps, max_iter, transition=True):
-    """sa_xt_solve_ex through the library, without ops.xt_solve's raise when max_iter is reached:
+def _lib_solve(sa, acc, eps, max_iter, transition=True):
+    """sa_xt_solve through the library, without ops.xt_solve's raise when max_iter is reached:
     (mats [4, C], trans_t or None, heatmaps [max_iter + 1, C], n_iter, path)."""
     _native = sa['_native']
     from socceraction_amd.batch import stream_handle
@@ -564,7 +573,7 @@ def _solve_ex(sa, acc, eps, max_iter, transition=True):
     heat = torch.full((max_iter + 1, C), -1.0, dtype=torch.float64, device=dev)
     n_iter, path = _native.ctypes.c_int32(7), _native.ctypes.c_int32(7)
     p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    _native.check(_native.lib().sa_xt_solve_ex(
+    _native.check(_native.lib().sa_xt_solve(
         p(acc.shot), p(acc.goal), p(acc.move), p(acc.trans), acc.l, acc.w, float(eps), int(max_iter), 0,
         p(mats), p(tt), p(heat), _native.ctypes.byref(n_iter), _native.ctypes.byref(path), None, None,
         stream_handle()))
@@ -635,7 +644,7 @@ def _steps(heat):
 
 
 def test_dense_solve_above_the_compact_limit(sa):
-    """9473 x 1, the smallest grid the compact form does not take: sa_xt_solve_ex's dense loop
+    """9473 x 1, the smallest grid the compact form does not take: sa_xt_solve's dense loop
     (one xt_iter_kernel launch per iteration, flags read back every 8) == the same iterations
     driven from here, bit for bit -- heatmaps, surface and count -- with convergence inside the
     first batch of 8, inside the second, and not within max_iter (n_iter -1, the surface the
@@ -656,7 +665,7 @@ def test_dense_solve_above_the_compact_limit(sa):
         assert torch.equal(sol.heatmaps, heat[:k + 1])
         assert torch.equal(sol.mats[:3], mats) and torch.equal(sol.mats[3], heat[k])
     for mi in (10, 16):  # max_iter reached inside a batch and at the end of one
-        mats, _, heat, n, path = _solve_ex(sa, acc, 0.5 * d[-1], mi, transition=False)
+        mats, _, heat, n, path = _lib_solve(sa, acc, 0.5 * d[-1], mi, transition=False)
         assert n == -1 and path == 'sequential'
         assert torch.equal(heat, ref[:mi + 1])
         assert torch.equal(mats[:3], ref_mats) and torch.equal(mats[3], ref[mi])
@@ -689,13 +698,13 @@ def few_games(sa):
 @pytest.mark.parametrize('l,w', [(8, 6), (30, 20)])
 def test_small_grid_solve_reaching_max_iter(sa, few_games, l, w):
     """The register solve (8 x 6) and the one-workgroup solve (30 x 20) stopped at max_iter = 2:
-    ops.xt_solve raises, sa_xt_solve_ex reports -1, sa_xt_solve_async's device count holds the
+    ops.xt_solve raises, sa_xt_solve reports -1, sa_xt_solve_async's device count holds the
     same -1, and both leave the same matrices and the iterates of an unstopped solve."""
     ops = sa['ops']
     acc = ops.xt_count(few_games, l, w)
     with pytest.raises(RuntimeError):
         ops.xt_solve(acc, max_iter=2)
-    mats, tt, heat, n, path = _solve_ex(sa, acc, 1e-5, 2)
+    mats, tt, heat, n, path = _lib_solve(sa, acc, 1e-5, 2)
     assert n == -1 and path == 'sequential'
     asy = ops.xt_solve_async(acc, max_iter=2)
     assert int(asy.n_iter.item()) == n
@@ -713,7 +722,7 @@ def test_solve_with_max_iter_zero(sa, few_games, l, w, path):
     zero, and the matrices normalised; above the small grids the reordered solve declines."""
     ops = sa['ops']
     acc = ops.xt_count(few_games, l, w)
-    mats, tt, heat, n, p = _solve_ex(sa, acc, 1e-5, 0)
+    mats, tt, heat, n, p = _lib_solve(sa, acc, 1e-5, 0)
     assert n == -1 and p == path
     assert not heat.any() and not mats[3].any()
     ref_mats, ref_tt = ops.xt_normalize(acc)

@@ -175,7 +175,7 @@ def test_native_constants_match_the_header():
         line = [ln for ln in src.splitlines() if ln.startswith(f'#define {name} ')]
         assert len(line) == 1, name
         assert int(line[0].split()[2]) == getattr(_native, name), name
-    assert _native.load_library().sa_abi_version() == 5
+    assert _native.load_library().sa_abi_version() == 6
 
 
 def test_metric_entry_points_validate_without_a_gpu():

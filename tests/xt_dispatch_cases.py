@@ -7,7 +7,7 @@ The xT half of the library picks its kernels from the cell count C = l * w:
   count for 200 - 12000 cells with R = 1 .. 8 start cells per band (``sa_xt_band_shape``), and
   XC_GLOBAL above -- :data:`COUNT_GRIDS` puts a grid on both sides of every C at which the mode
   or R changes;
-* the solve (``launch_small_solve`` / ``solve_ex``): the register kernel up to 192 cells (two
+* the solve (``launch_small_solve`` / ``solve_hooked``): the register kernel up to 192 cells (two
   column parts of 96, 32 rows per wave), one workgroup up to 1024, the compact rows up to 9472
   and the dense count rows above -- :data:`SOLVE_SMALL` / :data:`SOLVE_LARGE`.
 
