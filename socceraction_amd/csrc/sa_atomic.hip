@@ -633,11 +633,11 @@ extern "C" int sa_atomic_count(const sa_spadl_frame* in, int32_t after_passes, v
   hipStream_t st = (hipStream_t)stream;
   const int64_t nb = n_blocks(in->n);
   int64_t* bsum = (int64_t*)scratch;
-  if (after_passes)
-    hipLaunchKernelGGL(atomic_count_kernel<false>, dim3((unsigned)nb), dim3(AC_THREADS), 0, st, *in, bsum);
-  else
-    hipLaunchKernelGGL(atomic_count_kernel<true>, dim3((unsigned)nb), dim3(AC_THREADS), 0, st, *in, bsum);
-  if ((rc = check_launch("atomic_count_kernel"))) return rc;
+  rc = with_flags([&](auto PASSES) {
+    hipLaunchKernelGGL(atomic_count_kernel<PASSES()>, dim3((unsigned)nb), dim3(AC_THREADS), 0, st, *in, bsum);
+    return check_launch("atomic_count_kernel");
+  }, !after_passes);
+  if (rc) return rc;
   hipLaunchKernelGGL(atomic_scan_kernel, dim3(1), dim3(SC_THREADS), 0, st, bsum, nb);
   if ((rc = check_launch("atomic_scan_kernel"))) return rc;
   if ((rc = check_hip(hipMemcpyAsync(n_out, bsum + nb, sizeof(int64_t), hipMemcpyDeviceToHost, st),
@@ -656,13 +656,11 @@ extern "C" int sa_atomic_emit(const sa_spadl_frame* in, int32_t after_passes, co
       !out->bodypart_id)
     return fail(SA_EINVAL, "null scratch or output column");
   const int64_t nb = n_blocks(in->n);
-  if (after_passes)
-    hipLaunchKernelGGL(atomic_emit_kernel<false>, dim3((unsigned)nb), dim3(AC_THREADS), 0, (hipStream_t)stream,
+  return with_flags([&](auto PASSES) {
+    hipLaunchKernelGGL(atomic_emit_kernel<PASSES()>, dim3((unsigned)nb), dim3(AC_THREADS), 0, (hipStream_t)stream,
                        *in, (const int64_t*)scratch, *out);
-  else
-    hipLaunchKernelGGL(atomic_emit_kernel<true>, dim3((unsigned)nb), dim3(AC_THREADS), 0, (hipStream_t)stream,
-                       *in, (const int64_t*)scratch, *out);
-  return check_launch("atomic_emit_kernel");
+    return check_launch("atomic_emit_kernel");
+  }, !after_passes);
 }
 
 static bool spadl_out_ok(const sa_spadl_out* out) {

@@ -654,13 +654,11 @@ extern "C" int sa_boost_bin(const sa_block* f64_blk, const sa_block* i64_blk, in
   if (Bf.tile_rows < 1 || Bi.tile_rows < 1) return fail(SA_EINVAL, "sa_boost_bin: bad tile");
   if (n == 0 || n_num == 0) return SA_OK;
   const dim3 grid((unsigned)((n + BB_TILE - 1) / BB_TILE), (unsigned)n_num);
-  if (f32)
-    hipLaunchKernelGGL((boost_bin_kernel<1>), grid, dim3(BB_THREADS), 0, (hipStream_t)stream, Bf, Bi, slots, num_feat,
-                       cut_start, cuts, n, bins, ld);
-  else
-    hipLaunchKernelGGL((boost_bin_kernel<0>), grid, dim3(BB_THREADS), 0, (hipStream_t)stream, Bf, Bi, slots, num_feat,
-                       cut_start, cuts, n, bins, ld);
-  return check_launch("boost_bin_kernel");
+  return with_flags([&](auto F32) {
+    hipLaunchKernelGGL((boost_bin_kernel<F32() ? 1 : 0>), grid, dim3(BB_THREADS), 0, (hipStream_t)stream, Bf, Bi, slots,
+                       num_feat, cut_start, cuts, n, bins, ld);
+    return check_launch("boost_bin_kernel");
+  }, f32 != 0);
 }
 
 extern "C" int sa_boost_grad(const float* margin, const uint8_t* y, const uint8_t* row_mask, int64_t n,
@@ -675,13 +673,12 @@ extern "C" int sa_boost_grad(const float* margin, const uint8_t* y, const uint8_
   const u64 round_base = fmix64(fmix64((u64)seed ^ SA_BOOST_SALT_ROWS) + (u64)round);
   const grad_tuning tu{weight, scale_pos_weight, std::ldexp(1.0f, 30 - shift), row_keys, round_base, (u64)thr};
   const dim3 grid((unsigned)((n + 255) / 256));
-  if (!weight && scale_pos_weight == 1.0f && shift == 0 && !row_keys && thr == (1ull << 32))
-    hipLaunchKernelGGL((boost_grad_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, margin, y, row_mask, n, gq,
-                       hq, p, node, tu);
-  else
-    hipLaunchKernelGGL((boost_grad_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, margin, y, row_mask, n, gq,
-                       hq, p, node, tu);
-  return check_launch("boost_grad_kernel");
+  const bool plain = !weight && scale_pos_weight == 1.0f && shift == 0 && !row_keys && thr == (1ull << 32);
+  return with_flags([&](auto TUNED) {
+    hipLaunchKernelGGL((boost_grad_kernel<TUNED()>), grid, dim3(256), 0, (hipStream_t)stream, margin, y, row_mask, n,
+                       gq, hq, p, node, tu);
+    return check_launch("boost_grad_kernel");
+  }, !plain);
 }
 
 extern "C" int sa_boost_row_keys(const int64_t* game_id, const int64_t* action_id, int64_t n, int64_t* keys,
@@ -738,15 +735,12 @@ extern "C" int sa_boost_hist_bins(const uint8_t* bins, int64_t ld, const int32_t
   int64_t gx = (int64_t)device_cus(current_device()) * SA_BOOST_BINS_WG_PER_CU / groups;
   if (gx < SA_BOOST_BINS_MIN_GRID_X) gx = SA_BOOST_BINS_MIN_GRID_X;
   if (gx > steps) gx = steps;
-  if (num_rows)
-    hipLaunchKernelGGL((boost_hist_bins_kernel<true>), dim3((unsigned)gx, (unsigned)groups), dim3(HN_THREADS), lds,
+  return with_flags([&](auto ROWS) {
+    hipLaunchKernelGGL((boost_hist_bins_kernel<ROWS()>), dim3((unsigned)gx, (unsigned)groups), dim3(HN_THREADS), lds,
                        (hipStream_t)stream, bins, ld, num_feat, num_rows, n_bin_rows, n_num, gq, hq, node, n, node0,
                        n_nodes, n_features, fg, hist);
-  else
-    hipLaunchKernelGGL((boost_hist_bins_kernel<false>), dim3((unsigned)gx, (unsigned)groups), dim3(HN_THREADS), lds,
-                       (hipStream_t)stream, bins, ld, num_feat, num_rows, n_bin_rows, n_num, gq, hq, node, n, node0,
-                       n_nodes, n_features, fg, hist);
-  return check_launch("boost_hist_bins_kernel");
+    return check_launch("boost_hist_bins_kernel");
+  }, num_rows != nullptr);
 }
 
 extern "C" int sa_boost_split(const int64_t* hist, const int32_t* cut_start, const float* cuts, int32_t n_features,
@@ -787,13 +781,11 @@ extern "C" int sa_boost_advance(const sa_boost_node* tree, int32_t node0, int32_
   }
   if (n == 0) return SA_OK;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  if (margin)
-    hipLaunchKernelGGL((boost_advance_kernel<true>), grid, block, 0, (hipStream_t)stream, tree, node0, n_nodes, fmap,
+  return with_flags([&](auto ADD) {
+    hipLaunchKernelGGL((boost_advance_kernel<ADD()>), grid, block, 0, (hipStream_t)stream, tree, node0, n_nodes, fmap,
                        (const u64*)bits, bits_stride / 8, bins, ld, n, node, margin);
-  else
-    hipLaunchKernelGGL((boost_advance_kernel<false>), grid, block, 0, (hipStream_t)stream, tree, node0, n_nodes, fmap,
-                       (const u64*)bits, bits_stride / 8, bins, ld, n, node, margin);
-  return check_launch("boost_advance_kernel");
+    return check_launch("boost_advance_kernel");
+  }, margin != nullptr);
 }
 
 extern "C" int sa_boost_apply(const sa_boost_node* tree, int32_t max_depth, const int32_t* fmap, const uint64_t* bits,

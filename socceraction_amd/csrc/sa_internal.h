@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/socceraction_amd.h"
 #include "sa_debug.h"
 
@@ -21,6 +23,20 @@ int device_cus(int dev);
 int device_lds_max(int dev);
 // The current device (0 when the query fails).
 int current_device();
+
+// Runtime flags -> template arguments: calls the generic lambda `f` with one std::true_type /
+// std::false_type per flag, in the flags' order, and returns its int.  In the lambda a flag is a
+// constant (`kernel<A(), E()>`), so a launch's argument list is written once; a combination with
+// no kernel is excluded there by `if constexpr`, which also keeps it from being instantiated.
+template <class F, class... Rest>
+int with_flags(F&& f, bool flag, Rest... rest) {
+  if constexpr (sizeof...(rest) == 0) {
+    return flag ? f(std::true_type{}) : f(std::false_type{});
+  } else {
+    return flag ? with_flags([&](auto... r) { return f(std::true_type{}, r...); }, rest...)
+                : with_flags([&](auto... r) { return f(std::false_type{}, r...); }, rest...);
+  }
+}
 
 // Library-owned device scratch (the cached per-device arena of sa_api.hip).  acquire returns a
 // slot of at least `bytes` that no other call is using; release hands it back once the work

@@ -446,6 +446,7 @@ __global__ __launch_bounds__(TS_ROWS) void tree_cond_kernel(CondSet<typename std
                                                             CondModel<typename std::conditional<F32, float, double>::type> P,
                                                             sa_block Bb, const uint8_t* __restrict__ bits, int64_t bstride,
                                                             sa_block Bf, sa_block Bi, int64_t n) {
+  static_assert(F32 || !N32, "float32 numeric blocks (N32) only with float32 arithmetic (F32)");
   using A = typename std::conditional<F32, float, double>::type;
   extern __shared__ __attribute__((aligned(16))) unsigned char ts_lds[];
   // LDS carved by integer offsets from ts_lds (a pointer cast through uintptr_t would make
@@ -516,33 +517,17 @@ extern "C" int sa_tree_predict(const void* nodes, int32_t n_nodes, const int32_t
   const size_t lds_bytes = (size_t)n_nodes * sizeof(TNode) + (size_t)n_features * sizeof(int32_t);
   if (tree_depth && n_nodes <= TR_LDS_NODES && n_trees > 0) {
     const size_t fb = (size_t)n_nodes * (f32 ? sizeof(LNode<float>) : sizeof(LNode<double>));
-#define SA_TF_LAUNCH(F, LEQ)                                                                    \
-  hipLaunchKernelGGL((tree_fixed_kernel<F, LEQ>), grid, block, fb, st, nd, n_nodes, roots, tree_depth, n_trees, \
-                     feature_slots, Bb, Bf, Bi, n, base_margin, p_out)
-    if (f32 && le)
-      SA_TF_LAUNCH(true, true);
-    else if (f32)
-      SA_TF_LAUNCH(true, false);
-    else if (le)
-      SA_TF_LAUNCH(false, true);
-    else
-      SA_TF_LAUNCH(false, false);
-#undef SA_TF_LAUNCH
-    return check_launch("tree_fixed_kernel");
+    return with_flags([&](auto F32, auto LE) {
+      hipLaunchKernelGGL((tree_fixed_kernel<F32(), LE()>), grid, block, fb, st, nd, n_nodes, roots, tree_depth, n_trees,
+                         feature_slots, Bb, Bf, Bi, n, base_margin, p_out);
+      return check_launch("tree_fixed_kernel");
+    }, f32 != 0, le != 0);
   }
-#define SA_TREE_LAUNCH(F, S)                                                                       \
-  hipLaunchKernelGGL((tree_predict_kernel<F, S>), grid, block, S ? lds_bytes : 0, st, nd, n_nodes, roots, n_trees, \
-                     feature_slots, n_features, Bb, Bf, Bi, n, base_margin, le, p_out)
-  if (f32 && staged)
-    SA_TREE_LAUNCH(true, true);
-  else if (f32)
-    SA_TREE_LAUNCH(true, false);
-  else if (staged)
-    SA_TREE_LAUNCH(false, true);
-  else
-    SA_TREE_LAUNCH(false, false);
-#undef SA_TREE_LAUNCH
-  return check_launch("tree_predict_kernel");
+  return with_flags([&](auto F32, auto STAGED) {
+    hipLaunchKernelGGL((tree_predict_kernel<F32(), STAGED()>), grid, block, STAGED() ? lds_bytes : 0, st, nd, n_nodes,
+                       roots, n_trees, feature_slots, n_features, Bb, Bf, Bi, n, base_margin, le, p_out);
+    return check_launch("tree_predict_kernel");
+  }, f32 != 0, staged);
 }
 
 // The staged walk's LDS: conditions, nodes, leaf values, then the roots and depths padded to
@@ -582,30 +567,20 @@ extern "C" int sa_tree_predict_staged(const sa_tree_model* model, const int32_t*
   const int64_t tiles = (n + TS_ROWS - 1) / TS_ROWS;
   const dim3 block(TS_ROWS);
   hipStream_t st = (hipStream_t)stream;
-  // one workgroup per tile
-#define SA_TS_LAUNCH(F, LEQ, A, N32)                                                                     \
-  do {                                                                                                  \
-    CondSet<A> C{bool_cols, num_cols, col_start, (const A*)num_thr, num_dl, n_bool, n_num > 0 ? n_ncol : 0, \
-                 n_num};                                                                                \
-    CondModel<A> P{(const uint32_t*)m.nodes, (const A*)m.leaf, m.roots, m.tree_depth, m.n_nodes,        \
-                   m.n_trees,                m.base_margin,    m.p_out};                                \
-    hipLaunchKernelGGL((tree_cond_kernel<F, LEQ, N32>), dim3((unsigned)tiles), block, (size_t)lds, st, C, P, Bb, \
-                       bool_bits, bits_stride, Bf, Bi, n);                                               \
-  } while (0)
   const bool n32 = (f32 & 2) != 0;  // float32 numeric blocks
   if (n32 && !(f32 & 1)) return fail(SA_EINVAL, "float32 numeric blocks need float32 (xgboost) arithmetic");
-  if (n32 && le)
-    SA_TS_LAUNCH(true, true, float, true);
-  else if (n32)
-    SA_TS_LAUNCH(true, false, float, true);
-  else if (f32 && le)
-    SA_TS_LAUNCH(true, true, float, false);
-  else if (f32)
-    SA_TS_LAUNCH(true, false, float, false);
-  else if (le)
-    SA_TS_LAUNCH(false, true, double, false);
-  else
-    SA_TS_LAUNCH(false, false, double, false);
-#undef SA_TS_LAUNCH
-  return check_launch("tree_cond_kernel");
+  // one workgroup per tile.  tree_cond_kernel<F32, LE, N32>: N32 only with F32 (checked above)
+  return with_flags([&](auto F32, auto LE, auto N32) {
+    if constexpr (N32() && !F32()) {
+      return fail(SA_EINVAL, "float32 numeric blocks need float32 (xgboost) arithmetic");
+    } else {
+      using A = std::conditional_t<F32(), float, double>;
+      CondSet<A> C{bool_cols, num_cols, col_start, (const A*)num_thr, num_dl, n_bool, n_num > 0 ? n_ncol : 0, n_num};
+      CondModel<A> P{(const uint32_t*)m.nodes, (const A*)m.leaf, m.roots, m.tree_depth, m.n_nodes,
+                     m.n_trees,                m.base_margin,    m.p_out};
+      hipLaunchKernelGGL((tree_cond_kernel<F32(), LE(), N32()>), dim3((unsigned)tiles), block, (size_t)lds, st, C, P, Bb,
+                         bool_bits, bits_stride, Bf, Bi, n);
+      return check_launch("tree_cond_kernel");
+    }
+  }, f32 != 0, le != 0, n32);
 }

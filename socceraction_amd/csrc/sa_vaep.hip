@@ -1,10 +1,10 @@
 // VAEP / Atomic-VAEP hot-path kernels for gfx950 (MI355X).
 //
 //   bool_colgroup_kernel     one-hot + team features (gamestates + flip fused in), bool block
+//   formula_kernel           offensive / defensive / vaep value (f64 or f32)
 //   num_features_kernel      time / location / polar / movement / deltas / ids, f64 + i64 blocks
 //   goalscore_wave16_kernel  segmented exclusive scan (one wave per segment)
 //   labels_kernel            scores / concedes / goal_from_shot look-ahead
-//   formula_kernel           offensive / defensive / vaep value (f64 or f32)
 //
 // All of it is HBM-bound byte/int/f64 streaming; nothing here is GEMM-shaped.  The output
 // is ~94 % of the traffic, so the kernels are built around full-width stores:
@@ -63,27 +63,40 @@ struct FeatArgs {
   int64_t* iout;
   int64_t Cb, Cf, Ci;  // columns of each block
   int64_t Rb, Rf, Ri;  // rows per tile of each block (include/socceraction_amd.h)
-  uint32_t* xt_cells;  // optional: xT cell code of every action (sa_vaep_features with xt_cells)
-  int32_t xt_l, xt_w;
-  uint16_t* bbits;     // optional: bool features as bitmaps instead of bout (sa_vaep_features_bits)
-  int64_t bstride;     // u16 per bitmap
-  // optional tail (sa_vaep_step_f64): labels + f64 formula of the same rows, computed by the
-  // numeric pass (num_features_kernel<..., TAIL>)
-  int32_t nr;
-  uint8_t *sc, *co, *gfs;
-  const double *ps, *pc;
-  double *off, *def, *val;
-  bool vec_ok;
-  // optional (sa_vaep_features_conditions): the numeric columns become split-condition bitmaps
-  const int32_t *cond_fstart, *cond_istart;  // [Cf + 1], [Ci + 1]: conditions of each column
-  const float* cond_thr;                     // per condition: float32 threshold (`x < thr` goes left)
-  const int32_t* cond_dl;                    // per condition: NaN goes left
-  int32_t cond_row0;                         // bitmap row of condition 0 (after the bool columns)
-  int32_t cond_n;                             // conditions (num_cond_lds_kernel stages the tables)
-  // the numeric pass over rows [row0, row_end) only (row_end 0: to n); row0 a multiple of
-  // BLOCK_ACTS (sa_vaep_step_f64 with chunk_rows: one launch per chunk of the batch)
-  int64_t row0, row_end;
+  // The optional parts, one record each: an entry point fills the ones it uses (FeatReq) and
+  // launch_features copies them whole; all zero = absent.
+  struct XtCells {    // xT cell code of every action (sa_vaep_features with xt_cells)
+    uint32_t* cells;
+    int32_t l, w;
+  } xt;
+  struct Bits {       // bool features as bitmaps instead of bout (sa_vaep_features_bits)
+    uint16_t* words;
+    int64_t stride;   // u16 per bitmap
+  } bits;
+  struct Tail {       // sa_vaep_step_f64: labels + f64 formula of the same rows, computed by the
+    int32_t nr;       // numeric pass (num_features_kernel<..., TAIL>); nr >= 1 = present
+    uint8_t *sc, *co, *gfs;
+    const double *ps, *pc;
+    double *off, *def, *val;
+    bool vec_ok;
+  } tail;
+  struct Cond {       // sa_vaep_features_conditions: the numeric columns become split-condition bitmaps
+    const int32_t *fstart, *istart;  // [Cf + 1], [Ci + 1]: conditions of each column
+    const float* thr;                // per condition: float32 threshold (`x < thr` goes left)
+    const int32_t* dl;               // per condition: NaN goes left
+    int32_t row0;                    // bitmap row of condition 0 (after the bool columns)
+    int32_t n;                       // conditions (num_cond_lds_kernel stages the tables)
+  } cond;
+  struct Rows {       // the numeric pass over rows [row0, row_end) only (row_end 0: to n); row0 a
+    int64_t row0, row_end;  // multiple of BLOCK_ACTS (sa_vaep_step_f64 with chunk_rows: one launch per chunk)
+  } rows;
 };
+// The kernels take FeatArgs by value: the sub-records keep the flat record's field order, so the
+// kernel-argument bytes are where they were.
+static_assert(sizeof(FeatArgs) == 1184 && offsetof(FeatArgs, xt) == 1016 && offsetof(FeatArgs, bits) == 1032 &&
+                  offsetof(FeatArgs, tail) == 1048 && offsetof(FeatArgs, cond) == 1128 &&
+                  offsetof(FeatArgs, rows) == 1168,
+              "FeatArgs layout moved");
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // COND mode of the numeric pass: a store of column `col` (rows jb, jb+1 of the lane) evaluates
@@ -126,8 +139,8 @@ __device__ __forceinline__ CondSink cond_sink(const int32_t* start, int32_t n_st
                                               int64_t wb, int64_t n, CondAcc* acc) {
   const int lane = threadIdx.x & 63;
   const int64_t jb = wb + 2 * lane;
-  CondSink k{start, args.cond_thr, args.cond_dl, args.bbits, args.bstride, args.cond_row0, wb, n, acc,
-             n_start, args.cond_n, lane < n_start ? start[lane] : 0, __ballot(jb < n), __ballot(jb + 1 < n)};
+  CondSink k{start, args.cond.thr, args.cond.dl, args.bits.words, args.bits.stride, args.cond.row0, wb, n, acc,
+             n_start, args.cond.n, lane < n_start ? start[lane] : 0, __ballot(jb < n), __ballot(jb + 1 < n)};
   return k;
 }
 
@@ -353,7 +366,7 @@ __device__ __forceinline__ void st_bool_out(const FeatArgs& a, uint8_t* __restri
     SA_DGUARD(col >= 0 && col < a.Cb, col, return);
     uint32_t b = bits_of_strided(w0, w1, w2, w3);
     if (a.a.n - j0 < 16) b &= (1u << (a.a.n - j0)) - 1u;
-    a.bbits[col * a.bstride + j0 / 16] = (uint16_t)b;
+    a.bits.words[col * a.bits.stride + j0 / 16] = (uint16_t)b;
   } else {
     st_bool16(bb, col, a.Cb, a.Rb, w0, w1, w2, w3);
   }
@@ -480,6 +493,7 @@ constexpr int WIDE_D_MAX = 1 << 30;
 template <bool ATOMIC, bool EXPLICIT, bool BITS, bool WIDE>
 __device__ __forceinline__ void bool_colgroup_body(const FeatArgs& args, int ngroups, int gcols,
                                                    int64_t lblock) {
+  static_assert(!(EXPLICIT && (BITS || WIDE)), "explicit frames: the byte block, no gathered windows");
   const int lane = threadIdx.x & (WAVE - 1);
   const int wv = threadIdx.x / WAVE;
   const sa_actions& A = args.a;
@@ -1026,18 +1040,172 @@ __device__ __forceinline__ void goalscore_pair(const sa_actions& A, int64_t wb, 
   }
 }
 
-// ------------------------------------------------------------------------------ tail in the
-// numeric pass (sa_vaep_step_f64): labels + f64 formula of the lane's rows jb, jb+1.
+// ------------------------------------------------------------------------------ formula
+// vaep/formula.py:8-151, atomic/vaep/formula.py:8-141.  Arithmetic stays in the probability
+// dtype and mirrors the pandas expression tree operation by operation.  A lane owns V
+// consecutive actions (16-B stores); the previous row's values come from the same lane or,
+// for the lane's first action, from the neighbouring lane by a wave shuffle.
+// Rows j0 .. j0+V-1 of one lane (V = 16 / sizeof(T)); every lane of the wave calls it with
+// consecutive j0 (the previous row comes from the neighbouring lane); `cur` = a segment cursor
+// at or before row j0, advanced by the call.
+// t_in (optional, vector path): the rows' time_seconds the caller already holds (the numeric
+// step pass loaded them with its window rows), so they are not read a second time
+template <bool ATOMIC, typename T, typename VT>
+__device__ __forceinline__ bool formula_vals(const sa_actions& A, const T* __restrict__ ps,
+                                             const T* __restrict__ pc, bool vec_ok, int64_t j0, SegCursor& cur,
+                                             VT& vo, VT& vd, VT& vv, const double* t_in = nullptr) {
+  constexpr int V = 16 / sizeof(T);
+  const int64_t n = A.n;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const bool active = j0 < n;
+  const sa_frame& F = A.frames[0];
+  T s_[V], c_[V];
+  double t_[V];
+  int32_t tm_[V], ty_[V], rs_[V];
+  typedef T vec_t __attribute__((ext_vector_type(V)));
+  if (vec_ok && active && j0 + V <= n) {  // whole 16-B vectors (vec_ok: 16-B aligned probabilities)
+    const vec_t vs = ld_stream<2>(reinterpret_cast<const vec_t*>(ps + j0));
+    const vec_t vc = ld_stream<2>(reinterpret_cast<const vec_t*>(pc + j0));
+#pragma unroll
+    for (int q = 0; q < V; q += 2) {
+      if (t_in) {
+        t_[q] = t_in[q];
+        t_[q + 1] = t_in[q + 1];
+      } else {
+        const f64x2 tv = *reinterpret_cast<const f64x2*>(F.time_seconds + j0 + q);
+        t_[q] = tv[0];
+        t_[q + 1] = tv[1];
+      }
+    }
+    uint32_t tyw, rsw = 0;
+    if (V == 4) {
+      const int4 tv = *reinterpret_cast<const int4*>(F.team + j0);
+      tm_[0] = tv.x;
+      tm_[1 % V] = tv.y;
+      tm_[2 % V] = tv.z;
+      tm_[3 % V] = tv.w;
+      tyw = *reinterpret_cast<const uint32_t*>(F.type_id + j0);
+      if (!ATOMIC) rsw = *reinterpret_cast<const uint32_t*>(F.result_id + j0);
+    } else {
+      const int2 tv = *reinterpret_cast<const int2*>(F.team + j0);
+      tm_[0] = tv.x;
+      tm_[1 % V] = tv.y;
+      tyw = *reinterpret_cast<const uint16_t*>(F.type_id + j0);
+      if (!ATOMIC) rsw = *reinterpret_cast<const uint16_t*>(F.result_id + j0);
+    }
+#pragma unroll
+    for (int q = 0; q < V; ++q) {
+      s_[q] = vs[q];
+      c_[q] = vc[q];
+      ty_[q] = (int32_t)byte_of(tyw, q);
+      rs_[q] = (int32_t)byte_of(rsw, q);
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < V; ++q) {  // own rows j0 .. j0+V-1 (clamped to n-1 in the tail)
+      const int64_t j = active ? (j0 + q < n ? j0 + q : n - 1) : 0;
+      s_[q] = ps[j];
+      c_[q] = pc[j];
+      t_[q] = F.time_seconds[j];
+      tm_[q] = F.team[j];
+      ty_[q] = F.type_id[j];
+      rs_[q] = ATOMIC ? 0 : F.result_id[j];
+    }
+  }
+  // row j0-1 comes from the previous lane (lane 0 loads it itself)
+  T sp = __shfl_up(s_[V - 1], 1, WAVE), cp = __shfl_up(c_[V - 1], 1, WAVE);
+  double tp = __shfl_up(t_[V - 1], 1, WAVE);
+  int32_t tmp = __shfl_up(tm_[V - 1], 1, WAVE), typ = __shfl_up(ty_[V - 1], 1, WAVE),
+          rsp = __shfl_up(rs_[V - 1], 1, WAVE);
+  if (!active) return false;
+  if (lane == 0 && j0 > 0) {
+    const int64_t p = j0 - 1;
+    sp = ps[p];
+    cp = pc[p];
+    tp = F.time_seconds[p];
+    tmp = F.team[p];
+    typ = F.type_id[p];
+    rsp = ATOMIC ? 0 : F.result_id[p];
+  }
+#pragma unroll
+  for (int q = 0; q < V; ++q) {
+    const int64_t j = j0 + q < n ? j0 + q : n - 1;
+    seg_advance(A, cur, j);
+    const bool first = j == cur.s;  // _prev of a segment's first row is the row itself
+    T Sp = q ? s_[q - 1] : sp, Cp = q ? c_[q - 1] : cp;
+    double Tp = q ? t_[q - 1] : tp;
+    int32_t TMp = q ? tm_[q - 1] : tmp, TYp = q ? ty_[q - 1] : typ, RSp = q ? rs_[q - 1] : rsp;
+    if (first) {
+      Sp = s_[q];
+      Cp = c_[q];
+      Tp = t_[q];
+      TMp = tm_[q];
+      TYp = ty_[q];
+      RSp = rs_[q];
+    }
+    const T one = T(1), zero = T(0);
+    const bool same = TMp == tm_[q];
+    const T fs = same ? one : zero, fn = same ? zero : one;
+    T prev_s = Sp * fs + Cp * fn;  // _prev(scores) * sameteam + _prev(concedes) * ~sameteam
+    T prev_c = Cp * fs + Sp * fn;
+    bool prevgoal;
+    if (ATOMIC) {
+      prevgoal = TYp == AT_GOAL || TYp == AT_OWNGOAL;
+    } else {
+      if (fabs(t_[q] - Tp) > 10.0) {  // _samephase_nb
+        prev_s = zero;
+        prev_c = zero;
+      }
+      prevgoal = (TYp == T_SHOT || TYp == T_SHOT_PENALTY || TYp == T_SHOT_FREEKICK) &&
+                 RSp == R_SUCCESS;
+    }
+    if (prevgoal) {
+      prev_s = zero;
+      prev_c = zero;
+    }
+    if (!ATOMIC) {
+      if (ty_[q] == T_SHOT_PENALTY) prev_s = T(0.792453);
+      if (ty_[q] == T_CORNER_CROSSED || ty_[q] == T_CORNER_SHORT) prev_s = T(0.046500);
+    }
+    const T o = s_[q] - prev_s;
+    const T d = -(c_[q] - prev_c);
+    vo[q] = o;
+    vd[q] = d;
+    vv[q] = o + d;
+  }
+  return true;
+}
+
+// formula_vals of rows j0 .. j0+V-1, stored (one 16-B store per output column)
 template <bool ATOMIC, typename T>
 __device__ __forceinline__ void formula_rows(const sa_actions& A, const T* __restrict__ ps,
                                              const T* __restrict__ pc, T* __restrict__ off,
                                              T* __restrict__ def, T* __restrict__ val, bool vec_ok,
-                                             int64_t j0, SegCursor& cur);
-template <bool ATOMIC, typename T, typename V>
-__device__ __forceinline__ bool formula_vals(const sa_actions& A, const T* __restrict__ ps,
-                                             const T* __restrict__ pc, bool vec_ok, int64_t j0, SegCursor& cur,
-                                             V& vo, V& vd, V& vv, const double* t_in = nullptr);
+                                             int64_t j0, SegCursor& cur) {
+  constexpr int V = 16 / sizeof(T);
+  typedef T vec_t __attribute__((ext_vector_type(V)));
+  vec_t vo, vd, vv;
+  if (!formula_vals<ATOMIC, T>(A, ps, pc, vec_ok, j0, cur, vo, vd, vv)) return;
+  st16(off + j0, vo);
+  st16(def + j0, vd);
+  st16(val + j0, vv);
+}
 
+template <bool ATOMIC, typename T>
+__global__ __launch_bounds__(256) void formula_kernel(sa_actions A, const T* __restrict__ ps,
+                                                      const T* __restrict__ pc, T* __restrict__ off,
+                                                      T* __restrict__ def, T* __restrict__ val,
+                                                      bool vec_ok) {
+  constexpr int V = 16 / sizeof(T);
+  const int64_t j0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  const int64_t jw = ((int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~(WAVE - 1))) * V;
+  if (jw >= A.n) return;  // whole wave past the end (the shuffles need every lane of a live wave)
+  SegCursor cur = wave_cursor(A, jw);
+  formula_rows<ATOMIC, T>(A, ps, pc, off, def, val, vec_ok, j0, cur);
+}
+
+// ------------------------------------------------------------------------------ tail in the
+// numeric pass (sa_vaep_step_f64): labels + f64 formula of the lane's rows jb, jb+1.
 // goal (bit 0) / owngoal (bit 1) / shot (bit 2, atomic goal_from_shot) of row j
 template <bool ATOMIC>
 __device__ __forceinline__ uint32_t label_bits(const sa_frame& F, int64_t j) {
@@ -1145,10 +1313,10 @@ __device__ __forceinline__ void labels_store(int64_t n, uint8_t* __restrict__ sc
 #ifndef SA_NUM_WAVES
 #define SA_NUM_WAVES 0
 #endif
-template <bool ATOMIC, bool TAIL>
-constexpr int num_min_waves() {
-  return SA_NUM_WAVES > 0 ? SA_NUM_WAVES : 1;
-}
+constexpr int NUM_MIN_WAVES = SA_NUM_WAVES > 0 ? SA_NUM_WAVES : 1;
+// The forms with a kernel (launch_features instantiates these and no other): EXPLICIT only with
+// KF = 0; TAIL / N32 / COND only windowed with KF = 3, and at most one of them; TAIL only SPADL
+// (sa_vaep_step_f64 gives atomic actions the separate launches).
 // The pass over the wave's 128 rows from wave_base.  F0: frames[0] of args; ps_in / pc_in: the
 // probabilities (TAIL).
 template <bool ATOMIC, bool EXPLICIT, int KF, bool TAIL = false, bool N32 = false, bool COND = false>
@@ -1156,6 +1324,11 @@ __device__ __forceinline__ void num_features_body(const FeatArgs& args, int64_t 
                                                   const double* ps_in, const double* pc_in) {
   // N32: the f64 and i64 blocks hold float32 values (sa_vaep_features_bits with f32); COND: no blocks,
   // the columns' split conditions as bitmaps (sa_vaep_features_conditions)
+  static_assert(KF == 0 || KF == 3, "KF is 0 or 3");
+  static_assert(!(EXPLICIT && KF == 3), "explicit frames have no register-resident windows");
+  static_assert((int)TAIL + (int)N32 + (int)COND <= 1 && (!(TAIL || N32 || COND) || KF == 3),
+                "TAIL / N32 / COND: windowed with KF = 3, one at a time");
+  static_assert(!(ATOMIC && TAIL), "the fused step is SPADL only");
   using FT = typename std::conditional<COND, CondSink, typename std::conditional<N32, float, double>::type>::type;
   using IT = typename std::conditional<COND, CondSink, typename std::conditional<N32, float, int64_t>::type>::type;
   const int lane = threadIdx.x & (WAVE - 1);
@@ -1165,12 +1338,12 @@ __device__ __forceinline__ void num_features_body(const FeatArgs& args, int64_t 
   const int K = P.nb_prev_actions;
   const int64_t Rf = args.Rf, Ri = args.Ri;
   // whole wave past the end (uniform: the goalscore ballots need every lane)
-  if (wave_base >= n || (args.row_end > 0 && wave_base >= args.row_end)) return;
+  if (wave_base >= n || (args.rows.row_end > 0 && wave_base >= args.rows.row_end)) return;
   CondAcc acc{0, 0, 0, -64, 0.0f, 0};
   CondSink sink_f, sink_i;
   if constexpr (COND) {
-    sink_f = cond_sink(args.cond_fstart, (int)args.Cf + 1, args, wave_base, n, &acc);
-    sink_i = cond_sink(args.cond_istart, (int)args.Ci + 1, args, wave_base, n, &acc);
+    sink_f = cond_sink(args.cond.fstart, (int)args.Cf + 1, args, wave_base, n, &acc);
+    sink_i = cond_sink(args.cond.istart, (int)args.Ci + 1, args, wave_base, n, &acc);
   }
   auto fblock = [&](int64_t j) -> FT* {
     if constexpr (COND) return &sink_f;
@@ -1234,11 +1407,11 @@ __device__ __forceinline__ void num_features_body(const FeatArgs& args, int64_t 
     seg_advance(A, cur, jl);
     if (gcol >= 0) goalscore_pair<ATOMIC>(A, wave_base, jw, cur, gs);
     if (TAIL) {  // labels + formula of the same rows (every lane of the wave present)
-      labels_pair<ATOMIC>(A, args.nr, jw, cur, lso, lco, lgo);
-      if (args.ps) {  // uniform: labels only when no probabilities are given
+      labels_pair<ATOMIC>(A, args.tail.nr, jw, cur, lso, lco, lgo);
+      if (args.tail.ps) {  // uniform: labels only when no probabilities are given
         SegCursor fc = cur;
         const double t_rows[2] = {cand[0].ts, cand[1].ts};  // rows jw, jw+1 (KF = 3)
-        fok = formula_vals<ATOMIC, double>(A, ps_in, pc_in, args.vec_ok, jw, fc, fo, fd, fv,
+        fok = formula_vals<ATOMIC, double>(A, ps_in, pc_in, args.tail.vec_ok, jw, fc, fo, fd, fv,
                                            KF == 3 ? t_rows : nullptr);
       }
     }
@@ -1256,11 +1429,11 @@ __device__ __forceinline__ void num_features_body(const FeatArgs& args, int64_t 
       for (int k = 0; k < 3; ++k) st_i64x2(gib, gcol + k, (int)args.Ci, Ri, gs[k][0], gs[k][1]);
     }
     if (TAIL) {
-      labels_store(n, args.sc, args.co, args.gfs, jw, lso, lco, lgo);
+      labels_store(n, args.tail.sc, args.tail.co, args.tail.gfs, jw, lso, lco, lgo);
       if (fok) {
-        st16(args.off + jw, fo);
-        st16(args.def + jw, fd);
-        st16(args.val + jw, fv);
+        st16(args.tail.off + jw, fo);
+        st16(args.tail.def + jw, fd);
+        st16(args.tail.val + jw, fv);
       }
     }
   }
@@ -1294,25 +1467,25 @@ __device__ __forceinline__ void num_features_body(const FeatArgs& args, int64_t 
       // the next pool row, unless the action's window already reached its segment start
       // (d < i): then it keeps its row.  (If action 0 is clamped so is action 1, whose d is at
       // most d0 + 1.)
-      if (!ATOMIC && args.xt_cells) {  // the raw (unflipped) rows jb, jb+1: xT cell codes
+      if (!ATOMIC && args.xt.cells) {  // the raw (unflipped) rows jb, jb+1: xT cell codes
         uint32_t cc[2];
-        const bool c16 = xt_c16(args.xt_l * args.xt_w);
+        const bool c16 = xt_c16(args.xt.l * args.xt.w);
 #pragma unroll
         for (int e = 0; e < 2; ++e)
           cc[e] = c16 ? xt_cell_code16((cand[e].ids >> 8) & 0xFF, (cand[e].ids >> 16) & 0xFF, cand[e].c0,
-                                       cand[e].c1, cand[e].c2, cand[e].c3, args.xt_l, args.xt_w)
+                                       cand[e].c1, cand[e].c2, cand[e].c3, args.xt.l, args.xt.w)
                       : xt_cell_code((cand[e].ids >> 8) & 0xFF, (cand[e].ids >> 16) & 0xFF, cand[e].c0,
-                                     cand[e].c1, cand[e].c2, cand[e].c3, args.xt_l, args.xt_w);
+                                     cand[e].c1, cand[e].c2, cand[e].c3, args.xt.l, args.xt.w);
         if (c16) {
-          uint16_t* c2 = reinterpret_cast<uint16_t*>(args.xt_cells);
+          uint16_t* c2 = reinterpret_cast<uint16_t*>(args.xt.cells);
           if (jb + 2 <= n)
             *reinterpret_cast<uint32_t*>(c2 + jb) = cc[0] | (cc[1] << 16);
           else
             c2[jb] = (uint16_t)cc[0];
         } else if (jb + 2 <= n) {
-          *reinterpret_cast<uint2*>(args.xt_cells + jb) = make_uint2(cc[0], cc[1]);
+          *reinterpret_cast<uint2*>(args.xt.cells + jb) = make_uint2(cc[0], cc[1]);
         } else {
-          args.xt_cells[jb] = cc[0];
+          args.xt.cells[jb] = cc[0];
         }
       }
       // COND: family-major order -- the condition tables are numbered by column, so visiting the
@@ -1404,14 +1577,14 @@ __device__ __forceinline__ void num_features_body(const FeatArgs& args, int64_t 
         for (int e = 0; e < 2; ++e) {
           const int64_t r = EXPLICIT ? jr[e] : jr[e] - (dd[e] < i ? dd[e] : i);
           load_row(Fi, r, ATOMIC, w, e);
-          if (!ATOMIC && !EXPLICIT && i == 0 && args.xt_cells && jb + e < n)  // raw row jb+e
+          if (!ATOMIC && !EXPLICIT && i == 0 && args.xt.cells && jb + e < n)  // raw row jb+e
           {
-            if (xt_c16(args.xt_l * args.xt_w))
-              reinterpret_cast<uint16_t*>(args.xt_cells)[jb + e] = (uint16_t)xt_cell_code16(
-                  w.typ[e], w.res[e], w.c0[e], w.c1[e], w.c2[e], w.c3[e], args.xt_l, args.xt_w);
+            if (xt_c16(args.xt.l * args.xt.w))
+              reinterpret_cast<uint16_t*>(args.xt.cells)[jb + e] = (uint16_t)xt_cell_code16(
+                  w.typ[e], w.res[e], w.c0[e], w.c1[e], w.c2[e], w.c3[e], args.xt.l, args.xt.w);
             else
-              args.xt_cells[jb + e] = xt_cell_code(w.typ[e], w.res[e], w.c0[e], w.c1[e], w.c2[e],
-                                                   w.c3[e], args.xt_l, args.xt_w);
+              args.xt.cells[jb + e] = xt_cell_code(w.typ[e], w.res[e], w.c0[e], w.c1[e], w.c2[e],
+                                                   w.c3[e], args.xt.l, args.xt.w);
           }
           if (!EXPLICIT && away[e]) flip<ATOMIC>(w, e);
           if (i == 0) {
@@ -1430,11 +1603,11 @@ __device__ __forceinline__ void num_features_body(const FeatArgs& args, int64_t 
 }
 
 template <bool ATOMIC, bool EXPLICIT, int KF, bool TAIL = false, bool N32 = false, bool COND = false>
-__global__ __launch_bounds__(64 * BLOCK_WAVES) __attribute__((amdgpu_waves_per_eu(num_min_waves<ATOMIC, TAIL>(), 8)))
+__global__ __launch_bounds__(64 * BLOCK_WAVES) __attribute__((amdgpu_waves_per_eu(NUM_MIN_WAVES, 8)))
 void num_features_kernel(FeatArgs args) {
   const int wv = threadIdx.x / WAVE;
-  const int64_t wave_base = args.row0 + (xcd_logical_block() * BLOCK_WAVES + wv) * WAVE_ACTS;
-  num_features_body<ATOMIC, EXPLICIT, KF, TAIL, N32, COND>(args, wave_base, args.a.frames[0], args.ps, args.pc);
+  const int64_t wave_base = args.rows.row0 + (xcd_logical_block() * BLOCK_WAVES + wv) * WAVE_ACTS;
+  num_features_body<ATOMIC, EXPLICIT, KF, TAIL, N32, COND>(args, wave_base, args.a.frames[0], args.tail.ps, args.tail.pc);
 }
 
 // sa_vaep_features_conditions' numeric pass with the condition tables (column starts,
@@ -1447,29 +1620,29 @@ __host__ __device__ inline int64_t cond_lds_bytes(int64_t cf, int64_t ci, int64_
   return 4 * (cf + ci + 2) + 8 * n_cond;
 }
 template <bool ATOMIC>
-__global__ __launch_bounds__(64 * BLOCK_WAVES) __attribute__((amdgpu_waves_per_eu(num_min_waves<ATOMIC, false>(), 8)))
+__global__ __launch_bounds__(64 * BLOCK_WAVES) __attribute__((amdgpu_waves_per_eu(NUM_MIN_WAVES, 8)))
 void num_cond_lds_kernel(FeatArgs args) {
   extern __shared__ __attribute__((aligned(16))) int32_t ctab[];
-  const int nf = (int)args.Cf + 1, ni = (int)args.Ci + 1, nc = args.cond_n;
+  const int nf = (int)args.Cf + 1, ni = (int)args.Ci + 1, nc = args.cond.n;
   int32_t* fs = ctab;
   int32_t* is = fs + nf;
   float* th = reinterpret_cast<float*>(is + ni);
   int32_t* dl = reinterpret_cast<int32_t*>(th + nc);
-  for (int i = threadIdx.x; i < nf; i += 64 * BLOCK_WAVES) fs[i] = args.cond_fstart[i];
-  for (int i = threadIdx.x; i < ni; i += 64 * BLOCK_WAVES) is[i] = args.cond_istart[i];
+  for (int i = threadIdx.x; i < nf; i += 64 * BLOCK_WAVES) fs[i] = args.cond.fstart[i];
+  for (int i = threadIdx.x; i < ni; i += 64 * BLOCK_WAVES) is[i] = args.cond.istart[i];
   for (int i = threadIdx.x; i < nc; i += 64 * BLOCK_WAVES) {
-    th[i] = args.cond_thr[i];
-    dl[i] = args.cond_dl[i];
+    th[i] = args.cond.thr[i];
+    dl[i] = args.cond.dl[i];
   }
   __syncthreads();
   FeatArgs a = args;
-  a.cond_fstart = fs;
-  a.cond_istart = is;
-  a.cond_thr = th;
-  a.cond_dl = dl;
+  a.cond.fstart = fs;
+  a.cond.istart = is;
+  a.cond.thr = th;
+  a.cond.dl = dl;
   const int wv = threadIdx.x / WAVE;
-  const int64_t wave_base = args.row0 + (xcd_logical_block() * BLOCK_WAVES + wv) * WAVE_ACTS;
-  num_features_body<ATOMIC, false, 3, false, false, true>(a, wave_base, a.a.frames[0], a.ps, a.pc);
+  const int64_t wave_base = args.rows.row0 + (xcd_logical_block() * BLOCK_WAVES + wv) * WAVE_ACTS;
+  num_features_body<ATOMIC, false, 3, false, false, true>(a, wave_base, a.a.frames[0], a.tail.ps, a.tail.pc);
 }
 
 // ------------------------------------------------------------------------------ goalscore
@@ -1687,170 +1860,6 @@ __global__ __launch_bounds__(256) void labels_kernel(sa_actions A, int nr, uint8
   labels_rows<ATOMIC>(A, nr, sc, co, gfs, j0, wave_cursor(A, j0));  // first active lane's row
 }
 
-// ------------------------------------------------------------------------------ formula
-// vaep/formula.py:8-151, atomic/vaep/formula.py:8-141.  Arithmetic stays in the probability
-// dtype and mirrors the pandas expression tree operation by operation.  A lane owns V
-// consecutive actions (16-B stores); the previous row's values come from the same lane or,
-// for the lane's first action, from the neighbouring lane by a wave shuffle.
-// Rows j0 .. j0+V-1 of one lane (V = 16 / sizeof(T)); every lane of the wave calls it with
-// consecutive j0 (the previous row comes from the neighbouring lane); `cur` = a segment cursor
-// at or before row j0, advanced by the call.
-// t_in (optional, vector path): the rows' time_seconds the caller already holds (the numeric
-// step pass loaded them with its window rows), so they are not read a second time
-template <bool ATOMIC, typename T, typename VT>
-__device__ __forceinline__ bool formula_vals(const sa_actions& A, const T* __restrict__ ps,
-                                             const T* __restrict__ pc, bool vec_ok, int64_t j0, SegCursor& cur,
-                                             VT& vo, VT& vd, VT& vv, const double* t_in) {
-  constexpr int V = 16 / sizeof(T);
-  const int64_t n = A.n;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const bool active = j0 < n;
-  const sa_frame& F = A.frames[0];
-  T s_[V], c_[V];
-  double t_[V];
-  int32_t tm_[V], ty_[V], rs_[V];
-  typedef T vec_t __attribute__((ext_vector_type(V)));
-  if (vec_ok && active && j0 + V <= n) {  // whole 16-B vectors (vec_ok: 16-B aligned probabilities)
-    const vec_t vs = ld_stream<2>(reinterpret_cast<const vec_t*>(ps + j0));
-    const vec_t vc = ld_stream<2>(reinterpret_cast<const vec_t*>(pc + j0));
-#pragma unroll
-    for (int q = 0; q < V; q += 2) {
-      if (t_in) {
-        t_[q] = t_in[q];
-        t_[q + 1] = t_in[q + 1];
-      } else {
-        const f64x2 tv = *reinterpret_cast<const f64x2*>(F.time_seconds + j0 + q);
-        t_[q] = tv[0];
-        t_[q + 1] = tv[1];
-      }
-    }
-    uint32_t tyw, rsw = 0;
-    if (V == 4) {
-      const int4 tv = *reinterpret_cast<const int4*>(F.team + j0);
-      tm_[0] = tv.x;
-      tm_[1 % V] = tv.y;
-      tm_[2 % V] = tv.z;
-      tm_[3 % V] = tv.w;
-      tyw = *reinterpret_cast<const uint32_t*>(F.type_id + j0);
-      if (!ATOMIC) rsw = *reinterpret_cast<const uint32_t*>(F.result_id + j0);
-    } else {
-      const int2 tv = *reinterpret_cast<const int2*>(F.team + j0);
-      tm_[0] = tv.x;
-      tm_[1 % V] = tv.y;
-      tyw = *reinterpret_cast<const uint16_t*>(F.type_id + j0);
-      if (!ATOMIC) rsw = *reinterpret_cast<const uint16_t*>(F.result_id + j0);
-    }
-#pragma unroll
-    for (int q = 0; q < V; ++q) {
-      s_[q] = vs[q];
-      c_[q] = vc[q];
-      ty_[q] = (int32_t)byte_of(tyw, q);
-      rs_[q] = (int32_t)byte_of(rsw, q);
-    }
-  } else {
-#pragma unroll
-    for (int q = 0; q < V; ++q) {  // own rows j0 .. j0+V-1 (clamped to n-1 in the tail)
-      const int64_t j = active ? (j0 + q < n ? j0 + q : n - 1) : 0;
-      s_[q] = ps[j];
-      c_[q] = pc[j];
-      t_[q] = F.time_seconds[j];
-      tm_[q] = F.team[j];
-      ty_[q] = F.type_id[j];
-      rs_[q] = ATOMIC ? 0 : F.result_id[j];
-    }
-  }
-  // row j0-1 comes from the previous lane (lane 0 loads it itself)
-  T sp = __shfl_up(s_[V - 1], 1, WAVE), cp = __shfl_up(c_[V - 1], 1, WAVE);
-  double tp = __shfl_up(t_[V - 1], 1, WAVE);
-  int32_t tmp = __shfl_up(tm_[V - 1], 1, WAVE), typ = __shfl_up(ty_[V - 1], 1, WAVE),
-          rsp = __shfl_up(rs_[V - 1], 1, WAVE);
-  if (!active) return false;
-  if (lane == 0 && j0 > 0) {
-    const int64_t p = j0 - 1;
-    sp = ps[p];
-    cp = pc[p];
-    tp = F.time_seconds[p];
-    tmp = F.team[p];
-    typ = F.type_id[p];
-    rsp = ATOMIC ? 0 : F.result_id[p];
-  }
-#pragma unroll
-  for (int q = 0; q < V; ++q) {
-    const int64_t j = j0 + q < n ? j0 + q : n - 1;
-    seg_advance(A, cur, j);
-    const bool first = j == cur.s;  // _prev of a segment's first row is the row itself
-    T Sp = q ? s_[q - 1] : sp, Cp = q ? c_[q - 1] : cp;
-    double Tp = q ? t_[q - 1] : tp;
-    int32_t TMp = q ? tm_[q - 1] : tmp, TYp = q ? ty_[q - 1] : typ, RSp = q ? rs_[q - 1] : rsp;
-    if (first) {
-      Sp = s_[q];
-      Cp = c_[q];
-      Tp = t_[q];
-      TMp = tm_[q];
-      TYp = ty_[q];
-      RSp = rs_[q];
-    }
-    const T one = T(1), zero = T(0);
-    const bool same = TMp == tm_[q];
-    const T fs = same ? one : zero, fn = same ? zero : one;
-    T prev_s = Sp * fs + Cp * fn;  // _prev(scores) * sameteam + _prev(concedes) * ~sameteam
-    T prev_c = Cp * fs + Sp * fn;
-    bool prevgoal;
-    if (ATOMIC) {
-      prevgoal = TYp == AT_GOAL || TYp == AT_OWNGOAL;
-    } else {
-      if (fabs(t_[q] - Tp) > 10.0) {  // _samephase_nb
-        prev_s = zero;
-        prev_c = zero;
-      }
-      prevgoal = (TYp == T_SHOT || TYp == T_SHOT_PENALTY || TYp == T_SHOT_FREEKICK) &&
-                 RSp == R_SUCCESS;
-    }
-    if (prevgoal) {
-      prev_s = zero;
-      prev_c = zero;
-    }
-    if (!ATOMIC) {
-      if (ty_[q] == T_SHOT_PENALTY) prev_s = T(0.792453);
-      if (ty_[q] == T_CORNER_CROSSED || ty_[q] == T_CORNER_SHORT) prev_s = T(0.046500);
-    }
-    const T o = s_[q] - prev_s;
-    const T d = -(c_[q] - prev_c);
-    vo[q] = o;
-    vd[q] = d;
-    vv[q] = o + d;
-  }
-  return true;
-}
-
-// formula_vals of rows j0 .. j0+V-1, stored (one 16-B store per output column)
-template <bool ATOMIC, typename T>
-__device__ __forceinline__ void formula_rows(const sa_actions& A, const T* __restrict__ ps,
-                                             const T* __restrict__ pc, T* __restrict__ off,
-                                             T* __restrict__ def, T* __restrict__ val, bool vec_ok,
-                                             int64_t j0, SegCursor& cur) {
-  constexpr int V = 16 / sizeof(T);
-  typedef T vec_t __attribute__((ext_vector_type(V)));
-  vec_t vo, vd, vv;
-  if (!formula_vals<ATOMIC, T>(A, ps, pc, vec_ok, j0, cur, vo, vd, vv)) return;
-  st16(off + j0, vo);
-  st16(def + j0, vd);
-  st16(val + j0, vv);
-}
-
-template <bool ATOMIC, typename T>
-__global__ __launch_bounds__(256) void formula_kernel(sa_actions A, const T* __restrict__ ps,
-                                                      const T* __restrict__ pc, T* __restrict__ off,
-                                                      T* __restrict__ def, T* __restrict__ val,
-                                                      bool vec_ok) {
-  constexpr int V = 16 / sizeof(T);
-  const int64_t j0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
-  const int64_t jw = ((int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~(WAVE - 1))) * V;
-  if (jw >= A.n) return;  // whole wave past the end (the shuffles need every lane of a live wave)
-  SegCursor cur = wave_cursor(A, jw);
-  formula_rows<ATOMIC, T>(A, ps, pc, off, def, val, vec_ok, j0, cur);
-}
-
 // Labels and formula of the same 1024 rows in one wave (the step's tail: one launch, the ids
 // and team codes read once): the labels part as labels_kernel (a lane owns 16 rows), then the
 // formula part in passes of 64 * V rows as formula_kernel (a lane owns V rows), both lanes'
@@ -1922,15 +1931,6 @@ static int check_block(const sa_block* b, int64_t n, int64_t quantum, const char
   return SA_OK;
 }
 
-struct TailArgs {  // labels + f64 formula riding in the numeric pass (sa_vaep_step_f64)
-  int32_t nr;
-  uint8_t *sc, *co, *gfs;
-  const double *ps, *pc;
-  double *off, *def, *val;
-  int64_t chunk;     // > 0: the numeric pass in launches of `chunk` rows (sa_vaep_step_f64's chunk_rows)
-  int32_t prefetch;  // each chunk's inputs read into the Infinity Cache first
-};
-
 // The chunked sa_vaep_step_f64's probe of the numeric pass's read / write turnaround: rows [r0, r1)'s
 // inputs (coordinates, time, ids, team codes, probabilities: 64 B per row) read once with the
 // default cache policy, so the Infinity Cache holds them when the pass over the chunk runs --
@@ -1962,14 +1962,28 @@ __global__ __launch_bounds__(256) void prefetch_rows_kernel(sa_actions A, const 
   if (h == 0x5A5A5A5A5A5A5A5Aull) sink[0] = (uint32_t)h;  // never in practice: keeps the loads
 }
 
-// Argument checks shared by the entry points (each keeps its own order of checks).
-// The label columns: leading dimension and alignment.
-static int check_label_outputs(int64_t n, const uint8_t* scores, const uint8_t* concedes,
-                               const uint8_t* goal_from_shot, int64_t ld) {
-  if (ld % 16 != 0 || ld < ((n + 15) / 16) * 16)
+// Argument checks shared by the entry points, each stated once.  Inside a helper the order is the
+// one written here; an entry point calls check_actions first (sa_vaep_features with xt_cells:
+// check_xt_cells first, so an atomic batch gets the xT message whatever its frames), then the
+// helpers in the order labels, formula, xT cells.
+// The labels: look-ahead, then the label columns' leading dimension and alignment.
+static int check_labels(const sa_actions* a, int32_t nr_actions, const uint8_t* scores, const uint8_t* concedes,
+                        const uint8_t* goal_from_shot, int64_t ld) {
+  if (nr_actions < 1) return fail(SA_EINVAL, "nr_actions must be >= 1");
+  if (ld % 16 != 0 || ld < ((a->n + 15) / 16) * 16)
     return fail(SA_EINVAL, "ld must be a multiple of 16 and >= round_up(n, 16)");
   if (!aligned16(scores) || !aligned16(concedes) || !aligned16(goal_from_shot))
     return fail(SA_EINVAL, "label outputs must be 16-byte aligned");
+  return SA_OK;
+}
+
+// The xT cell codes a feature pass writes beside its blocks: SPADL, windowed, a grid whose codes fit.
+static int check_xt_cells(const sa_actions* a, int32_t l, int32_t w, const uint32_t* cells) {
+  if (!a) return fail(SA_EINVAL, "null sa_actions");
+  if (a->atomic || a->n_frames != 1) return fail(SA_EINVAL, "xT cells need SPADL actions in windowed mode");
+  if (l < 1 || w < 1 || (int64_t)l * w > SA_XT_CELLS_MAX_C)
+    return fail(SA_EINVAL, "xT cell codes need 1 <= l * w <= %d", SA_XT_CELLS_MAX_C);
+  if (!aligned16(cells)) return fail(SA_EINVAL, "xt_cells must be 16-byte aligned");
   return SA_OK;
 }
 
@@ -1992,23 +2006,24 @@ static int check_bool_bits(int64_t n, const uint8_t* bool_bits, int64_t bits_str
   return SA_OK;
 }
 
-struct FeatReq {  // what one feature pass writes; an entry point fills the fields it uses
-  const sa_block *bool_out, *f64_out, *i64_out;  // the three blocks (f64 / i64: float32 when num32)
-  int32_t xt_l, xt_w;       // with xt_cells: the xT cell code of every action
-  uint32_t* xt_cells;
-  uint8_t* bits;            // the bool features as bitmaps instead of bool_out
-  int64_t bits_stride;      // bytes per bitmap
-  int32_t n_bits;           // bitmaps (the bool columns)
-  const TailArgs* tail;     // labels + f64 formula in the numeric pass
-  bool num32;               // float32 numeric blocks
-  const FeatArgs* cond;     // the condition tables: the numeric columns as condition bitmaps
+// What one feature pass writes.  An entry point names the blocks launch_features is to check and
+// fills, by name, the optional parts of FeatArgs it uses (checked by the entry point itself); the
+// rest stays zero = absent.
+struct FeatReq {
+  const sa_block *bool_out = nullptr, *f64_out = nullptr, *i64_out = nullptr;  // f64 / i64: float32 when num32
+  int32_t n_bits = 0;    // with bits: bitmaps (the bool columns)
+  bool num32 = false;    // float32 numeric blocks
+  FeatArgs::XtCells xt{};
+  FeatArgs::Bits bits{};
+  FeatArgs::Tail tail{};
+  FeatArgs::Cond cond{};
+  int64_t chunk = 0;     // > 0: the numeric pass in launches of `chunk` rows (sa_vaep_step_f64's chunk_rows)
+  int32_t prefetch = 0;  // each chunk's inputs read into the Infinity Cache first
 };
 
 static int launch_features(const sa_actions* a, const sa_feature_plan* plan, const FeatReq& q, void* stream) {
   const sa_block *bool_out = q.bool_out, *f64_out = q.f64_out, *i64_out = q.i64_out;
-  uint8_t* const bits = q.bits;
-  const TailArgs* const tail = q.tail;
-  const FeatArgs* const cond = q.cond;
+  const bool bits = q.bits.words != nullptr, tail = q.tail.nr > 0, cond = q.cond.fstart != nullptr;
   int rc = check_actions(a, true);
   if (rc) return rc;
   if (!plan) return fail(SA_EINVAL, "null plan");
@@ -2046,38 +2061,30 @@ static int launch_features(const sa_actions* a, const sa_feature_plan* plan, con
   }
   if (a->n == 0) return SA_OK;
   hipStream_t st = (hipStream_t)stream;
-  FeatArgs args{*a,
-                *plan,
-                wb && !bits ? (uint8_t*)bool_out->data : nullptr,
-                wf ? (double*)f64_out->data : nullptr,
-                wi ? (int64_t*)i64_out->data : nullptr,
-                wb ? (bits ? (int64_t)q.n_bits : bool_out->n_cols) : 0,
-                wf ? f64_out->n_cols : 0,
-                wi ? i64_out->n_cols : 0,
-                wb && !bits ? bool_out->tile_rows : BOOL_TILE,
-                wf ? f64_out->tile_rows : 16,
-                wi ? i64_out->tile_rows : 16,
-                q.xt_cells,
-                q.xt_l,
-                q.xt_w,
-                (wb || cond) ? (uint16_t*)bits : nullptr,  // COND: the condition rows even with no bool column
-                q.bits_stride / 2,
-                tail ? tail->nr : 0,
-                tail ? tail->sc : nullptr,
-                tail ? tail->co : nullptr,
-                tail ? tail->gfs : nullptr,
-                tail ? tail->ps : nullptr,
-                tail ? tail->pc : nullptr,
-                tail ? tail->off : nullptr,
-                tail ? tail->def : nullptr,
-                tail ? tail->val : nullptr,
-                tail ? (aligned16(tail->ps) && aligned16(tail->pc)) : false,
-                cond ? cond->cond_fstart : nullptr,
-                cond ? cond->cond_istart : nullptr,
-                cond ? cond->cond_thr : nullptr,
-                cond ? cond->cond_dl : nullptr,
-                cond ? cond->cond_row0 : 0};
-  args.cond_n = cond ? cond->cond_n : 0;
+  FeatArgs args{};
+  args.a = *a;
+  args.p = *plan;
+  args.Rb = BOOL_TILE;  // an absent block: no data, no columns, a valid tile
+  args.Rf = args.Ri = 16;
+  if (wb) args.Cb = bits ? (int64_t)q.n_bits : bool_out->n_cols;
+  if (wb && !bits) {
+    args.bout = (uint8_t*)bool_out->data;
+    args.Rb = bool_out->tile_rows;
+  }
+  if (wf) {
+    args.fout = (double*)f64_out->data;
+    args.Cf = f64_out->n_cols;
+    args.Rf = f64_out->tile_rows;
+  }
+  if (wi) {
+    args.iout = (int64_t*)i64_out->data;
+    args.Ci = i64_out->n_cols;
+    args.Ri = i64_out->tile_rows;
+  }
+  args.xt = q.xt;
+  args.bits = q.bits;
+  args.tail = q.tail;
+  args.cond = q.cond;
   const dim3 grid(xcd_grid((a->n + BLOCK_ACTS - 1) / BLOCK_ACTS)), block(BLOCK_WAVES * WAVE);
   const bool expl = a->n_frames > 1, atomic = a->atomic != 0;
   if (wb) {  // one wave per (tile, group of ~32 columns), XCD-contiguous sweep order
@@ -2086,92 +2093,54 @@ static int launch_features(const sa_actions* a, const sa_feature_plan* plan, con
     const int64_t waves = (a->n + BOOL_TILE - 1) / BOOL_TILE * ng;
     const dim3 cgrid(xcd_grid((waves + CG_WAVES - 1) / CG_WAVES)), cblock(WAVE * CG_WAVES);
     const bool wide = !expl && K > BOOL_HALO + 1;  // windows past the register halo
-#define SA_BOOL_LAUNCH(ATOMIC, EXPLICIT, BITS, WIDE) \
-  hipLaunchKernelGGL((bool_colgroup_kernel<ATOMIC, EXPLICIT, BITS, WIDE>), cgrid, cblock, 0, st, args, ng, gc)
-    if (bits) {  // the on-device VAEP.rate: SPADL or atomic, windowed, as bitmaps
-      if (wide && atomic)
-        SA_BOOL_LAUNCH(true, false, true, true);
-      else if (wide)
-        SA_BOOL_LAUNCH(false, false, true, true);
-      else if (atomic)
-        SA_BOOL_LAUNCH(true, false, true, false);
-      else
-        SA_BOOL_LAUNCH(false, false, true, false);
-    } else if (atomic) {
-      if (expl)
-        SA_BOOL_LAUNCH(true, true, false, false);
-      else if (wide)
-        SA_BOOL_LAUNCH(true, false, false, true);
-      else
-        SA_BOOL_LAUNCH(true, false, false, false);
-    } else {
-      if (expl)
-        SA_BOOL_LAUNCH(false, true, false, false);
-      else if (wide)
-        SA_BOOL_LAUNCH(false, false, false, true);
-      else
-        SA_BOOL_LAUNCH(false, false, false, false);
-    }
-#undef SA_BOOL_LAUNCH
-    rc = check_launch("bool_colgroup_kernel");
+    // bool_colgroup_kernel<ATOMIC, EXPLICIT, BITS, WIDE>: EXPLICIT never with BITS (the bitmap
+    // entry points are windowed only) or WIDE (explicit frames hold their own windows)
+    rc = with_flags([&](auto A, auto E, auto B, auto W) {
+      if constexpr (E() && (B() || W())) {
+        return fail(SA_EINVAL, "no bool feature kernel for explicit frames as bitmaps");
+      } else {
+        hipLaunchKernelGGL((bool_colgroup_kernel<A(), E(), B(), W()>), cgrid, cblock, 0, st, args, ng, gc);
+        return check_launch("bool_colgroup_kernel");
+      }
+    }, atomic, expl, bits, wide);
     if (rc) return rc;
   }
   const int gc = plan->i64_col[SA_XFN_GOALSCORE];
-  if (wn || q.xt_cells || tail || (gc >= 0 && !expl)) {  // windowed mode: goalscore fused into this pass
+  if (wn || q.xt.cells || tail || (gc >= 0 && !expl)) {  // windowed mode: goalscore fused into this pass
     const bool fast = !expl && K <= 3;  // register-resident windows (KF = 3)
-    // num_features_kernel<ATOMIC, EXPLICIT, KF, TAIL, N32, COND> on grid G
-#define SA_NUM_LAUNCH(G, ...) hipLaunchKernelGGL((num_features_kernel<__VA_ARGS__>), G, block, 0, st, args)
-    if (cond && cond_lds_bytes(args.Cf, args.Ci, args.cond_n) <= COND_LDS_MAX) {
-      const size_t lds = (size_t)cond_lds_bytes(args.Cf, args.Ci, args.cond_n);
-      if (atomic)
-        hipLaunchKernelGGL(num_cond_lds_kernel<true>, grid, block, lds, st, args);
-      else
-        hipLaunchKernelGGL(num_cond_lds_kernel<false>, grid, block, lds, st, args);
-    } else if (cond) {  // windowed, K <= 3 (checked by sa_vaep_features_conditions)
-      if (atomic)
-        SA_NUM_LAUNCH(grid, true, false, 3, false, false, true);
-      else
-        SA_NUM_LAUNCH(grid, false, false, 3, false, false, true);
-    } else if (q.num32) {  // windowed, K <= 3 (checked by sa_vaep_features_bits)
-      if (atomic)
-        SA_NUM_LAUNCH(grid, true, false, 3, false, true);
-      else
-        SA_NUM_LAUNCH(grid, false, false, 3, false, true);
-    } else if (tail && tail->chunk > 0 && !atomic) {  // sa_vaep_step_f64 with chunk_rows (probe)
-      for (int64_t c0 = 0; c0 < a->n; c0 += tail->chunk) {
-        const int64_t c1 = c0 + tail->chunk < a->n ? c0 + tail->chunk : a->n;
-        if (tail->prefetch) {
+    // num_features_kernel<ATOMIC, EXPLICIT, KF, TAIL, N32, COND> on grid g over args.rows; the
+    // legal forms are listed above num_features_body.  TAIL, N32 and COND come with K <= 3 in
+    // windowed mode (checked by sa_vaep_step_f64, _features_bits, _features_conditions).
+    auto num_pass = [&](const dim3& g) {
+      return with_flags([&](auto A, auto E, auto F, auto T, auto N, auto C) {
+        if constexpr ((E() && F()) || T() + N() + C() > 1 || ((T() || N() || C()) && !F()) || (A() && T())) {
+          return fail(SA_EINVAL, "no numeric feature kernel for this form");
+        } else {
+          hipLaunchKernelGGL((num_features_kernel<A(), E(), F() ? 3 : 0, T(), N(), C()>), g, block, 0, st, args);
+          return check_launch("num_features_kernel");
+        }
+      }, atomic, expl, fast, tail, q.num32, cond);
+    };
+    if (cond && cond_lds_bytes(args.Cf, args.Ci, args.cond.n) <= COND_LDS_MAX) {  // the tables staged in LDS
+      const size_t lds = (size_t)cond_lds_bytes(args.Cf, args.Ci, args.cond.n);
+      rc = with_flags([&](auto A) {
+        hipLaunchKernelGGL(num_cond_lds_kernel<A()>, grid, block, lds, st, args);
+        return check_launch("num_features_kernel");
+      }, atomic);
+    } else if (tail && q.chunk > 0) {  // sa_vaep_step_f64 with chunk_rows (probe)
+      for (int64_t c0 = 0; c0 < a->n && !rc; c0 += q.chunk) {
+        const int64_t c1 = c0 + q.chunk < a->n ? c0 + q.chunk : a->n;
+        if (q.prefetch) {
           const int64_t th = (c1 - c0 + 3) / 4;
           hipLaunchKernelGGL(prefetch_rows_kernel, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, st, *a,
-                             tail->ps, tail->pc, c0, c1, q.xt_cells);
+                             q.tail.ps, q.tail.pc, c0, c1, q.xt.cells);
         }
-        args.row0 = c0;
-        args.row_end = c1;
-        const dim3 cg(xcd_grid((c1 - c0 + BLOCK_ACTS - 1) / BLOCK_ACTS));
-        SA_NUM_LAUNCH(cg, false, false, 3, true);
+        args.rows = {c0, c1};
+        rc = num_pass(dim3(xcd_grid((c1 - c0 + BLOCK_ACTS - 1) / BLOCK_ACTS)));
       }
-    } else if (tail) {  // windowed, K <= 3 (checked by sa_vaep_step_f64)
-      if (atomic)
-        SA_NUM_LAUNCH(grid, true, false, 3, true);
-      else
-        SA_NUM_LAUNCH(grid, false, false, 3, true);
-    } else if (atomic) {
-      if (expl)
-        SA_NUM_LAUNCH(grid, true, true, 0);
-      else if (fast)
-        SA_NUM_LAUNCH(grid, true, false, 3);
-      else
-        SA_NUM_LAUNCH(grid, true, false, 0);
     } else {
-      if (expl)
-        SA_NUM_LAUNCH(grid, false, true, 0);
-      else if (fast)
-        SA_NUM_LAUNCH(grid, false, false, 3);
-      else
-        SA_NUM_LAUNCH(grid, false, false, 0);
+      rc = num_pass(grid);
     }
-#undef SA_NUM_LAUNCH
-    rc = check_launch("num_features_kernel");
     if (rc) return rc;
   }
   if (gc >= 0 && expl) rc = sa_vaep_goalscore(a, i64_out, gc, stream);  // explicit frames: own scan
@@ -2182,13 +2151,12 @@ extern "C" int sa_vaep_features(const sa_actions* a, const sa_feature_plan* plan
                                 const sa_block* bool_out, const sa_block* f64_out,
                                 const sa_block* i64_out, int32_t xt_l, int32_t xt_w, uint32_t* xt_cells,
                                 void* stream) {
-  if (!xt_cells) return launch_features(a, plan, FeatReq{bool_out, f64_out, i64_out}, stream);
-  if (!a) return fail(SA_EINVAL, "null sa_actions");
-  if (a->atomic || a->n_frames != 1) return fail(SA_EINVAL, "xT cells need SPADL actions in windowed mode");
-  if (xt_l < 1 || xt_w < 1 || (int64_t)xt_l * xt_w > SA_XT_CELLS_MAX_C)
-    return fail(SA_EINVAL, "xT cell codes need 1 <= l * w <= %d", SA_XT_CELLS_MAX_C);
-  if (!aligned16(xt_cells)) return fail(SA_EINVAL, "xt_cells must be 16-byte aligned");
-  return launch_features(a, plan, FeatReq{bool_out, f64_out, i64_out, xt_l, xt_w, xt_cells}, stream);
+  FeatReq q{bool_out, f64_out, i64_out};
+  if (xt_cells) {
+    if (int rc = check_xt_cells(a, xt_l, xt_w, xt_cells)) return rc;
+    q.xt = {xt_cells, xt_l, xt_w};
+  }
+  return launch_features(a, plan, q, stream);
 }
 
 extern "C" int sa_vaep_features_bits(const sa_actions* a, const sa_feature_plan* plan, uint8_t* bool_bits,
@@ -2199,8 +2167,8 @@ extern "C" int sa_vaep_features_bits(const sa_actions* a, const sa_feature_plan*
   if (a->n_frames != 1) return fail(SA_EINVAL, "bool bitmaps: windowed mode only");
   if (f32 && (!plan || plan->nb_prev_actions > 3))
     return fail(SA_EINVAL, "float32 numeric blocks: nb_prev_actions <= 3 (use f32 = 0)");
-  FeatReq q{nullptr, f64_out, i64_out, 0, 0, nullptr, bool_bits, bits_stride, n_bool_cols};
-  q.num32 = f32 != 0;
+  FeatReq q{nullptr, f64_out, i64_out, n_bool_cols, f32 != 0};
+  q.bits = {(uint16_t*)bool_bits, bits_stride / 2};
   return launch_features(a, plan, q, stream);
 }
 
@@ -2221,22 +2189,99 @@ extern "C" int sa_vaep_features_conditions(const sa_actions* a, const sa_feature
     return fail(SA_EINVAL, "condition bitmaps: at most %d f64 and %d i64 columns", WAVE - 1, WAVE - 1);
   // stand-in descriptors: the numeric pass writes no block in this mode, only the bitmaps
   const sa_block fz{bits, n_f64_cols, 0, 128}, iz{bits, n_i64_cols, 0, 128};
-  FeatArgs c{};
-  c.cond_fstart = cond_fstart;
-  c.cond_istart = cond_istart;
-  c.cond_thr = cond_thr;
-  c.cond_dl = cond_dl;
-  c.cond_row0 = n_bool_cols;
-  c.cond_n = n_cond;
-  FeatReq q{nullptr, &fz, &iz, 0, 0, nullptr, bits, bits_stride, n_bool_cols};
-  q.cond = &c;
+  FeatReq q{nullptr, &fz, &iz, n_bool_cols};
+  q.bits = {(uint16_t*)bits, bits_stride / 2};
+  q.cond = {cond_fstart, cond_istart, cond_thr, cond_dl, n_bool_cols, n_cond};
   return launch_features(a, plan, q, stream);
+}
+
+extern "C" int sa_vaep_goalscore(const sa_actions* a, const sa_block* i64_out, int32_t col,
+                                 void* stream) {
+  int rc = check_actions(a, true);
+  if (rc) return rc;
+  if ((rc = check_block(i64_out, a->n, SA_NUM_TILE_QUANTUM, "i64"))) return rc;
+  if (col < 0 || col + 3 > i64_out->n_cols) return fail(SA_EINVAL, "goalscore columns outside the block");
+  if (a->n == 0) return SA_OK;
+  const dim3 g4((unsigned)((a->n_segments + 3) / 4));  // one wave per segment
+  return with_flags([&](auto ATOMIC) {
+    hipLaunchKernelGGL((goalscore_wave16_kernel<ATOMIC()>), g4, dim3(256), 0, (hipStream_t)stream, *a,
+                       (int64_t*)i64_out->data, (int64_t)i64_out->n_cols, (int64_t)col, i64_out->tile_rows);
+    return check_launch("goalscore_wave16_kernel");
+  }, a->atomic != 0);
+}
+
+extern "C" int sa_vaep_labels(const sa_actions* a, int32_t nr_actions, uint8_t* scores,
+                              uint8_t* concedes, uint8_t* goal_from_shot, int64_t ld, void* stream) {
+  int rc = check_actions(a, false);
+  if (rc) return rc;
+  if ((rc = check_labels(a, nr_actions, scores, concedes, goal_from_shot, ld))) return rc;
+  if (a->n == 0) return SA_OK;
+  const int64_t lanes = (a->n + LANE_ACTS - 1) / LANE_ACTS;
+  const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
+  return with_flags([&](auto ATOMIC) {
+    hipLaunchKernelGGL((labels_kernel<ATOMIC()>), grid, block, 0, (hipStream_t)stream, *a, nr_actions, scores,
+                       concedes, goal_from_shot);
+    return check_launch("labels_kernel");
+  }, a->atomic != 0);
+}
+
+template <typename T>
+static int launch_formula(const sa_actions* a, const T* ps, const T* pc, T* off, T* def, T* val,
+                          void* stream) {
+  int rc = check_actions(a, false);
+  if (rc) return rc;
+  if ((rc = check_formula_args(ps, pc, off, def, val, "round_up(n, 4)"))) return rc;
+  if (a->n == 0) return SA_OK;
+  constexpr int V = 16 / sizeof(T);
+  const int64_t lanes = (a->n + V - 1) / V;
+  const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
+  const bool vec_ok = aligned16(ps) && aligned16(pc);
+  return with_flags([&](auto ATOMIC) {
+    hipLaunchKernelGGL((formula_kernel<ATOMIC(), T>), grid, block, 0, (hipStream_t)stream, *a, ps, pc, off, def,
+                       val, vec_ok);
+    return check_launch("formula_kernel");
+  }, a->atomic != 0);
+}
+
+extern "C" int sa_vaep_formula(const sa_actions* a, int32_t f32, const void* p_scores, const void* p_concedes,
+                               void* off, void* def, void* val, void* stream) {
+  if (f32 != 0 && f32 != 1) return fail(SA_EINVAL, "f32 must be 0 or 1");
+  return with_flags([&](auto F32) {
+    using T = std::conditional_t<F32(), float, double>;
+    return launch_formula<T>(a, (const T*)p_scores, (const T*)p_concedes, (T*)off, (T*)def, (T*)val, stream);
+  }, f32 != 0);
 }
 
 template <typename T>
 static int launch_labels_formula(const sa_actions* a, int32_t nr_actions, uint8_t* scores,
                                  uint8_t* concedes, uint8_t* goal_from_shot, int64_t ld, const T* ps,
-                                 const T* pc, T* off, T* def, T* val, void* stream);
+                                 const T* pc, T* off, T* def, T* val, void* stream) {
+  int rc = check_actions(a, false);
+  if (rc) return rc;
+  if ((rc = check_labels(a, nr_actions, scores, concedes, goal_from_shot, ld))) return rc;
+  if ((rc = check_formula_args(ps, pc, off, def, val, "round_up(n, 16)"))) return rc;
+  if (a->n == 0) return SA_OK;
+  const int64_t waves = (a->n + WAVE * LANE_ACTS - 1) / (WAVE * LANE_ACTS);
+  const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+  const bool vec_ok = aligned16(ps) && aligned16(pc);
+  return with_flags([&](auto ATOMIC) {
+    hipLaunchKernelGGL((labels_formula_kernel<ATOMIC(), T>), grid, block, 0, (hipStream_t)stream, *a, nr_actions,
+                       scores, concedes, goal_from_shot, ps, pc, off, def, val, vec_ok);
+    return check_launch("labels_formula_kernel");
+  }, a->atomic != 0);
+}
+
+extern "C" int sa_vaep_labels_formula(const sa_actions* a, int32_t nr_actions, uint8_t* scores,
+                                      uint8_t* concedes, uint8_t* goal_from_shot, int64_t ld, int32_t f32,
+                                      const void* p_scores, const void* p_concedes, void* off, void* def,
+                                      void* val, void* stream) {
+  if (f32 != 0 && f32 != 1) return fail(SA_EINVAL, "f32 must be 0 or 1");
+  return with_flags([&](auto F32) {
+    using T = std::conditional_t<F32(), float, double>;
+    return launch_labels_formula<T>(a, nr_actions, scores, concedes, goal_from_shot, ld, (const T*)p_scores,
+                                    (const T*)p_concedes, (T*)off, (T*)def, (T*)val, stream);
+  }, f32 != 0);
+}
 
 extern "C" int sa_vaep_step_f64(const sa_actions* a, const sa_feature_plan* plan, const sa_block* bool_out,
                                 const sa_block* f64_out, const sa_block* i64_out, int32_t xt_l, int32_t xt_w,
@@ -2258,18 +2303,15 @@ extern "C" int sa_vaep_step_f64(const sa_actions* a, const sa_feature_plan* plan
   int rc = check_actions(a, false);
   if (rc) return rc;
   if (!plan) return fail(SA_EINVAL, "null plan");
-  if (nr_actions < 1) return fail(SA_EINVAL, "nr_actions must be >= 1");
-  if ((rc = check_label_outputs(a->n, scores, concedes, goal_from_shot, ld))) return rc;
+  if ((rc = check_labels(a, nr_actions, scores, concedes, goal_from_shot, ld))) return rc;
   // all NULL: labels only (never with chunk_rows: its probabilities make the output checks apply)
   const bool formula = p_scores || p_concedes || off || def || val;
   if (formula && (rc = check_formula_args(p_scores, p_concedes, off, def, val, "round_up(n, 16)"))) return rc;
+  FeatReq q{bool_out, f64_out, i64_out};
   if (xt_cells) {
-    if (a->atomic) return fail(SA_EINVAL, "xT cells need SPADL actions");
-    if (xt_l < 1 || xt_w < 1 || (int64_t)xt_l * xt_w > SA_XT_CELLS_MAX_C)
-      return fail(SA_EINVAL, "xT cell codes need 1 <= l * w <= %d", SA_XT_CELLS_MAX_C);
-    if (!aligned16(xt_cells)) return fail(SA_EINVAL, "xt_cells must be 16-byte aligned");
+    if ((rc = check_xt_cells(a, xt_l, xt_w, xt_cells))) return rc;
+    q.xt = {xt_cells, xt_l, xt_w};
   }
-  FeatReq q{bool_out, f64_out, i64_out, xt_l, xt_w, xt_cells};
   // no fused form: the separate launches.  Atomic actions always take them: their numeric pass
   // (136 VGPRs, 3 waves per SIMD) loses more to the tail's registers than the tail's launch
   // costs (cfg3, 4.0e7 atomic actions: 3.89 ms separate vs 4.35 ms fused, scripts/atomic_ab.py,
@@ -2280,112 +2322,9 @@ extern "C" int sa_vaep_step_f64(const sa_actions* a, const sa_feature_plan* plan
     return launch_labels_formula<double>(a, nr_actions, scores, concedes, goal_from_shot, ld, p_scores,
                                          p_concedes, off, def, val, stream);
   }
-  const TailArgs t{nr_actions, scores, concedes, goal_from_shot, p_scores, p_concedes, off, def, val, chunk_rows,
-                   prefetch};
-  q.tail = &t;
+  q.tail = {nr_actions, scores, concedes, goal_from_shot, p_scores, p_concedes, off, def, val,
+            aligned16(p_scores) && aligned16(p_concedes)};
+  q.chunk = chunk_rows;
+  q.prefetch = prefetch;
   return launch_features(a, plan, q, stream);
-}
-
-extern "C" int sa_vaep_goalscore(const sa_actions* a, const sa_block* i64_out, int32_t col,
-                                 void* stream) {
-  int rc = check_actions(a, true);
-  if (rc) return rc;
-  if ((rc = check_block(i64_out, a->n, SA_NUM_TILE_QUANTUM, "i64"))) return rc;
-  if (col < 0 || col + 3 > i64_out->n_cols) return fail(SA_EINVAL, "goalscore columns outside the block");
-  if (a->n == 0) return SA_OK;
-  hipStream_t st = (hipStream_t)stream;
-  int64_t* blk = (int64_t*)i64_out->data;
-  const dim3 g4((unsigned)((a->n_segments + 3) / 4));  // one wave per segment
-  if (a->atomic)
-    hipLaunchKernelGGL((goalscore_wave16_kernel<true>), g4, dim3(256), 0, st, *a, blk,
-                       (int64_t)i64_out->n_cols, (int64_t)col, i64_out->tile_rows);
-  else
-    hipLaunchKernelGGL((goalscore_wave16_kernel<false>), g4, dim3(256), 0, st, *a, blk,
-                       (int64_t)i64_out->n_cols, (int64_t)col, i64_out->tile_rows);
-  return check_launch("goalscore_wave16_kernel");
-}
-
-extern "C" int sa_vaep_labels(const sa_actions* a, int32_t nr_actions, uint8_t* scores,
-                              uint8_t* concedes, uint8_t* goal_from_shot, int64_t ld, void* stream) {
-  int rc = check_actions(a, false);
-  if (rc) return rc;
-  if (nr_actions < 1) return fail(SA_EINVAL, "nr_actions must be >= 1");
-  if ((rc = check_label_outputs(a->n, scores, concedes, goal_from_shot, ld))) return rc;
-  if (a->n == 0) return SA_OK;
-  const int64_t lanes = (a->n + LANE_ACTS - 1) / LANE_ACTS;
-  const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (a->atomic)
-    hipLaunchKernelGGL((labels_kernel<true>), grid, block, 0, st, *a, nr_actions, scores, concedes,
-                       goal_from_shot);
-  else
-    hipLaunchKernelGGL((labels_kernel<false>), grid, block, 0, st, *a, nr_actions, scores, concedes,
-                       goal_from_shot);
-  return check_launch("labels_kernel");
-}
-
-template <typename T>
-static int launch_formula(const sa_actions* a, const T* ps, const T* pc, T* off, T* def, T* val,
-                          void* stream) {
-  int rc = check_actions(a, false);
-  if (rc) return rc;
-  if ((rc = check_formula_args(ps, pc, off, def, val, "round_up(n, 4)"))) return rc;
-  if (a->n == 0) return SA_OK;
-  constexpr int V = 16 / sizeof(T);
-  const int64_t lanes = (a->n + V - 1) / V;
-  const dim3 grid((unsigned)((lanes + 255) / 256)), block(256);
-  const bool vec_ok = aligned16(ps) && aligned16(pc);
-  hipStream_t st = (hipStream_t)stream;
-  if (a->atomic)
-    hipLaunchKernelGGL((formula_kernel<true, T>), grid, block, 0, st, *a, ps, pc, off, def, val, vec_ok);
-  else
-    hipLaunchKernelGGL((formula_kernel<false, T>), grid, block, 0, st, *a, ps, pc, off, def, val, vec_ok);
-  return check_launch("formula_kernel");
-}
-
-extern "C" int sa_vaep_formula(const sa_actions* a, int32_t f32, const void* p_scores, const void* p_concedes,
-                               void* off, void* def, void* val, void* stream) {
-  if (f32 != 0 && f32 != 1) return fail(SA_EINVAL, "f32 must be 0 or 1");
-  if (f32)
-    return launch_formula<float>(a, (const float*)p_scores, (const float*)p_concedes, (float*)off, (float*)def,
-                                 (float*)val, stream);
-  return launch_formula<double>(a, (const double*)p_scores, (const double*)p_concedes, (double*)off,
-                                (double*)def, (double*)val, stream);
-}
-
-template <typename T>
-static int launch_labels_formula(const sa_actions* a, int32_t nr_actions, uint8_t* scores,
-                                 uint8_t* concedes, uint8_t* goal_from_shot, int64_t ld, const T* ps,
-                                 const T* pc, T* off, T* def, T* val, void* stream) {
-  int rc = check_actions(a, false);
-  if (rc) return rc;
-  if (nr_actions < 1) return fail(SA_EINVAL, "nr_actions must be >= 1");
-  if ((rc = check_label_outputs(a->n, scores, concedes, goal_from_shot, ld))) return rc;
-  if ((rc = check_formula_args(ps, pc, off, def, val, "round_up(n, 16)"))) return rc;
-  if (a->n == 0) return SA_OK;
-  const int64_t waves = (a->n + WAVE * LANE_ACTS - 1) / (WAVE * LANE_ACTS);
-  const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-  const bool vec_ok = aligned16(ps) && aligned16(pc);
-  hipStream_t st = (hipStream_t)stream;
-  if (a->atomic)
-    hipLaunchKernelGGL((labels_formula_kernel<true, T>), grid, block, 0, st, *a, nr_actions, scores,
-                       concedes, goal_from_shot, ps, pc, off, def, val, vec_ok);
-  else
-    hipLaunchKernelGGL((labels_formula_kernel<false, T>), grid, block, 0, st, *a, nr_actions, scores,
-                       concedes, goal_from_shot, ps, pc, off, def, val, vec_ok);
-  return check_launch("labels_formula_kernel");
-}
-
-extern "C" int sa_vaep_labels_formula(const sa_actions* a, int32_t nr_actions, uint8_t* scores,
-                                      uint8_t* concedes, uint8_t* goal_from_shot, int64_t ld, int32_t f32,
-                                      const void* p_scores, const void* p_concedes, void* off, void* def,
-                                      void* val, void* stream) {
-  if (f32 != 0 && f32 != 1) return fail(SA_EINVAL, "f32 must be 0 or 1");
-  if (f32)
-    return launch_labels_formula<float>(a, nr_actions, scores, concedes, goal_from_shot, ld,
-                                        (const float*)p_scores, (const float*)p_concedes, (float*)off,
-                                        (float*)def, (float*)val, stream);
-  return launch_labels_formula<double>(a, nr_actions, scores, concedes, goal_from_shot, ld,
-                                       (const double*)p_scores, (const double*)p_concedes, (double*)off,
-                                       (double*)def, (double*)val, stream);
 }

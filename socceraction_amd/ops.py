@@ -210,17 +210,23 @@ def _ptr(t: Optional[torch.Tensor]):
     return t.data_ptr() if (t is not None and t.numel()) else None
 
 
+def _xt_cells_args(n: int, xt_cells: Optional[tuple]):
+    """``(l, w, cells)`` of a feature pass's optional ``xt_cells`` (None: 0, 0, None), cells checked."""
+    l, w, cells = xt_cells if xt_cells is not None else (0, 0, None)
+    if cells is not None and (cells.dtype != torch.int32 or cells.numel() < n):
+        raise ValueError('cells must be an int32 tensor of at least n elements')
+    return int(l), int(w), cells
+
+
 def features_into(s: _native.SaActions, out: FeatureBlocks, xt_cells: Optional[tuple] = None) -> None:
     """Launch the feature kernels into ``out``. ``xt_cells = (l, w, cells)``: the same pass also
     writes every action's xT cell code for a fit + rate on the (l, w) grid
     (``sa_vaep_features``' ``xt_cells``; ``cells`` from :func:`xt_cells_buffer`)."""
     bb, fb, ib = out.sa_blocks()
-    l, w, cells = xt_cells if xt_cells is not None else (0, 0, None)
-    if cells is not None and (cells.dtype != torch.int32 or cells.numel() < s.n):
-        raise ValueError('cells must be an int32 tensor of at least n elements')
+    l, w, cells = _xt_cells_args(s.n, xt_cells)
     _native.check(_native.lib().sa_vaep_features(
         ctypes.byref(s), ctypes.byref(out.plan.struct), ctypes.byref(bb), ctypes.byref(fb),
-        ctypes.byref(ib), int(l), int(w), _ptr(cells), stream_handle()))
+        ctypes.byref(ib), l, w, _ptr(cells), stream_handle()))
 
 
 def features(batch: ActionBatch, xfns: Sequence[str], k: int, flip: bool = True,
@@ -309,11 +315,16 @@ class LabelBlocks:
     goal_from_shot: torch.Tensor
 
 
+def _alloc_label_blocks(batch: ActionBatch) -> LabelBlocks:
+    """The three label columns as the rows of one ``[3, ld]`` uint8 tensor."""
+    buf = torch.empty((3, _ld(batch.n)), dtype=torch.uint8, device=batch.device)
+    return LabelBlocks(batch.n, buf[0], buf[1], buf[2])
+
+
 def labels(batch: ActionBatch, nr_actions: int = 10, out: Optional[LabelBlocks] = None) -> LabelBlocks:
     ld = _ld(batch.n)
     if out is None:
-        buf = torch.empty((3, ld), dtype=torch.uint8, device=batch.device)
-        out = LabelBlocks(batch.n, buf[0], buf[1], buf[2])
+        out = _alloc_label_blocks(batch)
     s = batch.struct()
     _native.check(_native.lib().sa_vaep_labels(ctypes.byref(s), int(nr_actions), _ptr(out.scores),
                                                _ptr(out.concedes), _ptr(out.goal_from_shot), ld,
@@ -352,8 +363,7 @@ def labels_formula(batch: ActionBatch, p_scores: torch.Tensor, p_concedes: torch
     dt = _check_probabilities(batch.n, p_scores, p_concedes)
     ld = _ld(batch.n)
     if labels_out is None:
-        buf = torch.empty((3, ld), dtype=torch.uint8, device=batch.device)
-        labels_out = LabelBlocks(batch.n, buf[0], buf[1], buf[2])
+        labels_out = _alloc_label_blocks(batch)
     if values_out is None:
         values_out = torch.empty((3, ld), dtype=dt, device=batch.device)
     ps, pc = p_scores.contiguous(), p_concedes.contiguous()
@@ -386,13 +396,11 @@ def step_into(s: _native.SaActions, out: FeatureBlocks, p_scores: Optional[torch
     else:  # features + labels only
         ps = pc = None
         o = (None, None, None)
-    l, w, cells = xt_cells if xt_cells is not None else (0, 0, None)
-    if cells is not None and (cells.dtype != torch.int32 or cells.numel() < s.n):
-        raise ValueError('cells must be an int32 tensor of at least n elements')
+    l, w, cells = _xt_cells_args(s.n, xt_cells)
     bb, fb, ib = out.sa_blocks()
     _native.check(_native.lib().sa_vaep_step_f64(
         ctypes.byref(s), ctypes.byref(out.plan.struct), ctypes.byref(bb), ctypes.byref(fb),
-        ctypes.byref(ib), int(l), int(w), _ptr(cells), int(nr_actions), _ptr(labels_out.scores),
+        ctypes.byref(ib), l, w, _ptr(cells), int(nr_actions), _ptr(labels_out.scores),
         _ptr(labels_out.concedes), _ptr(labels_out.goal_from_shot), _ld(s.n), _ptr(ps), _ptr(pc),
         _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), int(chunk_rows), int(prefetch), stream_handle()))
 

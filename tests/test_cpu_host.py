@@ -196,6 +196,34 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     assert einval(step(win, 100), b'chunk_rows must be a non-negative multiple of 512')
     assert einval(step(atomic, 512), b'the chunked step takes the fused SPADL step form')
     assert einval(step(atomic, 0), b'n_frames') and b'chunked' not in lib.sa_last_error()
+    # the label and xT-cell checks are stated once in the library: each of their messages comes
+    # through every entry point that makes them.  An empty windowed batch (n = 0, no columns)
+    # passes the batch checks, and a valid call on it returns SA_OK before any HIP call
+    empty, empty_atomic = _native.SaActions(), _native.SaActions()
+    empty.n, empty.n_segments, empty.n_frames = 0, 0, 1
+    empty_atomic.n, empty_atomic.n_segments, empty_atomic.n_frames, empty_atomic.atomic = 0, 0, 1, 1
+    no_cols = _native.SaFeaturePlan()  # a plan that writes no column
+    no_cols.nb_prev_actions = 3
+    for x in range(_native.SA_XFN_COUNT):
+        no_cols.bool_col[x] = no_cols.f64_col[x] = no_cols.i64_col[x] = -1
+    step_empty = lambda a, l, w, cells, nr, sc, ld: lib.sa_vaep_step_f64(  # noqa: E731
+        ref(a), ref(no_cols), None, None, None, l, w, cells, nr, sc, fake, fake, ld, fake, fake, fake, fake, fake,
+        0, 0, None)
+    label_calls = (
+        lambda nr, sc, ld: lib.sa_vaep_labels(ref(empty), nr, sc, fake, fake, ld, None),
+        lambda nr, sc, ld: lib.sa_vaep_labels_formula(ref(empty), nr, sc, fake, fake, ld, 0, fake, fake, fake, fake,
+                                                      fake, None),
+        lambda nr, sc, ld: step_empty(empty, 0, 0, None, nr, sc, ld))
+    for call in label_calls:
+        assert call(10, fake, 16) == _native.SA_OK
+        assert einval(call(0, fake, 16), b'nr_actions must be >= 1')
+        assert einval(call(10, fake, 8), b'ld must be a multiple of 16 and >= round_up(n, 16)')
+        assert einval(call(10, ctypes.c_void_p(260), 16), b'label outputs must be 16-byte aligned')
+    assert step_empty(empty, 16, 12, fake, 10, fake, 16) == _native.SA_OK
+    assert einval(step_empty(empty, 16, 12, ctypes.c_void_p(260), 10, fake, 16), b'xt_cells must be 16-byte aligned')
+    assert einval(step_empty(empty, 4097, 1, fake, 10, fake, 16), b'xT cell codes need 1 <= l * w')
+    assert einval(step_empty(empty_atomic, 16, 12, fake, 10, fake, 16), b'xT cells need SPADL actions')
+    assert lib.sa_vaep_features(ref(empty), ref(no_cols), None, None, None, 16, 12, fake, None) == _native.SA_OK
     sorted_frame = _native.SaSpadlFrame()
     sorted_frame.order = 256
     n_out = ctypes.c_int64(0)

@@ -9,8 +9,10 @@ so are the f64 feature columns that are not angles and the f64 and f32 formula
 (golden_io.assert_same_floats); the angle columns lie within value_cases.ANGLE_ULPS ulps of the
 200-bit value (one more against a golden of the reference).
 
-The instantiations ``launch_features`` picks from, SPADL and atomic each, and the test here that
-checks them against the oracle or the reference:
+The instantiations ``launch_features`` can reach, SPADL and atomic each -- its flag dispatch
+excludes every other combination at compile time (EXPLICIT never with BITS or WIDE; TAIL, N32 and
+COND only windowed with KF = 3 and one at a time; TAIL only SPADL), so no other kernel exists --
+and the test here that checks them against the oracle or the reference:
 
 ==========================================================  =====================================
 ``bool_colgroup_kernel<A, EXPLICIT, BITS, WIDE>``
@@ -34,9 +36,8 @@ N32                                                         test_float32_and_con
 Not here: COND with its tables in global memory needs thousands of numeric conditions, which
 tests/test_gpu_tree_boundaries.py::test_condition_tables_in_global_memory checks against the
 oracle; the chunked TAIL launches are a benchmark probe that tests/test_gpu_parity.py compares
-with the step checked here; ``<true, false, 3, true>`` (atomic TAIL) is instantiated but no
-entry point reaches it: ``sa_vaep_step_f64`` gives atomic actions the separate launches, which
-test_step_vs_oracle checks through the same call.
+with the step checked here.  There is no atomic TAIL kernel: ``sa_vaep_step_f64`` gives atomic
+actions the separate launches, which test_step_vs_oracle checks through the same call.
 """
 import numpy as np
 import pytest
