@@ -86,11 +86,16 @@ class Arena:
     """Guarded allocations of one fill: keeps every backing buffer alive, counts them, and reads
     the guards (and the bodies of rehomed inputs) back in :meth:`check`."""
 
-    def __init__(self, fill: int, device_type: str = 'cuda'):
+    def __init__(self, fill: int, device_type: str = 'cuda', fill_stream=None):
         if not 0 <= int(fill) <= 255:
             raise ValueError('fill is one byte')
         self.fill = int(fill)
         self.device_type = device_type
+        # None: the fill is ordered on the requester's current stream, like the allocation's first
+        # use.  A stream: the fill runs there and is waited for before the body is handed out, so
+        # the poison is in memory whatever the requester's stream is waiting for
+        # (tests/test_gpu_streams.py builds under a stalled stream).
+        self.fill_stream = fill_stream
         self.allocs: List[_Alloc] = []
         self.count = 0          # guarded allocations
         self.passed_through = 0  # requests handed to the original (no guard)
@@ -102,13 +107,24 @@ class Arena:
         for s in shape:
             numel *= s
         nbytes = numel * _itemsize(dtype)
-        backing = _full((GUARD + nbytes + GUARD,), self.fill, dtype=torch.uint8, device=device)
-        body = backing[GUARD:GUARD + nbytes]
-        if zero:
-            body.zero_()
+        with self._filling():
+            backing = _full((GUARD + nbytes + GUARD,), self.fill, dtype=torch.uint8, device=device)
+            body = backing[GUARD:GUARD + nbytes]
+            if zero:
+                body.zero_()
         self.allocs.append(_Alloc(backing, nbytes, shape, dtype, site or _call_site()))
         self.count += 1
         return body.view(dtype).view(shape)
+
+    @contextlib.contextmanager
+    def _filling(self):
+        """The stream the fill runs on; with a ``fill_stream``, waited for on the way out."""
+        if self.fill_stream is None:
+            yield
+            return
+        with torch.cuda.stream(self.fill_stream):
+            yield
+        self.fill_stream.synchronize()
 
     def rehome(self, t: torch.Tensor, site: Optional[str] = None) -> torch.Tensor:
         """A guarded copy of ``t`` (made contiguous); its bytes are checked by :meth:`check`."""
@@ -216,18 +232,20 @@ def _make(arena: Arena, orig: Callable, zero: bool, like: bool, method: bool) ->
             if dev.type == arena.device_type and isinstance(dtype, torch.dtype):
                 return arena.alloc(size, dtype, dev, zero, site)
         arena.passed_through += 1
-        return _fill_passed(orig(*args, **kw), arena.fill, zero)
+        t = orig(*args, **kw)
+        with arena._filling():
+            return _fill_passed(t, arena.fill, zero)
     wrapper.__wrapped__ = orig
     return wrapper
 
 
 @contextlib.contextmanager
-def guarded_allocations(fill: int, device_type: str = 'cuda'):
+def guarded_allocations(fill: int, device_type: str = 'cuda', fill_stream=None):
     """Serve the ``empty`` / ``zeros`` family from guarded, ``fill``-poisoned allocations for the
     duration of the body (see the module docstring); yields the :class:`Arena`.  The originals
     are back when the body ends, also when it raises, and the guards are checked on a normal
-    exit."""
-    arena = Arena(fill, device_type)
+    exit.  ``fill_stream``: see :class:`Arena`."""
+    arena = Arena(fill, device_type, fill_stream)
     saved = []
     try:
         for name in _PATCHED_TORCH:

@@ -22,6 +22,11 @@ binary scores and grouped sums (test_chained_consumers).  What a producer leaves
 poison for its consumer.  Where a builder's row count is even the case also
 runs with the last row dropped, so end-of-column vector loads meet an odd n.
 
+Each family's cases are a module-level generator ``cases_<family>(sa, ...)`` that yields
+``(family, case)``; ``test_<family>`` runs every yielded ``case(run)`` through :func:`both_fills`,
+and tests/test_gpu_streams.py drives the same closures through another runner.  The closures read
+the generator's loop variables, so a consumer runs each case before it asks for the next.
+
 Regions WITHOUT a contract -- compared up to ``n`` only; the chained consumers are the proof that
 nothing reads them:
 
@@ -174,15 +179,14 @@ def _cut_ref(ref, n):
             None if exact is None else {k: v[:n] for k, v in exact.items()})
 
 
-@pytest.mark.parametrize('drop', [0, 1], ids=['n_even', 'n_odd'])
-@pytest.mark.parametrize('atomic', [False, True], ids=['spadl', 'atomic'])
-def test_vaep_kernels(sa, atomic, drop):
+def cases_vaep_kernels(sa, atomic, drop):
     """sa_vaep.hip on the segment-edge batch of tests/window_cases.py (7190 rows; 7189 with the
     last row dropped): features in byte, bitmap and float32 forms at k = 3 and at ``BOOL_HALO + 2``
     (the wide bool pass), labels and labels + formula at nr_actions 10 and ``LABELS_WINDOW``, the
     formula in f64 and f32, the fused step at k = 3
     -- each against the oracle through the helpers of tests/test_gpu_windows.py.  The bitmap-form
-    blocks then feed a small xgboost-shaped learner (staged walk, gather walk, condition bitmaps)."""
+    blocks then feed a small xgboost-shaped learner (staged walk, gather walk, condition bitmaps).
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import test_gpu_windows as tw
     import window_cases as wc
     from oracle import vaep_oracle as vo
@@ -277,13 +281,20 @@ def test_vaep_kernels(sa, atomic, drop):
             assert torch.equal(codes, ops.xt_cell_codes(run.call(ops.xt_cells, ab, 16, 12), n, 16, 12)), tag
             run.keep('step cell codes', codes)
 
-    both_fills('vaep', case)
+    yield 'vaep', case
 
 
+@pytest.mark.parametrize('drop', [0, 1], ids=['n_even', 'n_odd'])
 @pytest.mark.parametrize('atomic', [False, True], ids=['spadl', 'atomic'])
-def test_vaep_explicit_frames(sa, atomic):
+def test_vaep_kernels(sa, atomic, drop):
+    for family, case in cases_vaep_kernels(sa, atomic, drop):
+        both_fills(family, case)
+
+
+def cases_vaep_explicit_frames(sa, atomic):
     """The EXPLICIT instantiations: SA_MAX_FRAMES permuted frames of 1041 rows (one bool tile,
-    one lane and one row), every frame's columns rehomed."""
+    one lane and one row), every frame's columns rehomed.
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import test_gpu_windows as tw
     import window_cases as wc
     B, ops, N = sa['batch'], sa['ops'], sa['native']
@@ -302,13 +313,17 @@ def test_vaep_explicit_frames(sa, atomic):
         for kind in 'bfi':
             run.keep(f'{kind} block', fb.block(kind))
 
-    both_fills('vaep explicit', case)
+    yield 'vaep explicit', case
+
+
+@pytest.mark.parametrize('atomic', [False, True], ids=['spadl', 'atomic'])
+def test_vaep_explicit_frames(sa, atomic):
+    for family, case in cases_vaep_explicit_frames(sa, atomic):
+        both_fills(family, case)
 
 
 # =============================================================================== producers into consumers
-@pytest.mark.parametrize('drop', [0, 1], ids=['n_even', 'n_odd'])
-@pytest.mark.parametrize('atomic', [False, True], ids=['spadl', 'atomic'])
-def test_chained_consumers(sa, atomic, drop):
+def cases_chained_consumers(sa, atomic, drop):
     """What a producer leaves unwritten is live poison for its consumer.  On the segment-edge
     batch, everything made under the fill: the k = 3 bitmap-form blocks and the labels feed the
     logistic moments (limb sums at beta = 0 == the oracle's integers over the oracle's own feature
@@ -317,7 +332,8 @@ def test_chained_consumers(sa, atomic, drop):
     formula of those probabilities, bit for bit), the binary scores against the device labels
     (counts, Brier limbs and U2 == the integer restatements of tests/test_gpu_metrics.py) and,
     with the formula's values, the grouped sums by action type (== the integer restatement of
-    tests/test_gpu_ratings.py)."""
+    tests/test_gpu_ratings.py).
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import linear_reference as lr
     import test_gpu_metrics as tm
     import test_gpu_ratings as tg
@@ -401,7 +417,14 @@ def test_chained_consumers(sa, atomic, drop):
         assert torch.equal(sums.count.cpu(), torch.from_numpy(want_c)), tag
         run.keep('group sums', sums.buf)
 
-    both_fills('chained', case)
+    yield 'chained', case
+
+
+@pytest.mark.parametrize('drop', [0, 1], ids=['n_even', 'n_odd'])
+@pytest.mark.parametrize('atomic', [False, True], ids=['spadl', 'atomic'])
+def test_chained_consumers(sa, atomic, drop):
+    for family, case in cases_chained_consumers(sa, atomic, drop):
+        both_fills(family, case)
 
 
 # =============================================================================== tree inference
@@ -415,15 +438,14 @@ def _rehome_cond_cache(run, te):
                       for w in cache['walks']]
 
 
-@pytest.mark.parametrize('drop', [0, 1], ids=['n', 'n_minus_1'])
-@pytest.mark.parametrize('config', ['spadl_k3', 'atomic_k3'])
-def test_tree_inference(sa, config, drop):
+def cases_tree_inference(sa, config, drop):
     """sa_trees.hip and the condition passes on the boundary models of
     tests/tree_boundary_models.py (thresholds ON the batch, NaN coordinates, depths 1..5): the
     feature blocks are made under the fill, the model tables are rehomed, and the gather and the
     staged walks over tiled, plain and bitmap blocks and predict_pair_conditions equal the oracle
     at the bars of tests/test_gpu_tree_boundaries.py (float32 rtol 1e-6, float64 rtol 1e-12), on
-    the whole batch and on the batch cut one row short (segments end at the cut)."""
+    the whole batch and on the batch cut one row short (segments end at the cut).
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import test_gpu_tree_boundaries as tb
     import tree_boundary_models as bm
     from oracle import tree_oracle as to
@@ -469,16 +491,23 @@ def test_tree_inference(sa, config, drop):
             tb._assert_close(got, lrn['ref32'][:n], 1e-6, f'{tag} conditions, learner {q}')
             run.keep(f'conditions learner {q}', got)
 
-    both_fills('trees', case)
+    yield 'trees', case
+
+
+@pytest.mark.parametrize('drop', [0, 1], ids=['n', 'n_minus_1'])
+@pytest.mark.parametrize('config', ['spadl_k3', 'atomic_k3'])
+def test_tree_inference(sa, config, drop):
+    for family, case in cases_tree_inference(sa, config, drop):
+        both_fills(family, case)
 
 
 # =============================================================================== select, top-k, sums, metrics, moments
-@pytest.mark.parametrize('variant', ['f64', 'f32', 'atomic'])
-def test_select_rows(sa, variant):
+def cases_select_rows(sa, variant):
     """sa_select.hip on the source of tests/test_gpu_select.py made under the fill: the row lists
     ``edges``, ``repeats``, ``m65`` and ``m0`` equal the numpy restatement byte for byte, zero
     padding rows ``m .. ld - 1`` and clear tail bits included; the selected blocks then feed the
-    staged tree walk."""
+    staged tree walk.
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import test_gpu_select as ts
     from oracle import vaep_oracle as vo
     B, ops, syn, trees = sa['batch'], sa['ops'], sa['synthetic'], sa['trees']
@@ -515,13 +544,19 @@ def test_select_rows(sa, variant):
                     p = run.call(te.predict_blocks, got, method='staged')
                     assert torch.equal(p, whole[torch.from_numpy(rows.astype(np.int64)).cuda()]), which
 
-        both_fills('select', case)
+        yield 'select', case
 
 
-@pytest.mark.parametrize('f32', [False, True], ids=['f64', 'f32'])
-def test_top_rows(sa, f32):
+@pytest.mark.parametrize('variant', ['f64', 'f32', 'atomic'])
+def test_select_rows(sa, variant):
+    for family, case in cases_select_rows(sa, variant):
+        both_fills(family, case)
+
+
+def cases_top_rows(sa, f32):
     """sa_topk.hip: the tie-heavy pool column of 2 * CHUNK + 2 rows (and of one row fewer) with a
-    keep mask, k = 7 and CHUNK + 3, both directions, against tests/top_rows_reference.py."""
+    keep mask, k = 7 and CHUNK + 3, both directions, against tests/top_rows_reference.py.
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import test_gpu_top_rows as tt
     import top_rows_reference as tr
     ops = sa['ops']
@@ -536,15 +571,21 @@ def test_top_rows(sa, f32):
                         run.keep(f'k={k} largest={largest} keep={mask is not None} rows', rows)
                         run.keep(f'k={k} largest={largest} keep={mask is not None} vals', vals)
 
-        both_fills('top-k', case)
+        yield 'top-k', case
 
 
-@pytest.mark.parametrize('V,f32', [(8, False), (3, True)], ids=['8xf64', '3xf32'])
-def test_group_sums(sa, V, f32):
+@pytest.mark.parametrize('f32', [False, True], ids=['f64', 'f32'])
+def test_top_rows(sa, f32):
+    for family, case in cases_top_rows(sa, f32):
+        both_fills(family, case)
+
+
+def cases_group_sums(sa, V, f32):
     """sa_group.hip at G = 40 (the ``skipped`` key pattern of tests/test_gpu_ratings.py: 40 groups,
     a fifth of the rows skipped) at 65 rows, one chunk and one row, and 5000 / 4999 rows: limbs
     and counts equal the integer restatement, finalize() the Python-integer rounding; the whole
-    accumulator buffer is the same under both fills."""
+    accumulator buffer is the same under both fills.
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import test_gpu_ratings as tg
     ops = sa['ops']
     v, limbs = tg.values(f32)
@@ -565,14 +606,20 @@ def test_group_sums(sa, V, f32):
             run.keep('buf', acc.buf)
             run.keep('finalize', fin)
 
-        both_fills('group sums', case)
+        yield 'group sums', case
 
 
-@pytest.mark.parametrize('f32', [False, True], ids=['f64', 'f32'])
-def test_binary_metrics(sa, f32):
+@pytest.mark.parametrize('V,f32', [(8, False), (3, True)], ids=['8xf64', '3xf32'])
+def test_group_sums(sa, V, f32):
+    for family, case in cases_group_sums(sa, V, f32):
+        both_fills(family, case)
+
+
+def cases_binary_metrics(sa, f32):
     """sa_metrics.hip: the sums at one chunk and one row (4097) against the integer restatement
     and scikit-learn, and the exact AUROC count with 1025 minority keys of either class (one more
-    than the LDS sample holds) at 5000 and 4999 rows."""
+    than the LDS sample holds) at 5000 and 4999 rows.
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import test_gpu_metrics as tm
     ops = sa['ops']
     y, p, limbs = tm.rows(f32)
@@ -589,7 +636,7 @@ def test_binary_metrics(sa, f32):
         assert abs(res['log_loss'] - want) <= 1e-12 * want
         run.keep('sums', acc.buf)
 
-    both_fills('metrics', sums)
+    yield 'metrics', sums
     for name in (f'm={tm.SAMPLE + 1}', f'm={tm.SAMPLE + 1}_negatives'):
         y0, p0 = tm.auc_case(name, f32)
         assert len(y0) % 2 == 0
@@ -604,16 +651,22 @@ def test_binary_metrics(sa, f32):
                 assert tm.ulps(res['auroc'], tm.roc_auc_score(ya, pa.astype(np.float64))) <= 2
                 run.keep('auc', acc.buf)
 
-            both_fills('metrics', auc)
+            yield 'metrics', auc
 
 
-@pytest.mark.parametrize('cols', ['xg46', 'vaep568'])
-def test_logistic_moments(sa, cols):
+@pytest.mark.parametrize('f32', [False, True], ids=['f64', 'f32'])
+def test_binary_metrics(sa, f32):
+    for family, case in cases_binary_metrics(sa, f32):
+        both_fills(family, case)
+
+
+def cases_logistic_moments(sa, cols):
     """sa_linear.hip on the blocks of tests/test_gpu_linear.py (129 rows in tiles of 16, poison in
     the tiles' padding and set tail bits) rehomed: the limb sums at beta = 0 equal the oracle's
     integers, the moments at a non-zero beta lie within that file's 1e-12 of each entry's sum of
     |terms|, and predict_blocks of a model with that beta (the kernel's last rows end inside a
-    tile and a bitmap word) lies within that file's 4 ulps of the oracle's sigmoid in f64 and f32."""
+    tile and a bitmap word) lies within that file's 4 ulps of the oracle's sigmoid in f64 and f32.
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import linear_reference as lr
     import test_gpu_linear as tl
     lin = sa['linear']
@@ -659,7 +712,13 @@ def test_logistic_moments(sa, cols):
             assert tl._ulps(got, want_p.astype(ndt)).max() <= 4, ndt
             run.keep(f'predict {np.dtype(ndt).name}', p)
 
-    both_fills('logistic moments', case)
+    yield 'logistic moments', case
+
+
+@pytest.mark.parametrize('cols', ['xg46', 'vaep568'])
+def test_logistic_moments(sa, cols):
+    for family, case in cases_logistic_moments(sa, cols):
+        both_fills(family, case)
 
 
 # =============================================================================== xT
@@ -679,12 +738,12 @@ def _xt_games(sa):
     return _XT['variants']
 
 
-@pytest.mark.parametrize('l,w', [(16, 12), (30, 20), (40, 30)])
-def test_xt_small_grids(sa, l, w):
+def cases_xt_small_grids(sa, l, w):
     """sa_xt.hip on 30 synthetic games: count == xt_oracle's counts; the solve in both summation
     orders == xt_oracle.solve (bit for bit up to 1024 cells and in the reference's order; the
     reordered sums of the 1200-cell grid within the 1e-12 of tests/test_gpu_xt_large.py, same
-    iteration count); the rate of the surface == xt_oracle.rate."""
+    iteration count); the rate of the surface == xt_oracle.rate.
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     from oracle import xt_oracle as xo
     from xt_count_checks import ref_counts, same_counts
     B, ops = sa['batch'], sa['ops']
@@ -737,16 +796,23 @@ def test_xt_small_grids(sa, l, w):
                 _same_rate(got.cpu().numpy(), rated, f'{tag} xt_rate_codes')
                 run.keep('rate from codes', got)
 
-        both_fills('xT small grids', case)
+        yield 'xT small grids', case
 
 
-def test_xt_large_grid(sa):
+@pytest.mark.parametrize('l,w', [(16, 12), (30, 20), (40, 30)])
+def test_xt_small_grids(sa, l, w):
+    for family, case in cases_xt_small_grids(sa, l, w):
+        both_fills(family, case)
+
+
+def cases_xt_large_grid(sa):
     """sa_xt_large.hip at 105 x 68: the band count with interpolated-rate operands and without
     the dense table (every buffer of the fit poisoned, the accumulator's counts included: the
     overwriting count never reads them), its compact rows == xt_oracle's counts; the solve in both
     orders against the sparse restatement of xt_oracle.solve (tests/xt_dispatch_cases.py); the
     interpolated rate from coordinates, from the operand codes and fused behind the solve ==
-    xt_oracle.rate; at 120 x 68 the rate kernel that does not stage its tables in LDS."""
+    xt_oracle.rate; at 120 x 68 the rate kernel that does not stage its tables in LDS.
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import xt_dispatch_cases as dc
     from golden_io import assert_close
     from oracle import xt_oracle as xo
@@ -815,7 +881,12 @@ def test_xt_large_grid(sa):
             assert_close(got.cpu().numpy(), rated120, f'{tag} xt_rate_interp 120x68')
             run.keep('rate 120x68', got)
 
-        both_fills('xT large grid', case)
+        yield 'xT large grid', case
+
+
+def test_xt_large_grid(sa):
+    for family, case in cases_xt_large_grid(sa):
+        both_fills(family, case)
 
 
 # =============================================================================== convert, dribbles
@@ -825,13 +896,13 @@ def _rehome_cols(run, cols):
         cols[k] = arena.rehome(cols[k])
 
 
-@pytest.mark.parametrize('what', ['convert', 'dribbles'])
-def test_atomic_scan_tile(sa, what):
+def cases_atomic_scan_tile(sa, what):
     """sa_atomic.hip one block past the scan's first tile (SA_ATOMIC_SCAN_TILE * 256 + 1 rows, odd):
     the device expansion of the rehomed frame, every output column and the row count against the
     oracle's output for the 30-game base, as tests/test_gpu_convert.py and test_gpu_dribbles.py
     compare it; the output columns are carved from one poisoned buffer and are the same bytes
-    under both fills."""
+    under both fills.
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import convert_cases as cc
     import test_gpu_convert as tc
     import test_gpu_dribbles as td
@@ -862,14 +933,20 @@ def test_atomic_scan_tile(sa, what):
         for c in sorted(out.cols):
             run.keep(c, out.cols[c][:out.n])
 
-    both_fills('convert / dribbles', case)
+    yield 'convert / dribbles', case
 
 
-@pytest.mark.parametrize('layout', ['as_built', 'as_built_odd', 'duplicated_keys'])
-def test_convert_group_shapes(sa, layout):
+@pytest.mark.parametrize('what', ['convert', 'dribbles'])
+def test_atomic_scan_tile(sa, what):
+    for family, case in cases_atomic_scan_tile(sa, what):
+        both_fills(family, case)
+
+
+def cases_convert_group_shapes(sa, layout):
     """convert_to_atomic on the enumeration of every group shape (tests/convert_cases.py: 152,352
     rows; one fewer; repeated keys through the general path) == the four-pass restatement, floats
-    bit for bit, with every allocation of the public function poisoned and guarded."""
+    bit for bit, with every allocation of the public function poisoned and guarded.
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import convert_cases as cc
     import pandas as pd
     import test_gpu_convert as tc
@@ -888,12 +965,18 @@ def test_convert_group_shapes(sa, layout):
         tc._assert_exact(tc._cols(out), ref, layout)
         run.keep_frame('atomic', out)
 
-    both_fills('convert / dribbles', case)
+    yield 'convert / dribbles', case
 
 
-@pytest.mark.parametrize('layout', ['per_game_ids', 'per_game_ids_odd', 'global_ids'])
-def test_add_dribbles_group_shapes(sa, layout):
-    """_add_dribbles on the same enumeration == the restatement, every column bit for bit."""
+@pytest.mark.parametrize('layout', ['as_built', 'as_built_odd', 'duplicated_keys'])
+def test_convert_group_shapes(sa, layout):
+    for family, case in cases_convert_group_shapes(sa, layout):
+        both_fills(family, case)
+
+
+def cases_add_dribbles_group_shapes(sa, layout):
+    """_add_dribbles on the same enumeration == the restatement, every column bit for bit.
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import convert_cases as cc
     import pandas as pd
     import test_gpu_dribbles as td
@@ -911,7 +994,13 @@ def test_add_dribbles_group_shapes(sa, layout):
         td._vs_oracle_exact(got, df, layout)
         run.keep_frame('with dribbles', got)
 
-    both_fills('convert / dribbles', case)
+    yield 'convert / dribbles', case
+
+
+@pytest.mark.parametrize('layout', ['per_game_ids', 'per_game_ids_odd', 'global_ids'])
+def test_add_dribbles_group_shapes(sa, layout):
+    for family, case in cases_add_dribbles_group_shapes(sa, layout):
+        both_fills(family, case)
 
 
 # =============================================================================== the learner
@@ -952,9 +1041,10 @@ def _keep_fit(run, clf):
     run.keep('recorded margin', clf.record_['margin'])
 
 
-def test_learner_plain_fit(sa):
+def cases_learner_plain_fit(sa):
     """sa_boost.hip: five rounds of depth 3 on the table, replayed round by round against
-    tests/boost_reference.py (tests/test_gpu_boost.py::_replay: node tables and margins as bytes)."""
+    tests/boost_reference.py (tests/test_gpu_boost.py::_replay: node tables and margins as bytes).
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import boost_reference as br
     import boost_shard_cases as C
     import test_gpu_boost as tgb
@@ -969,12 +1059,18 @@ def test_learner_plain_fit(sa):
         assert tgb._replay(clf, params, T['B'], T['y'], T['cuts']) >= params['n_estimators']
         _keep_fit(run, clf)
 
-    both_fills('learner', case)
+    yield 'learner', case
 
 
-def test_learner_tuned_fit(sa):
+def test_learner_plain_fit(sa):
+    for family, case in cases_learner_plain_fit(sa):
+        both_fills(family, case)
+
+
+def cases_learner_tuned_fit(sa):
     """Weights (the last row's lifts the quantisation shift), row and column samples and the L1
-    penalty against tests/boost_sample_reference.py, as tests/test_gpu_boost_shard.py replays them."""
+    penalty against tests/boost_sample_reference.py, as tests/test_gpu_boost_shard.py replays them.
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import boost_reference as br
     import boost_sample_reference as bsr
     import boost_shard_cases as C
@@ -1009,13 +1105,19 @@ def test_learner_tuned_fit(sa):
         assert (clf.trees_['feature'] >= 0).sum() >= params['n_estimators']
         _keep_fit(run, clf)
 
-    both_fills('learner', case)
+    yield 'learner', case
 
 
-def test_learner_early_stopping(sa):
+def test_learner_tuned_fit(sa):
+    for family, case in cases_learner_tuned_fit(sa):
+        both_fills(family, case)
+
+
+def cases_learner_early_stopping(sa):
     """Early stopping by the log loss of held-out rows (the split of the two-rank case of
     tests/boost_shard_cases.py, on one device) against tests/boost_stop_reference.py: every
-    round's tree, the metric integers within 1e-12, the stopping round, the kept model."""
+    round's tree, the metric integers within 1e-12, the stopping round, the kept model.
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import boost_reference as br
     import boost_shard_cases as C
     import boost_stop_reference as bst
@@ -1064,17 +1166,21 @@ def test_learner_early_stopping(sa):
         run.keep('held-out p', clf.record_['eval_p'])
         run.keep('metric integers', np.array([str(v) for v in series]))
 
-    both_fills('learner', case)
+    yield 'learner', case
+
+
+def test_learner_early_stopping(sa):
+    for family, case in cases_learner_early_stopping(sa):
+        both_fills(family, case)
 
 
 # =============================================================================== pandas boundary, public path
-@pytest.mark.parametrize('chunks', ['one_game', 'default'])
-@pytest.mark.parametrize('atomic', [False, True], ids=['spadl', 'atomic'])
-def test_pandas_boundary(sa, atomic, chunks):
+def cases_pandas_boundary(sa, atomic, chunks):
     """pipeline.value_frames through compute_batch on the edge frame of tests/boundary_cases.py
     (string team ids, absent homes) at one-game chunks and at the default chunk size: features,
     labels and the f64 formula against the oracle as tests/test_gpu_boundary.py checks them, with
-    every slot, staging buffer and batch of the pipeline poisoned (the pinned ones too)."""
+    every slot, staging buffer and batch of the pipeline poisoned (the pinned ones too).
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import boundary_cases as bc
     import test_gpu_boundary as tbd
     import window_cases as wc
@@ -1092,14 +1198,22 @@ def test_pandas_boundary(sa, atomic, chunks):
         for name, frame in zip(('features', 'labels', 'values'), out):
             run.keep_frame(name, frame)
 
-    both_fills('pandas boundary', case)
+    yield 'pandas boundary', case
 
 
-def test_public_path(sa):
+@pytest.mark.parametrize('chunks', ['one_game', 'default'])
+@pytest.mark.parametrize('atomic', [False, True], ids=['spadl', 'atomic'])
+def test_pandas_boundary(sa, atomic, chunks):
+    for family, case in cases_pandas_boundary(sa, atomic, chunks):
+        both_fills(family, case)
+
+
+def cases_public_path(sa):
     """fit_batch -> rate_batch -> score_batch -> rate_players -> top_actions on the nine small
     games of tests/boost_shard_cases.py, every call under the fill: each result is byte for byte
     the unguarded call's (the paths the other cases of this module and the existing suite hold
-    to their oracles), and the same under both fills."""
+    to their oracles), and the same under both fills.
+    Yields ``(family, case)``: run each case before asking for the next (module docstring)."""
     import json
 
     import boost_shard_cases as C
@@ -1130,4 +1244,9 @@ def test_public_path(sa):
             run.keep_frame(k, got[k])
         run.keep('scores', np.array(json.dumps(got['scores'], sort_keys=True)))
 
-    both_fills('public path', case)
+    yield 'public path', case
+
+
+def test_public_path(sa):
+    for family, case in cases_public_path(sa):
+        both_fills(family, case)
